@@ -6,17 +6,25 @@ SEM, l2 loss, "data mode": X row-sharded over the N ranks, each step computes
 Z_k = X_k^T (X_k (I - W)) on MFMA, all-reduces Z over RCCL/xGMI, then runs the
 replicated log-det/inverse and fused Adam update.  Strong scaling (n fixed).
 
-On rank 0 at N=1 it also reports (same run, same box)
+A plain run does what the headline needs and no more: it generates X, warms up, times --steps
+steps and prints the JSON line (metric, value, unit, ms_per_step, ..., and sem_generator: the
+GPU SEM generator's time for this rank's X shard, measured while setting up).  --dump-outputs DIR
+also writes what the timed steps computed (W and the loop's counters) as DIR/<name>.npy, from
+inputs that depend only on the arguments, so two builds can be compared output for output.
+
+With --full, on rank 0 at N=1, it also reports (same run, same box)
+  * value_check : every leg's W against the CPU oracle's run of the same steps;
   * cpu_baseline : the workload's own math (data-mode step) on the host cores, CPU oracle;
   * cpu_reference_algorithm / cov_mode : BASELINE config 2 (d=1000, n=1e4) with the
     reference's own algorithm (cov = X^T X / n once, O(d^3) per step) on the CPU and the GPU;
   * full_fit : DagmaLinear('l2').fit defaults at config 2, wall-clock (the metric's 2nd half);
   * config3 : d=5000, n=5e4 cov mode, with its CPU reference-algorithm baseline;
   * config5 : DagmaNonlinear Adam steps at dims [200, 10, 1], n=1000, with its CPU oracle;
-  * sem_generator : the GPU SEM generator's time for this rank's X shard;
-  * roofline : the dominant data-mode GEMM vs the FP64 MFMA peak, PMC HBM traffic.
+  * roofline : the dominant data-mode GEMM vs the FP64 MFMA peak, PMC HBM traffic;
+and at N > 1 the one-process device-group leg and the CPU baselines.  The --no-* options take
+single legs out of a --full run.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N bench.py --gpus N ...
 """
 from __future__ import annotations
@@ -34,6 +42,8 @@ sys.path.insert(0, REPO)
 
 FP64_MFMA_PEAK_TF = 78.6    # MI355X dense FP64 matrix peak (spec)
 HBM_PEAK_GBS = 8000.0       # MI355X HBM3E peak (spec; MI355X_MICROARCH.md)
+# what only a --full run does (each also has its --no-* option)
+FULL_ONLY_LEGS = ("cpu", "cov", "fit", "fit4", "large", "mlp", "small", "tcc", "logistic", "check", "group")
 
 
 def log(*a):
@@ -75,7 +85,16 @@ def parse():
     p.add_argument("--no-group", action="store_true", help="skip the single-process device-group leg (ABI 11: "
                    "one process drives all N GPUs, DagmaLinear(devices=[...]))")
     p.add_argument("--group-leg", action="store_true", help=argparse.SUPPRESS)  # the leg's child process
-    return p.parse_args()
+    p.add_argument("--full", action="store_true", help="beside the headline: the value checks against the CPU "
+                   "oracle, the CPU baselines, the per-kernel profile and roofline, and every other leg (configs 1, "
+                   "2, 3, 5, TCC, logistic, the full fits, the device-group leg); off by default")
+    p.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write what they computed (W after "
+                   "the last timed step, the loop's counters) as DIR/<name>.npy")
+    args = p.parse_args()
+    if not args.full:  # a plain run: the headline workload alone
+        for leg in FULL_ONLY_LEGS:
+            setattr(args, "no_" + leg, True)
+    return args
 
 
 def _free_port():
@@ -485,6 +504,13 @@ def bench_data(args, world, rank, local):
         m = t.cpu().numpy()
         replicas = bool(m[0] == -m[2] and m[1] == -m[3])
         ok = ok and replicas
+    out = dict(ms_per_step=elapsed / K * 1e3, value=K / elapsed, verified_iters=int(r.iters), verified=ok,
+               n_local=n_k, prof=None, D=s.D, sem_gen_s=t_gen, replicas_identical=replicas, comm=comm,
+               W=Wf, cov=None, steps_total=Wm + K,
+               loop_state=np.array([r.iters, r.status, r.halvings, r.lr_final], dtype=np.float64))
+    if not getattr(args, "full", True):  # a plain run ends with its timed steps
+        s.close()
+        return out
     # value check: cov = X^T X / n of the same (centered, sharded) X from the device Gram,
     # all-reduced over ranks; rank 0 runs the oracle's reference algorithm on it (linear.py:244)
     s.data_gram()
@@ -504,9 +530,7 @@ def bench_data(args, world, rank, local):
     if rank != 0:
         prof = {}
     beat("data leg profiled")
-    out = dict(ms_per_step=elapsed / K * 1e3, value=K / elapsed, verified_iters=int(r.iters), verified=ok,
-               n_local=n_k, prof=prof, D=s.D, sem_gen_s=t_gen, replicas_identical=replicas, comm=comm,
-               W=Wf, cov=cov, steps_total=Wm + K)
+    out.update(prof=prof, cov=cov)
     s.close()
     return out
 
@@ -618,11 +642,14 @@ def bench_cov(args, device):
     r = s.poll()
     W = np.zeros((d, d))
     s.end(W)
-    s.begin(W, 1.0, 1000, 1.0, 3e-4, tol=-1.0, lambda1=0.03)
-    prof = s.profile_parts(20)
+    prof = {}
+    if getattr(args, "full", True):
+        s.begin(W, 1.0, 1000, 1.0, 3e-4, tol=-1.0, lambda1=0.03)
+        prof = s.profile_parts(20)
     s.close()
     return dict(value=K / (t1 - t0), ms_per_step=(t1 - t0) / K * 1e3, steps=K, verified=(r.status == 0 and
-                r.iters == K + 20), prof=prof, cov=cov, W=W, steps_total=K + 20)
+                r.iters == K + 20), prof=prof, cov=cov, W=W, steps_total=K + 20,
+                loop_state=np.array([r.iters, r.status, r.halvings, r.lr_final], dtype=np.float64))
 
 
 _MLP_CPU_CHILD = r"""
@@ -1545,6 +1572,15 @@ def _profile_roofline(d, n, world, n_k):
     return None
 
 
+def dump_outputs(path, arrays):
+    """--dump-outputs: what a caller of the timed path receives after its last timed step, one
+    float64 .npy per name (W: d x d, 8 MB at d=1000; loop_state: iterations, status, halvings and
+    the final learning rate)."""
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
+
+
 def main():
     args = parse()
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -1563,6 +1599,10 @@ def main():
     cov_res = None
     if rank == 0 and (args.workload == "cov" or (world == 1 and not args.no_cov)):
         cov_res = bench_cov(args, local)
+    if args.dump_outputs and rank == 0:
+        timed = res if args.workload == "data" else cov_res
+        if timed is not None:
+            dump_outputs(args.dump_outputs, {"W": timed["W"], "loop_state": timed["loop_state"]})
     fit_res = None
     if rank == 0 and world == 1 and not args.no_fit:
         fit_res = bench_fit(args, local)
@@ -1593,7 +1633,7 @@ def main():
     if not args.no_check:
         value_checks(res, cov_res, large_res, small_res, mlp_res, logi, rank, world, fit4, tcc_res)
         beat("value checks done")
-    if rank == 0 and res is not None and os.environ.get("MIDAGMA_BENCH_COV_OUT"):
+    if rank == 0 and res is not None and res["cov"] is not None and os.environ.get("MIDAGMA_BENCH_COV_OUT"):
         np.save(os.environ["MIDAGMA_BENCH_COV_OUT"], res["cov"])  # the supervisor's CPU baseline
     for leg in (small_res, mlp_res, tcc_res, *(logi or [])):
         if leg is not None:
@@ -1624,7 +1664,7 @@ def main():
         d = args.d
         sem_gen = None
         if args.workload == "data":
-            prof = res["prof"]
+            prof = res["prof"] or {}                # (None: a plain run profiles no kernels, no roofline)
             n_k = res["n_local"]
             gemm_flops = 2.0 * n_k * d * d          # each of X(I-W) and X^T Y
             t_xty, t_xw = prof.get("gemm_xty", 0) * 1e-3, prof.get("gemm_xw", 0) * 1e-3
@@ -1651,6 +1691,8 @@ def main():
                     "algorithmic_bytes_per_launch": 8.0 * 2 * n_k * d + 8.0 * d * d,
                     "algorithmic_per_launch": f"2*n_k*d^2 = {gemm_flops:.3e} flop",
                     "kernel_ms": {k: round(v, 4) for k, v in prof.items()}}
+            if res["prof"] is None:
+                roof = None
             verified = res["verified"]
             t_gen = res["sem_gen_s"]
             sem_gen = {"what": "X shard generation on the GPU (csrc/sem.hip: Philox noise, structural equations "
@@ -1668,7 +1710,7 @@ def main():
                 "steps": args.steps if args.workload == "data" else args.cov_steps,
                 "warmup": args.warmup, "ms_per_step": ms, "higher_is_better": True,
                 "scaling": "strong", "vs_baseline": None, "dtype": "f64", "data": "synthetic", "config": cfg,
-                "verified": verified}
+                "verified": verified, "full": bool(args.full)}
         if args.workload == "data" and res.get("value_check") is not None:
             line["value_check"] = res["value_check"]
         elif args.workload == "cov" and cov_res.get("value_check") is not None:

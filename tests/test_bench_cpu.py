@@ -72,6 +72,31 @@ def test_gpus_n_relaunches_as_torchrun_child(bench, monkeypatch):
     assert seen["new_session"]  # a timeout kills torchrun's whole session
 
 
+def test_plain_run_is_the_headline_alone(bench, monkeypatch):
+    """Without --full every leg beside the headline is off (value checks, CPU baselines, the other
+    configs, the group leg); --full turns them on and the --no-* options still take one out."""
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "2"])
+    a = bench.parse()
+    assert not a.full and a.steps == 7 and a.warmup == 2 and a.dump_outputs is None
+    assert all(getattr(a, "no_" + leg) for leg in bench.FULL_ONLY_LEGS)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--no-mlp", "--dump-outputs", "out"])
+    a = bench.parse()
+    assert a.full and a.no_mlp and a.dump_outputs == "out"
+    assert not any(getattr(a, "no_" + leg) for leg in bench.FULL_ONLY_LEGS if leg != "mlp")
+
+
+def test_dump_outputs_writes_float64_npy(bench, tmp_path):
+    """--dump-outputs: one float64 DIR/<name>.npy per array, the directory created."""
+    import numpy as np
+    W = np.arange(12, dtype=np.float32).reshape(3, 4).T        # not contiguous, not float64
+    out = tmp_path / "a" / "b"
+    bench.dump_outputs(str(out), {"W": W, "loop_state": [25, 0, 0, 3e-4]})
+    assert sorted(os.listdir(out)) == ["W.npy", "loop_state.npy"]
+    got = np.load(out / "W.npy")
+    assert got.dtype == np.float64 and got.flags.c_contiguous and np.array_equal(got, W)
+    assert np.load(out / "loop_state.npy").tolist() == [25.0, 0.0, 0.0, 3e-4]
+
+
 def test_oracle_check_child_matches_in_process_oracle(bench):
     """The value check's child process runs the same oracle steps as an in-process LinearOracle
     (bit for bit at one BLAS thread), and check_l2 flags a W one part in 1e8 off."""
@@ -137,7 +162,7 @@ def test_supervised_ranks_fall_back_to_host_path(tmp_path):
     env.pop("MIDAGMA_BENCH_COMM", None)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2",
            "--master-addr", "127.0.0.1", "--master-port", "29581", os.path.join(REPO, "bench.py"),
-           "--gpus", "2", "--dim", "20", "--rows", "500", "--no-group"]
+           "--gpus", "2", "--dim", "20", "--rows", "500", "--full", "--no-group"]
     t0 = __import__("time").time()
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, env=env, cwd=str(tmp_path))
     assert r.returncode == 0, r.stderr[-3000:]

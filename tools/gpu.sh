@@ -24,10 +24,11 @@ mkdir -p gpurun_out
 export TMPDIR=/tmp
 
 leg_args() {
-  local skip="--no-cpu --no-check --no-fit --no-fit4 --no-cov --no-large --no-mlp --no-logistic --no-small --no-tcc --no-group"
+  # (--full: the legs and the per-kernel profile live behind it; the --no-* options then leave one leg)
+  local skip="--full --no-cpu --no-check --no-fit --no-fit4 --no-cov --no-large --no-mlp --no-logistic --no-small --no-tcc --no-group"
   case "$1" in
     data)     echo "--steps 5 --warmup 1 ${skip}" ;;
-    cov)      echo "--workload cov --cov-steps 2000 --no-cpu --no-check --no-fit --no-fit4 --no-large" ;;
+    cov)      echo "--full --workload cov --cov-steps 2000 --no-cpu --no-check --no-fit --no-fit4 --no-large" ;;
     fit4)     echo "--steps 2 --warmup 1 ${skip/--no-fit4/}" ;;
     large)    echo "--no-data ${skip/--no-large/} --large-steps 200" ;;
     mlp)      echo "--no-data ${skip/--no-mlp/}" ;;
