@@ -16,7 +16,7 @@ from __future__ import annotations
 import numpy as np
 import torch
 
-__all__ = ["pst_value_grad"]
+__all__ = ["pst_value_grad", "tcc_value_grad", "tcc_perron", "tcc_from_perron"]
 
 
 def _f_of_w2(W2: torch.Tensor, seq: str, K_log, eps_inv: float) -> torch.Tensor:
@@ -78,22 +78,8 @@ def _positive(x: np.ndarray) -> np.ndarray:
     return -x if x.sum() < 0 else x
 
 
-def tcc_value_grad(W: np.ndarray, pairs, *, w: float = 1.0, eps: float = 1e-12, grad: bool = True):
-    """(value, d value / d W) of the TCC penalty as the minimize loop takes it: notreks
-    `trek_value_grad` calls `trek_cycle_coupling_value_gradW` with its defaults, i.e. the
-    spectral penalty, version 'approx_trek_graph', Perron pairs by `numpy.linalg.eig`
-    (notreks.py:156-238, 291-395, 667-706):
-
-        W2 = W o W,  A = [[W2, w S], [I, W2^T]],  B = [[W2, 0], [I, W2^T]]
-        rho_A, u, v = Perron root and left / right vectors of A (unit, positive sum)
-        G_A = u v^T / (u^T v + eps)
-        value = (rho_A - u^T B u / (u^T u + eps)) / m
-        grad  = 2 W o ((G_A[:d,:d] + G_A[d:,d:]^T) - (u1 u1^T + u2 u2^T) / (u^T u + eps)) / m
-    """
-    P = np.asarray(pairs, dtype=np.int64)
-    W = np.asarray(W, dtype=np.float64)
-    if P.size == 0:
-        return 0.0, np.zeros_like(W)
+def _tcc_matrices(W: np.ndarray, P: np.ndarray, w: float):
+    """A = [[W2, w S], [I, W2^T]] and B = [[W2, 0], [I, W2^T]] of the TCC penalty."""
     d = W.shape[0]
     W2 = W * W
     S = np.zeros((d, d))
@@ -101,12 +87,33 @@ def tcc_value_grad(W: np.ndarray, pairs, *, w: float = 1.0, eps: float = 1e-12, 
     eye = np.eye(d)
     A = np.block([[W2, float(w) * S], [eye, W2.T]])
     B = np.block([[W2, np.zeros((d, d))], [eye, W2.T]])
+    return A, B
+
+
+def tcc_perron(W: np.ndarray, pairs, w: float = 1.0):
+    """(rho_A, u, v): Perron root and left / right vectors of A by `numpy.linalg.eig`, as the
+    reference takes them (unit 2-norm, positive sum).  The expensive half of `tcc_value_grad`:
+    2 (2d) + 1 doubles from which `tcc_from_perron` restates value and gradient."""
+    P = np.asarray(pairs, dtype=np.int64)
+    W = np.asarray(W, dtype=np.float64)
+    A, _ = _tcc_matrices(W, P, w)
     vals, vecs = np.linalg.eig(A)
     idx = np.argmax(vals.real)
     rho = float(vals[idx].real)
     v = _positive(vecs[:, idx])
     valsT, vecsT = np.linalg.eig(A.T)
     u = _positive(vecsT[:, np.argmax(valsT.real)])
+    return rho, u, v
+
+
+def tcc_from_perron(W: np.ndarray, pairs, rho: float, u: np.ndarray, v: np.ndarray, eps: float = 1e-12,
+                    *, grad: bool = True):
+    """(value, d value / d W) from a Perron triple of A: the closed form of `tcc_value_grad`
+    (B does not depend on w, and A enters through (rho, u, v) alone)."""
+    P = np.asarray(pairs, dtype=np.int64)
+    W = np.asarray(W, dtype=np.float64)
+    d = W.shape[0]
+    _, B = _tcc_matrices(W, P, 1.0)
     G_A = np.outer(u, v) / ((u * v).sum() + eps)
     GW2_A = G_A[:d, :d] + G_A[d:, d:].T
     rho_lb = (u * (B @ u)).sum() / ((u * u).sum() + eps)
@@ -118,3 +125,25 @@ def tcc_value_grad(W: np.ndarray, pairs, *, w: float = 1.0, eps: float = 1e-12, 
     if not grad:
         return float(value), None
     return float(value), (2.0 * W * GW2_A - 2.0 * W * GW2_lb) / m
+
+
+def tcc_value_grad(W: np.ndarray, pairs, *, w: float = 1.0, eps: float = 1e-12, grad: bool = True):
+    """(value, d value / d W) of the TCC penalty as the minimize loop takes it: notreks
+    `trek_value_grad` calls `trek_cycle_coupling_value_gradW` with its defaults, i.e. the
+    spectral penalty, version 'approx_trek_graph', Perron pairs by `numpy.linalg.eig`
+    (notreks.py:156-238, 291-395, 667-706):
+
+        W2 = W o W,  A = [[W2, w S], [I, W2^T]],  B = [[W2, 0], [I, W2^T]]
+        rho_A, u, v = Perron root and left / right vectors of A (unit, positive sum)
+        G_A = u v^T / (u^T v + eps)
+        value = (rho_A - u^T B u / (u^T u + eps)) / m
+        grad  = 2 W o ((G_A[:d,:d] + G_A[d:,d:]^T) - (u1 u1^T + u2 u2^T) / (u^T u + eps)) / m
+
+    `tcc_perron` followed by `tcc_from_perron`.
+    """
+    P = np.asarray(pairs, dtype=np.int64)
+    W = np.asarray(W, dtype=np.float64)
+    if P.size == 0:
+        return 0.0, np.zeros_like(W)
+    rho, u, v = tcc_perron(W, P, w)
+    return tcc_from_perron(W, P, rho, u, v, eps, grad=grad)

@@ -212,7 +212,11 @@ def test_tcc_fixed_stage_settles_warm_slots():
 def test_tcc_fast_blocks_match_the_pivoted_inverse_d1000():
     """d = 1000 (D2 = 2048, eight 256-blocks): the fixed-stage inverse of fast slots with every outer
     block but the last on the warm-started product-form series (tcc.hip tcc_inverse_fix) against
-    the all-pivoted inverse: W after 80 steps from W = 0 (hand-backs included) within 1e-9."""
+    the all-pivoted inverse: W after 80 steps from W = 0 (hand-backs included) within 1e-9.
+
+    From W = 0 the fast-block leg hands back on 79 of its 80 steps (measured on an MI355X), so
+    this run is in effect all-pivoted and carries no cap on the count; the fast blocks are compared
+    with the oracle from W0 != 0 in test_minimize_with_tcc_blocked_matches_oracle."""
     d, K = 1000, 80
     o, pairs = _tcc_case(d)
     out = {}
@@ -226,3 +230,99 @@ def test_tcc_fast_blocks_match_the_pivoted_inverse_d1000():
         out[fb] = (W.copy(), s.debug_handbacks())
         s.close()
     assert np.abs(out[True][0] - out[False][0]).max() <= 1e-9, np.abs(out[True][0] - out[False][0]).max()
+
+
+# --- the blocked-inverse regime, d >= 993 (D2 >= 2048), against tests/golden/tcc_blocked*.npz ------
+#
+#   d     D2    block  outer blocks
+#   993   2048  256    8     smallest d on the path, 62 padding rows
+#   1000  2048  256    8     the benchmarked shape
+#   1024  2048  256    8     no padding
+#   1040  2112  -      -     binv_block(2112) = 0: the flat Gauss-Jordan (the seam inside the regime)
+#   1088  2176  128    17    the 128-wide series, odd block count (the ping-pong starts in Aalt)
+#   1152  2304  256    9     odd block count
+_BLOCKED_POINT_D = (993, 1000, 1024, 1040, 1088, 1152)
+_BLOCKED_TRAJ_D = (1000, 1088, 1152)
+
+
+def _blocked_point_cases():
+    import os
+    f = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "tcc_blocked.npz"))
+    return [(d, case) for d in _BLOCKED_POINT_D for case in ("dense", "dag") if f"rho_{case}_d{d}" in f.files]
+
+
+@pytest.mark.parametrize("d,case", _blocked_point_cases())
+def test_tcc_value_grad_blocked_matches_oracle(golden, d, case):
+    """trek_value at the shapes of the two-level blocked inverse against the oracle's closed form on
+    the fixture's Perron triple (numpy eig, certified by tests/test_trek_oracle.py to 1e-11): the
+    first call is cold (Noda on the pivoted blocked inverse), the second starts from the vectors
+    the first left (the fixed-shift stage).  1e-10 relative, value and gradient, both times."""
+    from oracle.trek_oracle import tcc_from_perron
+    from tests.golden.make_tcc_blocked import point_inputs
+    f = golden("tcc_blocked.npz")
+    k = f"{case}_d{d}"
+    W, pairs = point_inputs(d, case)
+    assert W.sum() == float(f[f"guard_Wsum_{k}"]) and len(pairs) == int(f[f"guard_npairs_{k}"])
+    assert np.array_equal(W[1, :8], f[f"guard_Wrow1_{k}"])
+    vr, gr = tcc_from_perron(W, pairs, float(f[f"rho_{k}"]), f[f"u_{k}"], f[f"v_{k}"], 1e-12)
+    s = _solver(d, np.eye(d))
+    s.set_trek_tcc(pairs, mode="opt", weight=1.0)
+    errs = []
+    for call in ("cold", "warm"):
+        v, g = s.trek_value(W)
+        errs.append((call, abs(v - vr) / abs(vr), np.abs(g - gr).max() / np.abs(gr).max()))
+        print(f"d={d} {case} {call}: value {errs[-1][1]:.2e} grad {errs[-1][2]:.2e} (relative)")
+    s.close()
+    for call, ev, eg in errs:
+        assert ev <= 1e-10, (call, ev)
+        assert eg <= 1e-10, (call, eg)
+
+
+_blocked_traj_cache = {}
+
+
+def _blocked_traj_inputs(d, f):
+    """(cov, pairs, W0) of a trajectory case, built once for both fast-block settings; the guards
+    tie them to the run the fixture recorded."""
+    if d not in _blocked_traj_cache:
+        from tests.golden.make_tcc_blocked import traj_w0
+        o, pairs = _tcc_case(d)
+        W0 = traj_w0(d, str(f[f"w0_traj_d{d}"]), o)
+        assert o.cov.sum() == float(f[f"guard_covsum_traj_d{d}"])
+        assert np.array_equal(o.cov[0, :8], f[f"guard_covrow0_traj_d{d}"])
+        assert W0.sum() == float(f[f"guard_W0sum_traj_d{d}"])
+        _blocked_traj_cache[d] = (o.cov, pairs, W0)
+    return _blocked_traj_cache[d]
+
+
+@pytest.mark.parametrize("fastblk", [False, True])
+@pytest.mark.parametrize("d", _BLOCKED_TRAJ_D)
+def test_minimize_with_tcc_blocked_matches_oracle(golden, d, fastblk):
+    """24 steps with TCC from a dense W0 against the oracle's own 24 steps (tcc_blocked_traj.npz: W at
+    32768 seeded positions, every row and column sum), with the fast blocks off and on.
+
+    The hand-back cap (at most K // 4 of the fast-block run's slots re-run on the pivoted path) is
+    not asserted at any d: measured on an MI355X, fast blocks on / off, 8 / 1 of 24 at d = 1000 and
+    1088 and 12 / 2 at d = 1152 from the dense W0, and 8 / 1 at all three from the W after 400 plain
+    steps.  So a third to a half of the fast-block run's slots pass on the pivoted path alone; the
+    rest ran the product-form series, and the count is printed."""
+    from tests.golden.make_tcc_blocked import K_TRAJ, traj_positions
+    f = golden("tcc_blocked_traj.npz")
+    cov, pairs, W0 = _blocked_traj_inputs(d, f)
+    K = int(f[f"iters_traj_d{d}"])
+    assert K == K_TRAJ
+    s = _solver(d, cov)
+    s.debug_tcc_fastblk(fastblk)
+    s.set_trek_tcc(pairs, mode="opt", weight=0.2)
+    W = W0.copy()
+    res = s.minimize(W, 1.0, K, 1.0, 3e-4, tol=-1.0, lambda1=0.03, checkpoint=1000)
+    backs = s.debug_handbacks()
+    s.close()
+    eW = np.abs(W.ravel()[traj_positions(d)] - f[f"W_traj_d{d}"]).max()
+    eR = np.abs(W.sum(axis=1) - f[f"rowsum_traj_d{d}"]).max()
+    eC = np.abs(W.sum(axis=0) - f[f"colsum_traj_d{d}"]).max()
+    print(f"d={d} fastblk={fastblk}: hand-backs {backs} of {K}, max|dW| {eW:.2e}, row sums {eR:.2e}, "
+          f"column sums {eC:.2e}")
+    assert res.iters == K
+    assert eW <= 1e-9
+    assert eR <= d * 1e-9 and eC <= d * 1e-9
