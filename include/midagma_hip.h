@@ -362,6 +362,45 @@ int midagma_mlp_objective_bwd(const double* g, const double* ssq, int64_t np, do
 int midagma_mlp_tail_bwd(const double* Z, const double* b1, const double* w2, const double* R, const double* g,
                          int64_t n, int64_t d, int64_t m1, double* dZ, double* dw2, double* db2, double* db1,
                          double* scratch, void* stream);
+
+/* Pairwise permutation independence tests (notreks/mi_tests.py: hsic_stat / dcor_stat under
+ * permutation_pvalue, as test_pairwise_independence runs them over a pair list), the step that
+ * builds the trek regularizers' pair set I.  Purely additive: MIDAGMA_ABI_VERSION stays 11.
+ * A handle owns two streams and the device copy of X; one host thread drives it at a time.  Every
+ * entry checks its arguments before it touches a device (MIDAGMA_E_ARG); the message comes from
+ * midagma_indep_last_error(handle) (or (NULL) for errors raised without a handle).
+ * set_data: host X (n x d row-major), 2 <= n <= 16384, d <= 65535, copied; MIDAGMA_E_ARG on inf/nan.
+ * set_bandwidths: the RBF kernel's sigma^2 per variable (d values, finite and > 0), for hsic.
+ * run: for each of the m pairs (i, j) (int64 m x 2; i == j and both orders allowed) the observed
+ *   statistic stat[q] of (X[:, i], X[:, j]) and ge[q] = #{p < P : stat(X[:, i], X[:, j][perm_qp]) >=
+ *   stat[q]}; null_out (nullable, m x P): every permuted statistic.  kind: 0 hsic, 1 dcor (dcor
+ *   counts by dcov^2 and returns sqrt(max(dcov^2, 0)) / sqrt(sqrt(dvar_x^2 dvar_y^2)), 0 when a
+ *   variance is <= 0).  A pair with a zero-range column gives stat 0, every permuted value 0 and
+ *   ge = P, as the reference's all-zero centred matrix does.  perms: m x P x n int32 host array,
+ *   each entry in [0, n) (checked), or NULL for device permutations: the stable argsort over a of
+ *   the 64-bit key (((o.x << 32) | o.y) & ~0x3fff) | a, o = Philox4x32-10(counter (q, p, a, 0), key
+ *   (seed low word, seed high word)), q the pair's index in this call; perms_out (nullable, m x P x n): those
+ *   permutations.  Pairs are processed in batches of midagma_indep_batch_pairs(h, P, budget_bytes)
+ *   (budget_bytes <= 0: 128 MiB over the two in-flight batches; at least 1 pair), the upload of a
+ *   batch overlapping the kernels of the one before; results do not depend on the batch size.
+ *   0 <= P <= 65535.
+ * profile (diagnostics): the last run's stage times in ms, summed over its batches (stages of
+ *   different batches overlap, so the sum can exceed the call's wall time): [0] host checking and
+ *   staging of the explicit permutations, [1] uploads, [2] the permutation kernel, [3] the
+ *   statistic kernels.  ms_out holds 4 doubles. */
+#define MIDAGMA_INDEP_HSIC 0
+#define MIDAGMA_INDEP_DCOR 1
+typedef struct midagma_indep midagma_indep;
+int midagma_indep_create(midagma_indep** out, int device);
+void midagma_indep_destroy(midagma_indep* h);
+const char* midagma_indep_last_error(const midagma_indep* h);
+int midagma_indep_set_data(midagma_indep* h, const double* X, int64_t n, int64_t d);
+int midagma_indep_set_bandwidths(midagma_indep* h, const double* sigma2, int64_t d);
+int64_t midagma_indep_batch_pairs(const midagma_indep* h, int64_t P, int64_t budget_bytes);
+int midagma_indep_profile(const midagma_indep* h, double* ms_out);
+int midagma_indep_run(midagma_indep* h, int kind, const int64_t* pairs, int64_t m, int64_t P, const int32_t* perms,
+                      uint64_t seed, int64_t budget_bytes, double* stat, int64_t* ge, double* null_out,
+                      int32_t* perms_out);
 #ifdef __cplusplus
 }
 #endif

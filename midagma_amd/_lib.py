@@ -136,6 +136,15 @@ EXPORTED = {
     "midagma_group_set_data": (_int, [_vp, _dp, _i64]),
     "midagma_group_allreduce_zbuf": (_int, [_vp]),
     "midagma_group_minimize": (_int, [_vp, _dp, _d, _i64, _d, _d, _d, _d, _d, _d, _i64, C.POINTER(MidagmaResult)]),
+    # additive to ABI 11: pairwise permutation independence tests (midagma_amd.solver.HipIndep)
+    "midagma_indep_create": (_int, [C.POINTER(_vp), _int]),
+    "midagma_indep_destroy": (None, [_vp]),
+    "midagma_indep_last_error": (C.c_char_p, [_vp]),
+    "midagma_indep_set_data": (_int, [_vp, _dp, _i64, _i64]),
+    "midagma_indep_set_bandwidths": (_int, [_vp, _dp, _i64]),
+    "midagma_indep_batch_pairs": (_i64, [_vp, _i64, _i64]),
+    "midagma_indep_profile": (_int, [_vp, _dp]),
+    "midagma_indep_run": (_int, [_vp, _int, _vp, _i64, _i64, _vp, C.c_uint64, _i64, _dp, _vp, _dp, _vp]),
 }
 
 GROUP_EMULATE = 1

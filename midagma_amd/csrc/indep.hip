@@ -1,0 +1,631 @@
+// Pairwise permutation independence tests on the GPU (include/midagma_hip.h, midagma_indep_*):
+// the reference's notreks/mi_tests.py, hsic_stat / dcor_stat under permutation_pvalue, for every
+// pair of a pair list at once.  Everything is FP64.
+//
+// For a pair (i, j), x = X[:, i], y = X[:, j], and a permutation pi of the rows of y:
+//   HSIC(x, y[pi])  = (1/n^2) sum_{a,b} Kc[a,b] exp(-(y[pi_a] - y[pi_b])^2 / (2 sigma_y^2))
+//   dcov^2(x, y[pi]) = (1/n^2) sum_{a,b} Ax[a,b] |y[pi_a] - y[pi_b]|
+// with Kc the double-centred RBF Gram of x and Ax its double-centred distance matrix.  The
+// reference centres the y matrix too (mi_tests.py:21-27, 63-65, 92-95); those terms multiply the
+// row sums of Kc / Ax, which are zero, so they drop out and nothing is re-centred per permutation.
+// No n x n matrix is stored:
+//   1. a per-variable pre-pass leaves the row means and the grand mean of the Gram / distance
+//      matrix (and dvar^2 for dCor);
+//   2. the main kernel's grid is (tile of the upper triangle a-tile <= b-tile, pair): a workgroup
+//      builds its 64 x 64 tile of Kc / Ax once in registers (16 per thread; off-diagonal tiles
+//      carry the weight 2 of their mirror image), then for the identity and every permutation
+//      gathers the 64 + 64 values of y through the permutation into LDS, G permutations per
+//      round, and leaves one partial sum per (pair, permutation, tile);
+//   3. the final kernel sums the tiles of every (pair, permutation) in a fixed order and counts
+//      ge = #{p : stat_p >= stat_obs}.
+// No floating-point atomics: every sum has one fixed order that depends on n alone, so results
+// are bit-identical from run to run and do not depend on how the pairs are split into batches.
+//
+// Device permutations (perms == NULL): pi for (pair q of the call, permutation p) is the stable
+// argsort over a of the 64-bit key(a) = (((o.x << 32) | o.y) & ~0x3fff) | a, o = Philox4x32-10(
+// counter = (q, p, a, 0), key = (seed low word, seed high word)): 50 random bits, then a itself
+// (a < 2^14), so the keys are distinct and one unsigned compare orders them.  rank(a) is counted
+// against every b, and pi[rank(a)] = a.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <chrono>
+#include <cmath>
+#include <cstring>
+#include <exception>
+#include <string>
+#include <vector>
+
+#include "../../include/midagma_hip.h"
+#include "launch.h"
+#include "philox.h"
+
+namespace midagma {
+namespace {
+
+constexpr int IT = 64;  // tile edge
+constexpr int IG = 8;   // permutations per LDS round
+constexpr int KIND_HSIC = 0, KIND_DCOR = 1;
+
+// the sum of v over the workgroup's 256 threads in a fixed order (butterfly within a wave, then
+// wave 0 + 1 + 2 + 3); the result is valid in every thread; w: 4 doubles of LDS
+__device__ __forceinline__ double block_sum(double v, double* w) {
+#pragma unroll
+  for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off);
+  __syncthreads();  // (w may still be read from a previous call)
+  if ((threadIdx.x & 63) == 0) w[threadIdx.x >> 6] = v;
+  __syncthreads();
+  return ((w[0] + w[1]) + w[2]) + w[3];
+}
+
+template <int KIND>
+__device__ __forceinline__ double kern(double dlt, double c) {
+  if constexpr (KIND == KIND_HSIC)
+    return exp(-(dlt * dlt) * c);
+  else
+    return fabs(dlt);
+}
+
+// PHASE 0: out[v][a] = mean_b k(x_a, x_b);  PHASE 1 (dCor): out[v][a] = sum_b Ax[a,b]^2.
+// grid (n, d), 256 threads.
+template <int KIND, int PHASE>
+__global__ __launch_bounds__(256) void indep_row_kernel(const double* __restrict__ XT, const double* __restrict__ c,
+                                                        const double* __restrict__ rm, const double* __restrict__ gm,
+                                                        int n, double* __restrict__ out) {
+  __shared__ double w[4];
+  const int v = blockIdx.y, a = blockIdx.x;
+  const double* x = XT + static_cast<int64_t>(v) * n;
+  const double xa = x[a];
+  const double cv = KIND == KIND_HSIC ? c[v] : 0.0;
+  double s = 0.0;
+  for (int b = threadIdx.x; b < n; b += 256) {
+    const double k = kern<KIND>(xa - x[b], cv);
+    if constexpr (PHASE == 0) {
+      s += k;
+    } else {
+      const double* r = rm + static_cast<int64_t>(v) * n;
+      const double ax = ((k - r[a]) - r[b]) + gm[v];
+      s += ax * ax;
+    }
+  }
+  s = block_sum(s, w);
+  if (threadIdx.x == 0) out[static_cast<int64_t>(v) * n + a] = PHASE == 0 ? s / n : s;
+}
+
+// out[v] = (sum_a in[v][a]) / div: the grand mean from the row means, dvar^2 from the row sums
+__global__ __launch_bounds__(256) void indep_col_kernel(const double* __restrict__ in, int n, double div,
+                                                        double* __restrict__ out) {
+  __shared__ double w[4];
+  const int v = blockIdx.x;
+  double s = 0.0;
+  for (int a = threadIdx.x; a < n; a += 256) s += in[static_cast<int64_t>(v) * n + a];
+  s = block_sum(s, w);
+  if (threadIdx.x == 0) out[v] = s / div;
+}
+
+// perms[q][p][rank(a)] = a (see the head of the file); grid (ceil(n / (256 IPA)), P, pairs): a
+// thread ranks IPA values of a against every b, the keys of 256 b at a time in LDS (each read is
+// a broadcast)
+constexpr int IPA = 4;
+__global__ __launch_bounds__(256) void indep_perm_kernel(uint32_t k0, uint32_t k1, int64_t q0, int n, int P,
+                                                         int32_t* __restrict__ perms) {
+  __shared__ uint64_t keys[256];
+  const int64_t ql = blockIdx.z;
+  const uint32_t q = static_cast<uint32_t>(q0 + ql), p = blockIdx.y;
+  auto key = [&](int i) -> uint64_t {
+    const U4 o = philox4x32_10(U4{q, p, static_cast<uint32_t>(i), 0u}, k0, k1);
+    return (((static_cast<uint64_t>(o.x) << 32) | o.y) & ~uint64_t(0x3fff)) | static_cast<uint64_t>(i);
+  };
+  int a[IPA], rank[IPA];
+  uint64_t ka[IPA];
+#pragma unroll
+  for (int k = 0; k < IPA; ++k) {
+    a[k] = (blockIdx.x * IPA + k) * 256 + threadIdx.x;
+    ka[k] = key(a[k]);
+    rank[k] = 0;
+  }
+  for (int c0 = 0; c0 < n; c0 += 256) {
+    __syncthreads();
+    keys[threadIdx.x] = key(c0 + threadIdx.x);
+    __syncthreads();
+    const int lim = min(256, n - c0);
+    for (int b = 0; b < lim; ++b) {
+      const uint64_t kb = keys[b];
+#pragma unroll
+      for (int k = 0; k < IPA; ++k) rank[k] += kb < ka[k] ? 1 : 0;
+    }
+  }
+  // rank < n for a < n: it counts the b < n whose key is smaller, and a itself is not among them
+#pragma unroll
+  for (int k = 0; k < IPA; ++k)
+    if (a[k] < n) perms[(ql * P + p) * n + rank[k]] = a[k];
+}
+
+// partial[q][p][t] for p = 0 (identity), 1 .. P; grid (ntiles, pairs), 256 threads.
+// Thread (tx, ty) = (tid & 15, tid >> 4) holds rows r0 + ty + 16 u, columns c0 + tx + 16 v.
+template <int KIND>
+__global__ __launch_bounds__(256) void indep_main_kernel(const double* __restrict__ XT, const double* __restrict__ rm,
+                                                         const double* __restrict__ gm, const double* __restrict__ c,
+                                                         const int64_t* __restrict__ pairs,
+                                                         const int32_t* __restrict__ perms, int n, int nt, int P,
+                                                         double* __restrict__ partial) {
+  __shared__ double yr[IG][IT], yc[IG][IT];
+  __shared__ double wsum[IG][4];
+  const int tid = threadIdx.x, tx = tid & 15, ty = tid >> 4;
+  const int64_t q = blockIdx.y;
+  const int t = blockIdx.x, ntiles = gridDim.x;
+  int ti = 0, rem = t;
+  while (rem >= nt - ti) {
+    rem -= nt - ti;
+    ++ti;
+  }
+  const int tj = ti + rem;
+  const int r0 = ti * IT, c0 = tj * IT;
+  const int64_t vi = pairs[2 * q], vj = pairs[2 * q + 1];
+  const double* x = XT + vi * n;
+  const double* y = XT + vj * n;
+  const double* rx = rm + vi * n;
+  const double gx = gm[vi];
+  const double cx = KIND == KIND_HSIC ? c[vi] : 0.0, cy = KIND == KIND_HSIC ? c[vj] : 0.0;
+  const double wt = ti == tj ? 1.0 : 2.0;
+
+  double kc[4][4];
+#pragma unroll
+  for (int u = 0; u < 4; ++u) {
+    const int a = r0 + ty + 16 * u;
+#pragma unroll
+    for (int v = 0; v < 4; ++v) {
+      const int b = c0 + tx + 16 * v;
+      double val = 0.0;
+      if (a < n && b < n) val = wt * (((kern<KIND>(x[a] - x[b], cx) - rx[a]) - rx[b]) + gx);
+      kc[u][v] = val;
+    }
+  }
+
+  for (int p0 = 0; p0 <= P; p0 += IG) {
+    const int ng = min(IG, P + 1 - p0);
+    for (int e = tid; e < IG * 2 * IT; e += 256) {
+      const int g = e >> 7, k = e & 127, kk = k & 63;
+      const bool row = k < 64;
+      const int idx = (row ? r0 : c0) + kk;
+      double val = 0.0;
+      if (g < ng && idx < n) {
+        const int p = p0 + g;
+        const int src = p == 0 ? idx : perms[(q * P + (p - 1)) * n + idx];
+        val = y[src];
+      }
+      if (row)
+        yr[g][kk] = val;
+      else
+        yc[g][kk] = val;
+    }
+    __syncthreads();
+    for (int g = 0; g < ng; ++g) {
+      double ycv[4];
+#pragma unroll
+      for (int v = 0; v < 4; ++v) ycv[v] = yc[g][tx + 16 * v];
+      double s = 0.0;
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        const double yu = yr[g][ty + 16 * u];
+#pragma unroll
+        for (int v = 0; v < 4; ++v) s += kc[u][v] * kern<KIND>(yu - ycv[v], cy);
+      }
+#pragma unroll
+      for (int off = 32; off >= 1; off >>= 1) s += __shfl_xor(s, off);
+      if ((tid & 63) == 0) wsum[g][tid >> 6] = s;
+    }
+    __syncthreads();
+    if (tid < ng)
+      partial[(q * (P + 1) + p0 + tid) * ntiles + t] = ((wsum[tid][0] + wsum[tid][1]) + wsum[tid][2]) + wsum[tid][3];
+  }
+}
+
+// vals[q][p] = the statistic of permutation p (0: observed) and ge[q]; grid (pairs), 256 threads:
+// wave w sums the tiles of p = w, w + 4, ... (lane-strided, then the butterfly).  dCor: the count
+// orders by dcov^2, the values are sqrt(max(dcov^2, 0)) / sqrt(sqrt(dvar_x^2 dvar_y^2)).
+template <int KIND>
+__global__ __launch_bounds__(256) void indep_final_kernel(const double* __restrict__ partial,
+                                                          const int64_t* __restrict__ pairs,
+                                                          const double* __restrict__ dvar, int n, int ntiles, int P,
+                                                          double* __restrict__ vals, int64_t* __restrict__ ge) {
+  __shared__ int cnt[4];
+  const int64_t q = blockIdx.x;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  double* out = vals + q * (P + 1);
+  const double nn = static_cast<double>(n) * static_cast<double>(n);
+  for (int p = wave; p <= P; p += 4) {
+    const double* src = partial + (q * (P + 1) + p) * ntiles;
+    double s = 0.0;
+    for (int t = lane; t < ntiles; t += 64) s += src[t];
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) s += __shfl_xor(s, off);
+    if (lane == 0) out[p] = s / nn;
+  }
+  __syncthreads();
+  const double obs = out[0];
+  int k = 0;
+  for (int p = 1 + threadIdx.x; p <= P; p += 256) k += out[p] >= obs ? 1 : 0;
+#pragma unroll
+  for (int off = 32; off >= 1; off >>= 1) k += __shfl_xor(k, off);
+  if (lane == 0) cnt[wave] = k;
+  __syncthreads();
+  if (threadIdx.x == 0) ge[q] = cnt[0] + cnt[1] + cnt[2] + cnt[3];
+  if constexpr (KIND == KIND_DCOR) {
+    const double vx = dvar[pairs[2 * q]], vy = dvar[pairs[2 * q + 1]];
+    const bool degenerate = vx <= 0.0 || vy <= 0.0;
+    const double den = degenerate ? 1.0 : sqrt(sqrt(vx * vy));
+    for (int p = threadIdx.x; p <= P; p += 256) out[p] = degenerate ? 0.0 : sqrt(fmax(out[p], 0.0)) / den;
+  }
+}
+
+thread_local std::string g_err;  // errors raised without a handle
+
+}  // namespace
+}  // namespace midagma
+
+using namespace midagma;
+
+namespace {
+
+constexpr int64_t kMaxN = 16384, kMaxD = 65535, kMaxP = 65535, kMaxBatchPairs = 32768;
+constexpr int64_t kDefaultBudget = int64_t(128) << 20;
+
+template <class T>
+struct DevBuf {
+  T* p = nullptr;
+  size_t cap = 0;
+  void need(size_t count) {
+    if (count <= cap) return;
+    release();
+    HIP_TRY(hipMalloc(reinterpret_cast<void**>(&p), std::max<size_t>(count, 1) * sizeof(T)));
+    cap = count;
+  }
+  void release() {
+    if (p) (void)hipFree(p);
+    p = nullptr;
+    cap = 0;
+  }
+};
+
+template <class T>
+struct PinBuf {
+  T* p = nullptr;
+  size_t cap = 0;
+  void need(size_t count) {
+    if (count <= cap) return;
+    release();
+    HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&p), std::max<size_t>(count, 1) * sizeof(T), hipHostMallocDefault));
+    cap = count;
+  }
+  void release() {
+    if (p) (void)hipHostFree(p);
+    p = nullptr;
+    cap = 0;
+  }
+};
+
+struct Slot {
+  PinBuf<int32_t> hperm;
+  PinBuf<int64_t> hpairs, hge;
+  PinBuf<double> hvals;
+  DevBuf<int32_t> dperm;
+  DevBuf<int64_t> dpairs, dge;
+  DevBuf<double> partial, dvals;
+  // up0 .. up: the batch's upload (copy stream); k0 .. k1: its permutation kernel; k1 .. k2: its
+  // statistic kernels; done: its results are on the host (compute stream)
+  hipEvent_t up0 = nullptr, up = nullptr, k0 = nullptr, k1 = nullptr, k2 = nullptr, done = nullptr;
+  int64_t q0 = 0, mb = 0;
+  bool busy = false;
+  void release() {
+    hperm.release(), hpairs.release(), hge.release(), hvals.release();
+    dperm.release(), dpairs.release(), dge.release(), partial.release(), dvals.release();
+  }
+};
+
+}  // namespace
+
+struct midagma_indep {
+  int device = 0;
+  int64_t n = 0, d = 0;
+  std::string err;
+  hipStream_t comp = nullptr, copy = nullptr;
+  DevBuf<double> XT, rm[2], gm[2], dvar, c, rowtmp;
+  std::vector<uint8_t> constant;  // zero-range columns: the reference's all-zero centred matrix
+  bool have_bw = false, have_stats[2] = {false, false};
+  Slot slot[2];
+  double prof[4] = {0, 0, 0, 0};  // the last run's stage times (midagma_indep_profile), ms
+};
+
+namespace {
+
+int ifail(midagma_indep* h, int code, const std::string& msg) {
+  (h ? h->err : g_err) = msg;
+  return code;
+}
+
+template <class F>
+int iguarded(midagma_indep* h, F&& f) {
+  try {
+    f();
+    return MIDAGMA_OK;
+  } catch (const HipError& x) {
+    return ifail(h, MIDAGMA_E_HIP, x.what());
+  } catch (const std::invalid_argument& x) {
+    return ifail(h, MIDAGMA_E_ARG, x.what());
+  } catch (const std::exception& x) {
+    return ifail(h, MIDAGMA_E_STATE, x.what());
+  } catch (...) {
+    return ifail(h, MIDAGMA_E_STATE, "unknown error");
+  }
+}
+
+int64_t tiles_of(int64_t n) {
+  const int64_t nt = (n + IT - 1) / IT;
+  return nt * (nt + 1) / 2;
+}
+
+// device + pinned bytes one pair of a batch takes in one of the two slots
+int64_t pair_bytes(int64_t n, int64_t P) {
+  return P * n * 4 + (P + 1) * tiles_of(n) * 8 + (P + 1) * 8 + 24;
+}
+
+int64_t batch_pairs(int64_t n, int64_t P, int64_t budget) {
+  if (budget <= 0) budget = kDefaultBudget;
+  return std::min<int64_t>(kMaxBatchPairs, std::max<int64_t>(1, budget / (2 * pair_bytes(n, P))));
+}
+
+// the per-variable pre-pass of one kind, on the compute stream
+void prepare_stats(midagma_indep* h, int kind) {
+  if (h->have_stats[kind]) return;
+  const int n = static_cast<int>(h->n), d = static_cast<int>(h->d);
+  const size_t nd = static_cast<size_t>(n) * d;
+  h->rm[kind].need(nd);
+  h->gm[kind].need(d);
+  const dim3 grid(n, d);
+  if (kind == KIND_HSIC) {
+    hipLaunchKernelGGL((indep_row_kernel<KIND_HSIC, 0>), grid, dim3(256), 0, h->comp, h->XT.p, h->c.p, nullptr, nullptr,
+                       n, h->rm[kind].p);
+    hipLaunchKernelGGL(indep_col_kernel, dim3(d), dim3(256), 0, h->comp, h->rm[kind].p, n, static_cast<double>(n),
+                       h->gm[kind].p);
+  } else {
+    h->dvar.need(d);
+    h->rowtmp.need(nd);
+    hipLaunchKernelGGL((indep_row_kernel<KIND_DCOR, 0>), grid, dim3(256), 0, h->comp, h->XT.p, nullptr, nullptr,
+                       nullptr, n, h->rm[kind].p);
+    hipLaunchKernelGGL(indep_col_kernel, dim3(d), dim3(256), 0, h->comp, h->rm[kind].p, n, static_cast<double>(n),
+                       h->gm[kind].p);
+    hipLaunchKernelGGL((indep_row_kernel<KIND_DCOR, 1>), grid, dim3(256), 0, h->comp, h->XT.p, nullptr, h->rm[kind].p,
+                       h->gm[kind].p, n, h->rowtmp.p);
+    hipLaunchKernelGGL(indep_col_kernel, dim3(d), dim3(256), 0, h->comp, h->rowtmp.p, n,
+                       static_cast<double>(n) * static_cast<double>(n), h->dvar.p);
+  }
+  HIP_TRY(hipGetLastError());
+  h->have_stats[kind] = true;
+}
+
+}  // namespace
+
+extern "C" const char* midagma_indep_last_error(const midagma_indep* h) { return (h ? h->err : g_err).c_str(); }
+
+extern "C" int midagma_indep_create(midagma_indep** out, int device) {
+  if (!out || device < 0) return ifail(nullptr, MIDAGMA_E_ARG, "indep_create: bad arguments");
+  *out = nullptr;
+  midagma_indep* h = nullptr;
+  const int rc = iguarded(nullptr, [&] {
+    int count = 0;
+    HIP_TRY(hipGetDeviceCount(&count));
+    if (device >= count) throw std::invalid_argument("indep_create: no such device");
+    HIP_TRY(hipSetDevice(device));
+    h = new midagma_indep;
+    h->device = device;
+    HIP_TRY(hipStreamCreateWithFlags(&h->comp, hipStreamNonBlocking));
+    HIP_TRY(hipStreamCreateWithFlags(&h->copy, hipStreamNonBlocking));
+    for (Slot& s : h->slot) {
+      HIP_TRY(hipEventCreate(&s.up0));
+      HIP_TRY(hipEventCreate(&s.up));
+      HIP_TRY(hipEventCreate(&s.k0));
+      HIP_TRY(hipEventCreate(&s.k1));
+      HIP_TRY(hipEventCreate(&s.k2));
+      HIP_TRY(hipEventCreateWithFlags(&s.done, hipEventDisableTiming));
+    }
+  });
+  if (rc != MIDAGMA_OK) {
+    midagma_indep_destroy(h);
+    return rc;
+  }
+  *out = h;
+  return MIDAGMA_OK;
+}
+
+extern "C" void midagma_indep_destroy(midagma_indep* h) {
+  if (!h) return;
+  (void)hipSetDevice(h->device);
+  if (h->comp) (void)hipStreamSynchronize(h->comp);
+  if (h->copy) (void)hipStreamSynchronize(h->copy);
+  for (Slot& s : h->slot) {
+    s.release();
+    for (hipEvent_t e : {s.up0, s.up, s.k0, s.k1, s.k2, s.done})
+      if (e) (void)hipEventDestroy(e);
+  }
+  h->XT.release(), h->dvar.release(), h->c.release(), h->rowtmp.release();
+  for (int k = 0; k < 2; ++k) h->rm[k].release(), h->gm[k].release();
+  if (h->comp) (void)hipStreamDestroy(h->comp);
+  if (h->copy) (void)hipStreamDestroy(h->copy);
+  delete h;
+}
+
+extern "C" int midagma_indep_set_data(midagma_indep* h, const double* X, int64_t n, int64_t d) {
+  if (!h) return ifail(nullptr, MIDAGMA_E_ARG, "indep_set_data: null handle");
+  if (!X || n < 2 || n > kMaxN || d < 1 || d > kMaxD)
+    return ifail(h, MIDAGMA_E_ARG, "indep_set_data: need X, 2 <= n <= 16384 and 1 <= d <= 65535");
+  std::vector<double> xt(static_cast<size_t>(n) * d);
+  std::vector<uint8_t> constant(d, 1);
+  for (int64_t a = 0; a < n; ++a)
+    for (int64_t v = 0; v < d; ++v) {
+      const double val = X[a * d + v];
+      if (!std::isfinite(val)) return ifail(h, MIDAGMA_E_ARG, "indep_set_data: X holds inf or nan");
+      xt[v * n + a] = val;
+      if (val != X[v]) constant[v] = 0;
+    }
+  return iguarded(h, [&] {
+    HIP_TRY(hipSetDevice(h->device));
+    HIP_TRY(hipStreamSynchronize(h->comp));
+    h->XT.need(xt.size());
+    HIP_TRY(hipMemcpy(h->XT.p, xt.data(), xt.size() * sizeof(double), hipMemcpyHostToDevice));
+    h->n = n;
+    h->d = d;
+    h->constant.swap(constant);
+    h->have_bw = h->have_stats[0] = h->have_stats[1] = false;
+  });
+}
+
+extern "C" int midagma_indep_set_bandwidths(midagma_indep* h, const double* sigma2, int64_t d) {
+  if (!h) return ifail(nullptr, MIDAGMA_E_ARG, "indep_set_bandwidths: null handle");
+  if (h->n == 0) return ifail(h, MIDAGMA_E_ARG, "indep_set_bandwidths: set the data first");
+  if (!sigma2 || d != h->d) return ifail(h, MIDAGMA_E_ARG, "indep_set_bandwidths: need d squared bandwidths");
+  std::vector<double> c(d);
+  for (int64_t v = 0; v < d; ++v) {
+    if (!(sigma2[v] > 0.0) || !std::isfinite(sigma2[v]))
+      return ifail(h, MIDAGMA_E_ARG, "indep_set_bandwidths: squared bandwidths must be finite and > 0");
+    c[v] = 1.0 / (2.0 * sigma2[v]);
+  }
+  return iguarded(h, [&] {
+    HIP_TRY(hipSetDevice(h->device));
+    HIP_TRY(hipStreamSynchronize(h->comp));
+    h->c.need(d);
+    HIP_TRY(hipMemcpy(h->c.p, c.data(), d * sizeof(double), hipMemcpyHostToDevice));
+    h->have_bw = true;
+    h->have_stats[KIND_HSIC] = false;
+  });
+}
+
+extern "C" int64_t midagma_indep_batch_pairs(const midagma_indep* h, int64_t P, int64_t budget_bytes) {
+  if (!h || h->n == 0 || P < 0 || P > kMaxP) return 0;
+  return batch_pairs(h->n, P, budget_bytes);
+}
+
+extern "C" int midagma_indep_profile(const midagma_indep* h, double* ms_out) {
+  if (!h || !ms_out) return ifail(nullptr, MIDAGMA_E_ARG, "indep_profile: bad arguments");
+  std::copy(h->prof, h->prof + 4, ms_out);
+  return MIDAGMA_OK;
+}
+
+extern "C" int midagma_indep_run(midagma_indep* h, int kind, const int64_t* pairs, int64_t m, int64_t P,
+                                 const int32_t* perms, uint64_t seed, int64_t budget_bytes, double* stat, int64_t* ge,
+                                 double* null_out, int32_t* perms_out) {
+  if (!h) return ifail(nullptr, MIDAGMA_E_ARG, "indep_run: null handle");
+  if ((kind != KIND_HSIC && kind != KIND_DCOR) || m < 0 || P < 0 || P > kMaxP || (m > 0 && (!pairs || !stat || !ge)))
+    return ifail(h, MIDAGMA_E_ARG, "indep_run: bad arguments (kind 0 hsic / 1 dcor, 0 <= P <= 65535)");
+  if (h->n == 0) return ifail(h, MIDAGMA_E_ARG, "indep_run: set the data first");
+  if (kind == KIND_HSIC && !h->have_bw) return ifail(h, MIDAGMA_E_ARG, "indep_run: hsic needs the bandwidths");
+  const int64_t n = h->n, d = h->d;
+  for (int64_t k = 0; k < 2 * m; ++k)
+    if (pairs[k] < 0 || pairs[k] >= d) return ifail(h, MIDAGMA_E_ARG, "indep_run: pair index outside [0, d)");
+  if (2 * pair_bytes(n, P) > (int64_t(8) << 30)) return ifail(h, MIDAGMA_E_ARG, "indep_run: P too large for this n");
+  using clock = std::chrono::steady_clock;
+  auto ms_since = [](clock::time_point t0) { return std::chrono::duration<double, std::milli>(clock::now() - t0).count(); };
+  h->prof[0] = h->prof[1] = h->prof[2] = h->prof[3] = 0.0;
+  const clock::time_point t_check = clock::now();
+  if (perms)  // every index is read as an address offset on the device
+    for (int64_t k = 0, e = m * P * n; k < e; ++k)
+      if (perms[k] < 0 || perms[k] >= n) return ifail(h, MIDAGMA_E_ARG, "indep_run: permutation index outside [0, n)");
+  h->prof[0] += ms_since(t_check);
+  if (m == 0) return MIDAGMA_OK;
+
+  const int64_t mbmax = std::min(m, batch_pairs(n, P, budget_bytes));
+  const int64_t ntiles = tiles_of(n), nt = (n + IT - 1) / IT, P1 = P + 1;
+  const bool device_perms = perms == nullptr;
+
+  auto collect = [&](Slot& s) {
+    if (!s.busy) return;
+    HIP_TRY(hipEventSynchronize(s.done));
+    s.busy = false;
+    float ms = 0.f;
+    HIP_TRY(hipEventElapsedTime(&ms, s.up0, s.up));
+    h->prof[1] += ms;
+    HIP_TRY(hipEventElapsedTime(&ms, s.k0, s.k1));
+    h->prof[2] += ms;
+    HIP_TRY(hipEventElapsedTime(&ms, s.k1, s.k2));
+    h->prof[3] += ms;
+    for (int64_t k = 0; k < s.mb; ++k) {
+      const int64_t q = s.q0 + k;
+      // a zero-range column: the reference's centred matrix is exactly 0 (mi_tests.py:21-27, 99-100)
+      const bool zero = h->constant[pairs[2 * q]] || h->constant[pairs[2 * q + 1]];
+      stat[q] = zero ? 0.0 : s.hvals.p[k * P1];
+      ge[q] = zero ? P : s.hge.p[k];
+      if (null_out)
+        for (int64_t p = 0; p < P; ++p) null_out[q * P + p] = zero ? 0.0 : s.hvals.p[k * P1 + 1 + p];
+    }
+    if (perms_out && device_perms && P > 0)
+      HIP_TRY(hipMemcpy(perms_out + s.q0 * P * n, s.dperm.p, s.mb * P * n * sizeof(int32_t), hipMemcpyDeviceToHost));
+  };
+
+  const int rc = iguarded(h, [&] {
+    HIP_TRY(hipSetDevice(h->device));
+    prepare_stats(h, kind);
+    int64_t b = 0;
+    for (int64_t q0 = 0; q0 < m; q0 += mbmax, ++b) {
+      Slot& s = h->slot[b & 1];
+      collect(s);  // batch b - 2: its kernels are done, its buffers free
+      const int64_t mb = std::min(mbmax, m - q0);
+      s.q0 = q0;
+      s.mb = mb;
+      s.hpairs.need(2 * mb), s.dpairs.need(2 * mb);
+      s.hge.need(mb), s.dge.need(mb);
+      s.hvals.need(mb * P1), s.dvals.need(mb * P1);
+      s.partial.need(mb * P1 * ntiles);
+      s.dperm.need(mb * P * n);
+      std::memcpy(s.hpairs.p, pairs + 2 * q0, 2 * mb * sizeof(int64_t));
+      HIP_TRY(hipEventRecord(s.up0, h->copy));
+      HIP_TRY(hipMemcpyAsync(s.dpairs.p, s.hpairs.p, 2 * mb * sizeof(int64_t), hipMemcpyHostToDevice, h->copy));
+      if (!device_perms && P > 0) {
+        s.hperm.need(mb * P * n);
+        const clock::time_point t_stage = clock::now();
+        std::memcpy(s.hperm.p, perms + q0 * P * n, mb * P * n * sizeof(int32_t));
+        h->prof[0] += ms_since(t_stage);
+        HIP_TRY(hipMemcpyAsync(s.dperm.p, s.hperm.p, mb * P * n * sizeof(int32_t), hipMemcpyHostToDevice, h->copy));
+      }
+      HIP_TRY(hipEventRecord(s.up, h->copy));
+      HIP_TRY(hipStreamWaitEvent(h->comp, s.up, 0));
+      HIP_TRY(hipEventRecord(s.k0, h->comp));
+      if (device_perms && P > 0)
+        hipLaunchKernelGGL(indep_perm_kernel, dim3((n + 256 * IPA - 1) / (256 * IPA), P, mb), dim3(256), 0, h->comp,
+                           static_cast<uint32_t>(seed), static_cast<uint32_t>(seed >> 32), q0, static_cast<int>(n),
+                           static_cast<int>(P), s.dperm.p);
+      HIP_TRY(hipEventRecord(s.k1, h->comp));
+      const dim3 grid(ntiles, mb);
+      if (kind == KIND_HSIC) {
+        hipLaunchKernelGGL(indep_main_kernel<KIND_HSIC>, grid, dim3(256), 0, h->comp, h->XT.p, h->rm[kind].p,
+                           h->gm[kind].p, h->c.p, s.dpairs.p, s.dperm.p, static_cast<int>(n), static_cast<int>(nt),
+                           static_cast<int>(P), s.partial.p);
+        hipLaunchKernelGGL(indep_final_kernel<KIND_HSIC>, dim3(mb), dim3(256), 0, h->comp, s.partial.p, s.dpairs.p,
+                           nullptr, static_cast<int>(n), static_cast<int>(ntiles), static_cast<int>(P), s.dvals.p,
+                           s.dge.p);
+      } else {
+        hipLaunchKernelGGL(indep_main_kernel<KIND_DCOR>, grid, dim3(256), 0, h->comp, h->XT.p, h->rm[kind].p,
+                           h->gm[kind].p, nullptr, s.dpairs.p, s.dperm.p, static_cast<int>(n), static_cast<int>(nt),
+                           static_cast<int>(P), s.partial.p);
+        hipLaunchKernelGGL(indep_final_kernel<KIND_DCOR>, dim3(mb), dim3(256), 0, h->comp, s.partial.p, s.dpairs.p,
+                           h->dvar.p, static_cast<int>(n), static_cast<int>(ntiles), static_cast<int>(P), s.dvals.p,
+                           s.dge.p);
+      }
+      HIP_TRY(hipGetLastError());
+      HIP_TRY(hipEventRecord(s.k2, h->comp));
+      HIP_TRY(hipMemcpyAsync(s.hvals.p, s.dvals.p, mb * P1 * sizeof(double), hipMemcpyDeviceToHost, h->comp));
+      HIP_TRY(hipMemcpyAsync(s.hge.p, s.dge.p, mb * sizeof(int64_t), hipMemcpyDeviceToHost, h->comp));
+      HIP_TRY(hipEventRecord(s.done, h->comp));
+      s.busy = true;
+    }
+    // the two batches still in flight, older first
+    collect(h->slot[b & 1]);
+    collect(h->slot[(b + 1) & 1]);
+  });
+  if (rc != MIDAGMA_OK) {
+    // leave nothing in flight that reads the slots
+    (void)hipStreamSynchronize(h->copy);
+    (void)hipStreamSynchronize(h->comp);
+    h->slot[0].busy = h->slot[1].busy = false;
+  }
+  return rc;
+}

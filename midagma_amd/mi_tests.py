@@ -1,0 +1,258 @@
+"""Pairwise independence tests that build the trek regularizers' pair set I -- the reference's
+`notreks.mi_tests` with the permutation tests on the GPU.
+
+Names, signatures, defaults and pair order are the reference's.  'hsic' and 'dcor' run their
+permutation tests in csrc/indep.hip through `midagma_amd.solver.HipIndep`; there is no CPU path for
+them (no device: `HipSolverError`).  'pearson' and 'spearman' are analytic and stay on the host
+(scipy), as in the reference.
+
+One keyword is added, ``perms``:
+  * ``"numpy"`` (default): the host draws ``rng = np.random.default_rng(seed)`` once and calls
+    ``rng.permutation(n)`` num_perm times per pair, in pair order -- the reference's stream, so the
+    p-values are the reference's.  Generation of the next chunk of pairs overlaps the device work
+    of the current one.
+  * ``"device"``: the permutations are made on the GPU from Philox4x32-10 ("Independence
+    tests").  The p-values are valid permutation p-values but come from another stream than the
+    reference's.
+
+Not mirrored: `permutation_pvalue(stat_fn, ...)`, which takes an arbitrary Python callable.
+"""
+from __future__ import annotations
+
+from concurrent.futures import ThreadPoolExecutor
+from dataclasses import dataclass
+from typing import Iterable, List, Literal, Optional, Tuple
+
+import numpy as np
+
+from .solver import HipIndep
+
+__all__ = ["IndepTestResult", "hsic_stat", "dcor_stat", "permutation_null", "test_pairwise_independence",
+           "get_I_from_full_pairwise_tests", "summarize_I", "median_sigma2"]
+
+TestName = Literal["hsic", "dcor", "pearson", "spearman"]
+
+# host bytes of numpy permutations generated ahead of the device (two chunks exist at a time)
+_HOST_CHUNK_BYTES = 128 << 20
+
+
+@dataclass(frozen=True)
+class IndepTestResult:
+    i: int
+    j: int
+    stat: float
+    pvalue: float
+
+
+def median_sigma2(x: np.ndarray) -> float:
+    """The reference's median heuristic (`_rbf_gram`, sigma=None): the median of the off-diagonal
+    squared differences, 1.0 when that median is 0.  Host work: n (n - 1) / 2 values."""
+    x = np.asarray(x, dtype=np.float64).ravel()
+    n = x.shape[0]
+    off = np.empty(n * (n - 1) // 2)
+    k = 0
+    for a in range(n - 1):
+        off[k:k + n - 1 - a] = (x[a] - x[a + 1:]) ** 2
+        k += n - 1 - a
+    med = np.median(off)
+    return float(med) if med > 0 else 1.0
+
+
+def _sigma2(x, sigma) -> float:
+    if sigma is None:
+        return median_sigma2(x)
+    s2 = float(sigma) ** 2
+    return s2 if s2 > 0 else 1.0
+
+
+def _as_data(X) -> np.ndarray:
+    """A C-contiguous float64 copy (the caller's X is never touched), checked."""
+    X = np.array(X, dtype=np.float64, order="C", copy=True)
+    if X.ndim != 2:
+        raise ValueError("X must be a 2-d array (n samples x d variables)")
+    if X.shape[0] < 2:
+        raise ValueError("need at least 2 samples")
+    if X.shape[0] > HipIndep.MAX_N:
+        raise ValueError(f"at most {HipIndep.MAX_N} samples are supported, got {X.shape[0]}")
+    if not np.isfinite(X).all():
+        raise ValueError("X holds inf or nan")
+    return X
+
+
+def _as_pairs(pairs, d: int) -> np.ndarray:
+    P = np.asarray(list(pairs), dtype=np.int64).reshape(-1, 2)
+    if P.size and (P.min() < 0 or P.max() >= d):
+        raise ValueError(f"pair index outside [0, {d})")
+    return P
+
+
+def _two_columns(x, y) -> np.ndarray:
+    x = np.asarray(x, dtype=np.float64).ravel()
+    y = np.asarray(y, dtype=np.float64).ravel()
+    if x.shape != y.shape:
+        raise ValueError("x and y must have the same length")
+    return _as_data(np.column_stack([x, y]))
+
+
+def hsic_stat(x: np.ndarray, y: np.ndarray, sigma_x: Optional[float] = None, sigma_y: Optional[float] = None) -> float:
+    """Biased HSIC estimator (1/n^2) sum(Kc * Lc) with RBF kernels (median-heuristic bandwidths
+    unless given), on the GPU."""
+    X = _two_columns(x, y)
+    eng = HipIndep(X)
+    try:
+        eng.set_bandwidths([_sigma2(X[:, 0], sigma_x), _sigma2(X[:, 1], sigma_y)])
+        stat, _ = eng.run("hsic", [(0, 1)], 0)
+    finally:
+        eng.close()
+    return float(stat[0])
+
+
+def dcor_stat(x: np.ndarray, y: np.ndarray) -> float:
+    """Distance correlation (from the biased distance covariance), on the GPU."""
+    X = _two_columns(x, y)
+    eng = HipIndep(X)
+    try:
+        stat, _ = eng.run("dcor", [(0, 1)], 0)
+    finally:
+        eng.close()
+    return float(stat[0])
+
+
+def _numpy_perms(rng: np.random.Generator, m: int, P: int, n: int) -> np.ndarray:
+    out = np.empty((m, P, n), dtype=np.int32)
+    for q in range(m):
+        for p in range(P):
+            out[q, p] = rng.permutation(n)
+    return out
+
+
+def permutation_null(X, pairs, *, test: str = "hsic", num_perm: int = 200, seed: int = 0, perms: str = "numpy",
+                     device: int = 0, budget_bytes: int = 0, return_null: bool = True):
+    """(stat, ge, null): per pair the observed statistic, ge = #{p : stat_p >= stat} and (m x
+    num_perm, or None) the permuted statistics of the 'hsic' / 'dcor' permutation test.
+    budget_bytes: the device's byte budget per pair batch (0: the library's default); results do
+    not depend on it."""
+    if test not in HipIndep.KINDS:
+        raise ValueError("test must be 'hsic' or 'dcor'")
+    if perms not in ("numpy", "device"):
+        raise ValueError("perms must be 'numpy' or 'device'")
+    X = _as_data(X)
+    n, d = X.shape
+    pairs = _as_pairs(pairs, d)
+    m, P = len(pairs), int(num_perm)
+    if P < 0:
+        raise ValueError("num_perm must be >= 0")
+    eng = HipIndep(X, device)
+    try:
+        if test == "hsic":
+            s2 = np.ones(d)
+            for v in np.unique(pairs):
+                s2[v] = median_sigma2(X[:, v])
+            eng.set_bandwidths(s2)
+        if perms == "device":
+            out = eng.run(test, pairs, P, None, seed, budget_bytes, return_null=return_null)
+            return out[0], out[1], (out[2] if return_null else None)
+        rng = np.random.default_rng(seed)
+        stat = np.zeros(m)
+        ge = np.zeros(m, dtype=np.int64)
+        null = np.zeros((m, P)) if return_null else None
+        chunk = max(1, _HOST_CHUNK_BYTES // max(1, 4 * P * n))
+
+        def consume(q0, q1, pm):
+            out = eng.run(test, pairs[q0:q1], P, pm, 0, budget_bytes, return_null=return_null)
+            stat[q0:q1], ge[q0:q1] = out[0], out[1]
+            if return_null:
+                null[q0:q1] = out[2]
+
+        # the worker thread drives the device (the library call releases the GIL) while this
+        # thread draws the next chunk's permutations
+        with ThreadPoolExecutor(max_workers=1) as pool:
+            pending = None
+            for q0 in range(0, m, chunk):
+                q1 = min(m, q0 + chunk)
+                pm = _numpy_perms(rng, q1 - q0, P, n)
+                if pending is not None:
+                    pending.result()
+                pending = pool.submit(consume, q0, q1, pm)
+            if pending is not None:
+                pending.result()
+        return stat, ge, null
+    finally:
+        eng.close()
+
+
+def _pearson_stat_pvalue(x, y) -> Tuple[float, float]:
+    from scipy import stats
+    r, p = stats.pearsonr(np.asarray(x).ravel(), np.asarray(y).ravel())
+    return float(abs(r)), float(p)
+
+
+def _spearman_stat_pvalue(x, y) -> Tuple[float, float]:
+    import warnings
+
+    from scipy import stats
+    with warnings.catch_warnings():
+        warnings.simplefilter("ignore")  # (scipy warns about constant input; the rule below handles it)
+        rho, p = stats.spearmanr(np.asarray(x).ravel(), np.asarray(y).ravel())
+    if not np.isfinite(rho) or not np.isfinite(p):  # scipy returns nan for constant inputs
+        return 0.0, 1.0
+    return float(abs(rho)), float(p)
+
+
+def test_pairwise_independence(X: np.ndarray, pairs: Iterable[Tuple[int, int]], *, test: TestName = "hsic",
+                               num_perm: int = 200, seed: int = 0,
+                               perms: str = "numpy") -> List[IndepTestResult]:
+    """(stat, pvalue) per pair.  hsic, dcor: permutation p-values (ge + 1) / (num_perm + 1) on the
+    GPU; pearson, spearman: scipy's analytic p-values (num_perm, seed, perms ignored)."""
+    if test not in ("hsic", "dcor", "pearson", "spearman"):
+        raise ValueError("test must be one of 'hsic', 'dcor', 'pearson', 'spearman'")
+    pairs = [(int(i), int(j)) for (i, j) in pairs]
+    if test in ("pearson", "spearman"):
+        X = _as_data(X)
+        _as_pairs(pairs, X.shape[1])
+        fn = _pearson_stat_pvalue if test == "pearson" else _spearman_stat_pvalue
+        out = []
+        for (i, j) in pairs:
+            stat, p = fn(X[:, i], X[:, j])
+            out.append(IndepTestResult(i=i, j=j, stat=stat, pvalue=p))
+        return out
+    stat, ge, _ = permutation_null(X, pairs, test=test, num_perm=num_perm, seed=seed, perms=perms, return_null=False)
+    return [IndepTestResult(i=i, j=j, stat=float(stat[q]), pvalue=float((int(ge[q]) + 1) / (int(num_perm) + 1)))
+            for q, (i, j) in enumerate(pairs)]
+
+
+test_pairwise_independence.__test__ = False  # a library function, not a pytest test
+
+
+def get_I_from_full_pairwise_tests(X: np.ndarray, *, alpha: float = 0.05, test: TestName = "hsic",
+                                   num_perm: int = 200, seed: int = 0, bonferroni: bool = True,
+                                   undirected: bool = True, exclude_diagonal: bool = True,
+                                   perms: str = "numpy") -> np.ndarray:
+    """Test all pairs and return I = {(i, j): p > alpha_eff}, the pairs whose independence is not
+    rejected (alpha_eff = alpha / #pairs under Bonferroni), in the reference's pair order."""
+    X = np.asarray(X)
+    n, d = X.shape
+    pairs: List[Tuple[int, int]] = []
+    if undirected:
+        for i in range(d):
+            for j in range(i + 1, d):
+                pairs.append((i, j))
+    else:
+        for i in range(d):
+            for j in range(d):
+                if exclude_diagonal and i == j:
+                    continue
+                pairs.append((i, j))
+    results = test_pairwise_independence(X, pairs, test=test, num_perm=num_perm, seed=seed, perms=perms)
+    m = len(results)
+    alpha_eff = (alpha / m) if (bonferroni and m > 0) else alpha
+    I = [(r.i, r.j) for r in results if r.pvalue > alpha_eff]
+    return np.asarray(I, dtype=int)
+
+
+def summarize_I(I: np.ndarray, d: int, max_show: int = 10) -> None:
+    I = np.asarray(I, dtype=int)
+    print(f"I size: {len(I)} pairs (d={d})")
+    if len(I) == 0:
+        return
+    print("first pairs:", I[:max_show].tolist(), ("..." if len(I) > max_show else ""))

@@ -17,7 +17,7 @@ import numpy as np
 from . import _lib
 from ._lib import check, dptr
 
-__all__ = ["HipSolver", "HipGroup", "MinimizeResult", "CheckpointRecord", "run_allreduce_minimize",
+__all__ = ["HipSolver", "HipGroup", "HipIndep", "MinimizeResult", "CheckpointRecord", "run_allreduce_minimize",
            "device_count", "colsum_dev", "center_dev", "gram", "row_range"]
 
 
@@ -590,6 +590,94 @@ class HipGroup:
         self.score_partial(W)
         self.allreduce_zbuf()
         return self.score_finish()
+
+
+class HipIndep:
+    """Pairwise permutation independence tests on one GPU (`midagma_indep_*`, csrc/indep.hip):
+    the engine under `midagma_amd.mi_tests`.  Holds a device copy of X (n x d)."""
+
+    KINDS = {"hsic": 0, "dcor": 1}
+    MAX_N = 16384
+
+    def __init__(self, X: np.ndarray, device: int = 0):
+        self.L = _lib.lib()
+        X = _as_f64(X)  # (the library copies it to the device and never writes it)
+        if X.ndim != 2:
+            raise ValueError("X must be n x d")
+        self.n, self.d = int(X.shape[0]), int(X.shape[1])
+        if self.n < 2 or self.n > self.MAX_N:
+            raise ValueError(f"need 2 <= n <= {self.MAX_N} samples, got {self.n}")
+        if not np.isfinite(X).all():
+            raise ValueError("X holds inf or nan")
+        h = C.c_void_p()
+        self._check(self.L.midagma_indep_create(C.byref(h), int(device)), None, "indep_create")
+        self.h = h
+        self._check(self.L.midagma_indep_set_data(self.h, dptr(X), self.n, self.d), self.h, "indep_set_data")
+
+    def _check(self, rc, handle, what):
+        if rc >= 0:
+            return rc
+        m = self.L.midagma_indep_last_error(handle)
+        msg = m.decode() if m else ""
+        if rc == _lib.E_ARG:
+            raise ValueError(f"{what}: {msg}")
+        raise _lib.HipSolverError(f"{what} failed ({rc}): {msg}")
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.L.midagma_indep_destroy(self.h)
+            self.h = None
+
+    def __del__(self):  # pragma: no cover
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def set_bandwidths(self, sigma2):
+        """The RBF kernels' sigma^2 per variable (hsic)."""
+        s2 = _as_f64(sigma2).ravel()
+        self._check(self.L.midagma_indep_set_bandwidths(self.h, dptr(s2), s2.size), self.h, "indep_set_bandwidths")
+
+    def batch_pairs(self, P: int, budget_bytes: int = 0) -> int:
+        """Pairs per device batch under a byte budget (0: the library's default)."""
+        return int(self.L.midagma_indep_batch_pairs(self.h, int(P), int(budget_bytes)))
+
+    def profile(self) -> dict:
+        """The last run's stage times in ms, summed over its batches (diagnostics)."""
+        ms = np.zeros(4)
+        self._check(self.L.midagma_indep_profile(self.h, dptr(ms)), self.h, "indep_profile")
+        return dict(zip(("host_stage_ms", "upload_ms", "perm_kernel_ms", "stat_kernel_ms"), ms.tolist()))
+
+    def run(self, kind: str, pairs, P: int, perms=None, seed: int = 0, budget_bytes: int = 0,
+            return_null: bool = False, return_perms: bool = False):
+        """(stat, ge[, null][, perms]) per pair: the observed statistic, ge = #{p : stat_p >= stat}
+        over P permutations, the P permuted statistics (m x P) and the device's permutations.
+        perms: explicit m x P x n int32 permutations, or None for device permutations from `seed`."""
+        pairs = np.ascontiguousarray(pairs, dtype=np.int64).reshape(-1, 2)
+        m, P = int(pairs.shape[0]), int(P)
+        if perms is not None:
+            perms = np.ascontiguousarray(perms, dtype=np.int32)
+            if perms.shape != (m, P, self.n):
+                raise ValueError(f"perms must be {(m, P, self.n)}, got {perms.shape}")
+        stat = np.zeros(m)
+        ge = np.zeros(m, dtype=np.int64)
+        null = np.zeros((m, P)) if return_null else None
+        pout = np.zeros((m, P, self.n), dtype=np.int32) if (return_perms and perms is None) else None
+
+        def vp(a):
+            return None if a is None else C.c_void_p(a.ctypes.data)
+
+        rc = self.L.midagma_indep_run(self.h, self.KINDS[kind], vp(pairs), m, P, vp(perms),
+                                      C.c_uint64(int(seed) & (2**64 - 1)), int(budget_bytes), dptr(stat), vp(ge),
+                                      dptr(null), vp(pout))
+        self._check(rc, self.h, "indep_run")
+        out = [stat, ge]
+        if return_null:
+            out.append(null)
+        if return_perms:
+            out.append(perms if perms is not None else pout)
+        return tuple(out)
 
 
 def run_allreduce_minimize(backend, W, mu, max_iter, s, lr, tol=1e-6, beta_1=0.99, beta_2=0.999,
