@@ -77,13 +77,11 @@ __global__ __launch_bounds__(NTHREADS, 2) void gemm_cupart_kernel(int64_t K, int
   }
 }
 
-void launch_gemm_cupart(int64_t M, int64_t N, int64_t K, const double* A, int64_t lda, bool a_trans, const double* B,
-                        int64_t ldb, GemmB bmode, double* C, int64_t ldc, int split, int64_t slice_stride,
-                        const State* st, int ses, int* ctr, hipStream_t stream) {
-  if (M % 128 || N % 128 || K % 16 || split < 1 || ses < 1) throw std::invalid_argument("launch_gemm_cupart: bad shape");
-  const int64_t ktiles16 = K / 16, per16 = (ktiles16 + split - 1) / split;
-  const int nsplit = (int)((ktiles16 + per16 - 1) / per16);
-  const int tm = (int)(M / 128), tn = (int)(N / 128);
+void launch_gemm_cupart(const GemmSpec& gs, const State* st, int ses, int* ctr, hipStream_t stream) {
+  if (gs.M % 128 || gs.N % 128 || gs.K % 16 || gs.split < 1 || ses < 1 || gs.epi != EPI_STORE)
+    throw std::invalid_argument("launch_gemm_cupart: bad shape");
+  const SplitK sk = split_k(gs.K, 16, gs.split);
+  const int tm = (int)(gs.M / 128), tn = (int)(gs.N / 128);
   static int cus = 0;
   static bool attr = false;
   if (!cus) {
@@ -92,28 +90,20 @@ void launch_gemm_cupart(int64_t M, int64_t N, int64_t K, const double* A, int64_
     HIP_TRY(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
   }
   if (!attr) {
-    for (const void* f : {reinterpret_cast<const void*>(gemm_cupart_kernel<1, B_PLAIN>),
-                          reinterpret_cast<const void*>(gemm_cupart_kernel<1, B_IMINUS>),
-                          reinterpret_cast<const void*>(gemm_cupart_kernel<0, B_PLAIN>),
-                          reinterpret_cast<const void*>(gemm_cupart_kernel<0, B_IMINUS>)})
-      HIP_TRY(hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kGemmPipeLds));
+    gemm_forms([](auto a, auto b, auto e) {
+      if constexpr (decltype(e)::value == EPI_STORE)
+        set_lds(gemm_cupart_kernel<decltype(a)::value, decltype(b)::value>, kGemmPipeLds);
+    });
     attr = true;
   }
   HIP_TRY(hipMemsetAsync(ctr, 0, sizeof(int), stream));
-  const int ntasks = tm * tn * nsplit;
+  const int ntasks = tm * tn * sk.nsplit;
   const dim3 grid((unsigned)(2 * cus));
-#define MIDAGMA_CP(AM, BM)                                                                                    \
-  hipLaunchKernelGGL((gemm_cupart_kernel<AM, BM>), grid, dim3(NTHREADS), kGemmPipeLds, stream, K, per16 * 16, tm, \
-                     tn, ntasks, A, lda, B, ldb, C, ldc, slice_stride, st, ses, ctr)
-  if (a_trans && bmode == B_PLAIN)
-    MIDAGMA_CP(1, B_PLAIN);
-  else if (a_trans)
-    MIDAGMA_CP(1, B_IMINUS);
-  else if (bmode == B_PLAIN)
-    MIDAGMA_CP(0, B_PLAIN);
-  else
-    MIDAGMA_CP(0, B_IMINUS);
-#undef MIDAGMA_CP
+  gemm_dispatch(gs.a_trans, gs.bmode, EPI_STORE, [&](auto a, auto b, auto) {
+    hipLaunchKernelGGL((gemm_cupart_kernel<decltype(a)::value, decltype(b)::value>), grid, dim3(NTHREADS),
+                       kGemmPipeLds, stream, gs.K, sk.kslice, tm, tn, ntasks, gs.A, gs.lda, gs.B, gs.ldb, gs.C, gs.ldc,
+                       gs.slice_stride, st, ses, ctr);
+  });
   HIP_TRY(hipGetLastError());
 }
 

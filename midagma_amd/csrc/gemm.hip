@@ -4,13 +4,15 @@
 //   data mode : Y = X_k @ (I - W)  then  Z_k = X_k^T @ Y      (l2, row shard k)
 //   logistic  : Y = expit(X_k @ W)  then  Z_k = X_k^T @ Y      (+ loss partials)
 //
-// 64 x 64 output tile per 256-thread workgroup, 64-deep K tiles staged through
-// LDS in conflict-free images (mfma64.h); I - W is formed while staging B, the
-// sigmoid and the logistic loss are fused into the epilogue.  Long K (= rows of
-// the shard) is split over blockIdx.z into fixed slices summed in fixed order.
+// Two tiers (launch_gemm): the pipelined 128 x 128 tile kernel (gemm_pipe_kernel) when M and N
+// are multiples of 128, else the 64 x 64 tile kernel (gemm_kernel) below: 64 x 64 output tile per
+// 256-thread workgroup, 64-deep K tiles staged through LDS in conflict-free images (mfma64.h).
+// In both, I - W is formed while staging B, the sigmoid and the logistic loss are fused into the
+// epilogue, and long K (= rows of the shard) is split into fixed slices summed in fixed order.
 #include <algorithm>
 #include <cstdlib>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "binv_tile.h"
@@ -91,226 +93,19 @@ __global__ __launch_bounds__(NTHREADS) void gemm_kernel(int64_t K, int64_t kslic
   if (threadIdx.x == 0) loss_part[blockIdx.y * gridDim.x + blockIdx.x] = red[0];
 }
 
-// ---- 128 x 128 tile GEMM (the data-mode and large-d workhorse) ---------------------------
-// 4 waves in 2 x 2, each owning a 64 x 64 sub-tile = 4 x 4 accumulators of 16 x 16 (64 f64
-// accumulator values per lane).  BK = 16, LDS double-buffered with register prefetch of the
-// next k-tile (one barrier per k-tile).  LDS images (strides in doubles, conflict-free for
-// the MFMA fragment reads of a 32-lane group):
-//   op(A) from A[m][k] : [m][k] image, stride 17  (34 r dwords: distinct banks mod 64 for
-//                        ds_read_b64 AND mod 32 for the ds_read2_b64 hipcc forms from two
-//                        k-steps; stride 18 gave a 2-way conflict there: SQ_LDS_BANK_CONFLICT)
-//   op(A) from A[k][m] : [k][m] image, stride 144 (= 16 mod 32)
-//   op(B)              : [k][n] image, stride 144
 // Workgroups are remapped so consecutive tiles (which share an A panel) run on one XCD.
-constexpr int G_BM = 128, G_BN = 128, G_BK = 16;
-constexpr int G_SMK = 17, G_SKM = 144;
-constexpr int G_IMG = 16 * 144;  // doubles per operand image (>= 128 * 17)
-
 __device__ __forceinline__ int xcd_remap(int w, int nwg) {
   const int q = nwg / 8, r = nwg % 8, x = w % 8;
   return (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + w / 8;
 }
 
-template <bool ATRANS, int BMODE, int EPI>
-__global__ __launch_bounds__(NTHREADS, 2) void gemm128_kernel(int64_t K, int64_t kslice, int tiles_m, int tiles_n,
-                                                              const double* __restrict__ A, int64_t lda,
-                                                              const double* __restrict__ B, int64_t ldb,
-                                                              double* __restrict__ C, int64_t ldc,
-                                                              int64_t slice_stride, double* __restrict__ loss_part,
-                                                              int64_t m_valid, int64_t n_valid,
-                                                              const State* __restrict__ st) {
-  if (st && st->status != ST_RUNNING) return;
-  extern __shared__ __attribute__((aligned(16))) double smem[];
-  const int nwg = gridDim.x;
-  const int t = xcd_remap(blockIdx.x, nwg);
-  const int per_slice = tiles_m * tiles_n;
-  const int z = t / per_slice, rem = t % per_slice;
-  int bm = rem / tiles_n, bn = rem % tiles_n;
-  if (EPI == EPI_SUB_BAND || EPI == EPI_SUB_PRE || EPI == EPI_SUB_MID) {
-    // trailing update of the blocked inverse: the tile grid skips the pivot band
-    // [m_valid, m_valid + n_valid) (in 128-tiles) in both rows and columns
-    bm += bm >= (int)m_valid ? (int)n_valid : 0;
-    bn += bn >= (int)m_valid ? (int)n_valid : 0;
-  }
-  const int64_t m0 = (int64_t)bm * G_BM, n0 = (int64_t)bn * G_BN;
-  const int64_t k_begin = (int64_t)z * kslice;
-  const int64_t k_end = (k_begin + kslice < K) ? k_begin + kslice : K;
-  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-  const int r = lane & 15, kq = lane >> 4;
-  const int mb = (w >> 1) * 64, nbs = (w & 1) * 64;
-
-  // Register prefetch of the next k-tile.  Straight-line code (no lambdas, no conditional
-  // loads) so the staging registers stay in VGPRs; the last iteration re-loads its own
-  // tile into the idle buffer, which is harmless.
-  double2 ra0, ra1, ra2, ra3, rb0, rb1, rb2, rb3;
-  // tile-invariant per-thread offsets (32-bit) and uniform tile bases
-  const double* Ablk = ATRANS ? A + m0 : A + m0 * lda;
-  const int64_t a_kstride = ATRANS ? lda : 1;
-  const double* Bblk = B + n0;
-  int offA[4], offB[4];
-#pragma unroll
-  for (int it = 0; it < 4; ++it) {
-    const int i_ = it * NTHREADS + tid;
-    offA[it] = ATRANS ? (i_ >> 6) * (int)lda + 2 * (i_ & 63) : (i_ >> 3) * (int)lda + 2 * (i_ & 7);
-    offB[it] = (i_ >> 6) * (int)ldb + 2 * (i_ & 63);
-  }
-#define G128_LOAD1(IT, RA, RB, KT)                                                              \
-  {                                                                                             \
-    const int i_ = (IT) * NTHREADS + tid;                                                       \
-    RA = *reinterpret_cast<const double2*>(Ablk + (KT) * a_kstride + offA[IT]);                 \
-    double2 v_ = *reinterpret_cast<const double2*>(Bblk + (KT) * ldb + offB[IT]);               \
-    if (BMODE == B_IMINUS) {                                                                    \
-      const int64_t kg_ = (KT) + (i_ >> 6), ng_ = n0 + 2 * (i_ & 63);                            \
-      v_.x = (kg_ == ng_ ? 1.0 : 0.0) - v_.x;                                                    \
-      v_.y = (kg_ == ng_ + 1 ? 1.0 : 0.0) - v_.y;                                                \
-    }                                                                                           \
-    RB = v_;                                                                                    \
-  }
-#define G128_STORE1(IT, RA, RB, AS, BS)                                                        \
-  {                                                                                             \
-    const int i_ = (IT) * NTHREADS + tid;                                                       \
-    if (ATRANS)                                                                                 \
-      *reinterpret_cast<double2*>((AS) + (i_ >> 6) * G_SKM + 2 * (i_ & 63)) = RA;               \
-    else {                                                                                      \
-      double* a_ = (AS) + (i_ >> 3) * G_SMK + 2 * (i_ & 7); /* odd stride: 8-byte aligned */    \
-      a_[0] = RA.x;                                                                             \
-      a_[1] = RA.y;                                                                             \
-    }                                                                                           \
-    *reinterpret_cast<double2*>((BS) + (i_ >> 6) * G_SKM + 2 * (i_ & 63)) = RB;                 \
-  }
-#define G128_LOAD(KT)                 \
-  G128_LOAD1(0, ra0, rb0, KT)         \
-  G128_LOAD1(1, ra1, rb1, KT)         \
-  G128_LOAD1(2, ra2, rb2, KT)         \
-  G128_LOAD1(3, ra3, rb3, KT)
-#define G128_STORE(AS, BS)            \
-  G128_STORE1(0, ra0, rb0, AS, BS)    \
-  G128_STORE1(1, ra1, rb1, AS, BS)    \
-  G128_STORE1(2, ra2, rb2, AS, BS)    \
-  G128_STORE1(3, ra3, rb3, AS, BS)
-
-  dbl4 acc[4][4];
-#pragma unroll
-  for (int i = 0; i < 4; ++i)
-#pragma unroll
-    for (int j = 0; j < 4; ++j) acc[i][j] = dbl4{0.0, 0.0, 0.0, 0.0};
-
-  double* As0 = smem;
-  double* As1 = smem + 2 * G_IMG;
-  if (k_begin < k_end) {
-    G128_LOAD(k_begin)
-    G128_STORE(As0, As0 + G_IMG)
-  }
-  __syncthreads();
-  for (int64_t kt = k_begin; kt < k_end; kt += G_BK) {
-    const int64_t kn = (kt + G_BK < k_end) ? kt + G_BK : kt;
-    G128_LOAD(kn)
-    // keep the prefetch issued ahead of the MFMA block (hipcc otherwise sinks the loads next to
-    // their LDS stores, serializing memory latency and compute)
-    __builtin_amdgcn_sched_barrier(0);
-    const double* As = As0;
-    const double* Bs = As0 + G_IMG;
-#pragma unroll
-    for (int kk = 0; kk < G_BK / 4; ++kk) {
-      const int k = kk * 4 + kq;
-      double a[4], b[4];
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        a[i] = ATRANS ? As[k * G_SKM + mb + i * 16 + r] : As[(mb + i * 16 + r) * G_SMK + k];
-        b[i] = Bs[k * G_SKM + nbs + i * 16 + r];
-      }
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) acc[i][j] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[i], b[j], acc[i][j], 0, 0, 0);
-    }
-    G128_STORE(As1, As1 + G_IMG)
-    __syncthreads();
-    double* tmp = As0;
-    As0 = As1;
-    As1 = tmp;
-  }
-#undef G128_LOAD
-#undef G128_STORE
-#undef G128_LOAD1
-#undef G128_STORE1
-
-  double* Ct = C + (int64_t)z * slice_stride;
-  if (EPI == EPI_SUB_BAND) {  // C = C0 - acc, C0 passed as loss_part; slice_stride = check flags
-    const double* C0 = loss_part;
-    int flag = 0;
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-      for (int j = 0; j < 4; ++j)
-#pragma unroll
-        for (int tt = 0; tt < 4; ++tt) {
-          const int64_t row = m0 + mb + i * 16 + acc_row(lane, tt);
-          const int64_t col = n0 + nbs + j * 16 + acc_col(lane);
-          const double v = C0[row * ldc + col] - acc[i][j][tt];
-          C[row * ldc + col] = v;
-          flag |= (v + 1e-16 < 0.0 ? 1 : 0) | (isfinite(v) ? 0 : 2);
-        }
-    if (slice_stride && flag) atomicOr(const_cast<int32_t*>(&st->flags), flag);
-    return;
-  }
-  if (EPI == EPI_STORE) {
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-      for (int j = 0; j < 4; ++j)
-#pragma unroll
-        for (int tt = 0; tt < 4; ++tt) {
-          const int64_t row = m0 + mb + i * 16 + acc_row(lane, tt);
-          const int64_t col = n0 + nbs + j * 16 + acc_col(lane);
-          Ct[row * ldc + col] = acc[i][j][tt];
-        }
-    return;
-  }
-  // (sigmoid: the accumulators pass through a per-lane LDS stage so that the transcendental
-  // loop can stay rolled without demoting acc to scratch; see gemm_pipe_kernel)
-  const bool want_loss = loss_part != nullptr && (st == nullptr || st->ckpt_pending);
-  double part = 0.0;
-  __syncthreads();
-  double* stg = smem + (tid >> 6) * 1024 + lane;
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-#pragma unroll
-    for (int j = 0; j < 4; ++j)
-#pragma unroll
-      for (int tt = 0; tt < 4; ++tt) stg[(4 * j + tt) * 64] = acc[i][j][tt];
-#pragma unroll 1
-    for (int jt = 0; jt < 16; ++jt) {
-      const int j = jt >> 2, tt = jt & 3;
-      {
-        const int64_t row = m0 + mb + i * 16 + acc_row(lane, tt);
-        const int64_t col = n0 + nbs + j * 16 + acc_col(lane);
-        const double v = stg[jt * 64];
-        if (want_loss && row < m_valid && col < n_valid)  // X[row][col]: A's (m, k) = (row, col)
-          part += logaddexp0(v) - (ATRANS ? A[col * lda + row] : A[row * lda + col]) * v;
-        Ct[row * ldc + col] = 1.0 / (1.0 + exp(-v));
-      }
-    }
-  }
-  if (!want_loss) return;
-  __syncthreads();
-  double* red = smem;
-  red[tid] = part;
-  __syncthreads();
-  for (int s2 = NTHREADS / 2; s2 > 0; s2 >>= 1) {
-    if (tid < s2) red[tid] += red[tid + s2];
-    __syncthreads();
-  }
-  if (tid == 0) loss_part[EPI == EPI_SIGMOID_SPLIT ? blockIdx.x - per_slice : blockIdx.x] = red[0];
-}
-
-constexpr size_t kGemm128Lds = 4 * G_IMG * sizeof(double);
-
 // ---- pipelined 128 x 128 tile GEMM (data-mode and cov-mode score GEMMs) --------------------
-// The A tile goes through a double-buffered LDS image shared by the 4 waves; each wave owns all
-// 128 rows x 32 columns (8 x 2 accumulators) and loads its B values straight into MFMA operand
-// registers.  The software pipeline follows the vendor DGEMM's (measured: rocBLAS 94% on the
-// X(I-W) shape where the 2 x 2-wave gemm128 above reached 83%):
+// One 128 x 128 output tile per 256-thread workgroup, 16-deep K tiles; workgroup w takes tile
+// xcd_remap(w).  The A tile goes through a double-buffered LDS image shared by the 4 waves; each
+// wave owns all 128 rows x 32 columns (8 x 2 accumulators of 16 x 16) and loads its B values
+// straight into MFMA operand registers.  The software pipeline follows the vendor DGEMM's
+// (measured: rocBLAS 94% on the X(I-W) shape where this kernel's unpipelined predecessor, 4 waves
+// in 2 x 2 with both operands staged through LDS, reached 83%):
 //   * k is permuted inside a 16-deep tile: lane quarter kq takes k = 4 kq + kk at k-step kk, so
 //     one lane's B values of a k-step sit in one row of B, and its two columns 2r, 2r+1 (output
 //     column c of accumulator j is n = 2c + j) are one 16-B load;
@@ -323,7 +118,8 @@ constexpr size_t kGemm128Lds = 4 * G_IMG * sizeof(double);
 //   * B row kk of the next tile is reloaded into the same registers right after k-step kk's
 //     MFMAs are issued (no loop-carried register copies, which made hipcc drain the loads).
 // AMODE 1: A stored [k][m] (lda), AMODE 0: A stored [m][k].  BMODE B_IMINUS forms I - B in
-// registers.  Split-K slices as gemm128.  Measured at n = 1e6, d = 1000 (MI355X): X(I-W) from
+// registers.  Split-K: K slice z = t / (tiles_m tiles_n) of kslice, written to C + z slice_stride.
+// Measured at n = 1e6, d = 1000 (MI355X): X(I-W) from
 // X^T 29.1 ms (B = I - W pre-formed, 91.7% of FP64 peak), X^T Y split 16 28.7 ms (92.8%).
 constexpr int P_S = 132;
 constexpr int P_IMG = 16 * P_S;
@@ -899,169 +695,125 @@ __global__ __launch_bounds__(NTHREADS, 2) void gemm_trail128_kernel(Gemm2Args a2
 
 constexpr size_t kGemmLds = (2 * 64 * SB) * sizeof(double);
 
-template <bool AT, int BM, int EP>
-static void set_attr() {
-  HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_kernel<AT, BM, EP>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)kGemmLds));
+// ---- host side: one list of the GEMM forms, one dispatch ------------------------------------
+// Every (a_trans, bmode, epi) launch_gemm can be asked for, as compile-time tags.  The launchers
+// pick their kernel from this list (gemm_dispatch) and gemm_setup_attributes walks the same list,
+// so a form that can be launched has its attribute call and no other form is instantiated.
+template <int V>
+using ic = std::integral_constant<int, V>;
+template <class F>
+static void gemm_forms(F&& f) {
+  f(ic<0>{}, ic<B_PLAIN>{}, ic<EPI_STORE>{});
+  f(ic<0>{}, ic<B_IMINUS>{}, ic<EPI_STORE>{});
+  f(ic<1>{}, ic<B_PLAIN>{}, ic<EPI_STORE>{});
+  f(ic<1>{}, ic<B_IMINUS>{}, ic<EPI_STORE>{});
+  f(ic<0>{}, ic<B_PLAIN>{}, ic<EPI_SIGMOID>{});
+  f(ic<1>{}, ic<B_PLAIN>{}, ic<EPI_SIGMOID>{});
+  f(ic<0>{}, ic<B_PLAIN>{}, ic<EPI_SIGMOID_SPLIT>{});
+  f(ic<1>{}, ic<B_PLAIN>{}, ic<EPI_SIGMOID_SPLIT>{});
+}
+// the forms the narrower kernels have (the pipelined kernel has them all)
+constexpr bool gemm64_has(int a, int epi) { return epi == EPI_STORE || (epi == EPI_SIGMOID && !a); }
+constexpr bool gemm_trail_has(int a, int epi) { return a == 1 && epi == EPI_STORE; }
+
+// f(a, b, e) on the form equal to the run-time triple; false: there is no such form
+template <class F>
+static bool gemm_dispatch(bool a_trans, int bmode, int epi, F&& f) {
+  bool hit = false;
+  gemm_forms([&](auto a, auto b, auto e) {
+    if (a == (int)a_trans && b == bmode && e == epi) {
+      f(a, b, e);
+      hit = true;
+    }
+  });
+  return hit;
 }
 
-template <bool AT, int BM, int EP>
-static void set_attr128() {
-  HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(gemm128_kernel<AT, BM, EP>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)kGemm128Lds));
-}
-
-template <int AM, int BM, int EP>
-static void set_attr_pipe() {
-  HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_pipe_kernel<AM, BM, EP>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)kGemmPipeLds));
-}
-
-template <int AM, int BM>
-static void set_attr_gt() {
-  HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_trail_kernel<AM, BM>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)kGemmTrailLds));
-  HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_trail128_kernel<AM, BM>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)kGemmPipeLds));
+template <class Kern>
+static void set_lds(Kern* kern, size_t bytes) {
+  HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
+                              (int)bytes));
 }
 
 void gemm_setup_attributes() {
-  set_attr_gt<1, B_PLAIN>();
-  set_attr_gt<1, B_IMINUS>();
-  set_attr_gt<0, B_PLAIN>();
-  set_attr_gt<0, B_IMINUS>();
-  set_attr_pipe<1, B_PLAIN, EPI_STORE>();
-  set_attr_pipe<1, B_IMINUS, EPI_STORE>();
-  set_attr_pipe<0, B_PLAIN, EPI_STORE>();
-  set_attr_pipe<0, B_IMINUS, EPI_STORE>();
-  set_attr_pipe<1, B_PLAIN, EPI_SIGMOID>();
-  set_attr_pipe<0, B_PLAIN, EPI_SIGMOID>();
-  set_attr_pipe<1, B_PLAIN, EPI_SIGMOID_SPLIT>();
-  set_attr_pipe<0, B_PLAIN, EPI_SIGMOID_SPLIT>();
-  set_attr_pipe<0, B_PLAIN, EPI_SUB_BAND>();
-  set_attr_pipe<0, B_PLAIN, EPI_SUB_CROSS>();
-  set_attr_pipe<0, B_PLAIN, EPI_SUB_CROSS_MID>();
+  gemm_forms([](auto a, auto b, auto e) {
+    constexpr int A = decltype(a)::value, B = decltype(b)::value, E = decltype(e)::value;
+    set_lds(gemm_pipe_kernel<A, B, E>, kGemmPipeLds);
+    if constexpr (gemm64_has(A, E)) set_lds(gemm_kernel<(A != 0), B, E>, kGemmLds);
+    if constexpr (gemm_trail_has(A, E)) {
+      set_lds(gemm_trail_kernel<A, B>, kGemmTrailLds);
+      set_lds(gemm_trail128_kernel<A, B>, kGemmPipeLds);
+    }
+  });
+  // the trailing updates' tile bodies (launch_trail128, launch_trail128_split)
+  set_lds(gemm_pipe_kernel<0, B_PLAIN, EPI_SUB_BAND>, kGemmPipeLds);
+  set_lds(gemm_pipe_kernel<0, B_PLAIN, EPI_SUB_CROSS>, kGemmPipeLds);
+  set_lds(gemm_pipe_kernel<0, B_PLAIN, EPI_SUB_CROSS_MID>, kGemmPipeLds);
 #ifdef MIDAGMA_EXPERIMENTS
-  set_attr_pipe<0, B_PLAIN, EPI_SUB_PRE>();
+  set_lds(gemm_pipe_kernel<0, B_PLAIN, EPI_SUB_PRE>, kGemmPipeLds);
 #endif
-  set_attr128<false, B_PLAIN, EPI_STORE>();
-  set_attr128<false, B_IMINUS, EPI_STORE>();
-  set_attr128<true, B_PLAIN, EPI_STORE>();
-  set_attr128<true, B_IMINUS, EPI_STORE>();
-  set_attr128<false, B_PLAIN, EPI_SIGMOID>();
-  set_attr128<true, B_PLAIN, EPI_SIGMOID>();
-  set_attr128<false, B_PLAIN, EPI_SUB_BAND>();
-  set_attr<false, B_PLAIN, EPI_STORE>();
-  set_attr<false, B_IMINUS, EPI_STORE>();
-  set_attr<true, B_PLAIN, EPI_STORE>();
-  set_attr<true, B_IMINUS, EPI_STORE>();
-  set_attr<false, B_PLAIN, EPI_SIGMOID>();
 }
 
-void launch_gemm(int64_t M, int64_t N, int64_t K, const double* A, int64_t lda, bool a_trans, const double* B,
-                 int64_t ldb, GemmB bmode, double* C, int64_t ldc, GemmEpi epi, int split, int64_t slice_stride,
-                 double* loss_part, int64_t m_valid, int64_t n_valid, const State* st, hipStream_t stream) {
+// K cut into at most `split` slices of whole `tile`-deep K tiles: the slices used, and their depth
+struct SplitK {
+  int nsplit;
+  int64_t kslice;
+};
+static SplitK split_k(int64_t K, int tile, int split) {
+  const int64_t ktiles = K / tile, per = (ktiles + split - 1) / split;
+  return {(int)((ktiles + per - 1) / per), per * tile};
+}
+
+void launch_gemm(const GemmSpec& gs, const State* st, hipStream_t stream) {
   // (K % 16 suffices for the pipelined kernel: the k loop of a padded problem may stop at the
   // first 16-multiple past the logical size, the rest of A's k range being zero)
-  if (M % 64 || N % 64 || K % 16 || split < 1) throw std::invalid_argument("launch_gemm: bad shape");
-  static const bool force64 = knob_set("MIDAGMA_EXP_GEMM64");  // experiment knobs (knobs.h)
-  static const bool no_pipe = knob_set("MIDAGMA_EXP_NO_PIPE");
-  if (M % 128 == 0 && N % 128 == 0 && K % 16 == 0 && !force64 && !no_pipe &&
-      (epi == EPI_STORE || (epi == EPI_SIGMOID && (split == 1 || split == 2) && bmode == B_PLAIN))) {
-    const int64_t ktiles16 = K / 16;
-    const int64_t per16 = (ktiles16 + split - 1) / split;
-    const int nsplit = (int)((ktiles16 + per16 - 1) / per16);
-    const int tm = (int)(M / 128), tn = (int)(N / 128);
-    const int64_t nwg = (int64_t)tm * tn * nsplit;
-    const int64_t kslice = per16 * 16;
-    if (epi == EPI_SIGMOID && nsplit > 1 && (nsplit != 2 || (tm * tn) % 8 || slice_stride < M * ldc))
+  if (gs.M % 64 || gs.N % 64 || gs.K % 16 || gs.split < 1) throw std::invalid_argument("launch_gemm: bad shape");
+  static const bool force64 = knob_set("MIDAGMA_EXP_GEMM64");  // experiment knob (knobs.h)
+  const bool sigmoid = gs.epi == EPI_SIGMOID;
+  const char* no_form = sigmoid ? "launch_gemm: sigmoid form" : "launch_gemm: no kernel of this form";
+  if (gs.M % 128 == 0 && gs.N % 128 == 0 && !force64) {
+    const SplitK sk = split_k(gs.K, 16, gs.split);
+    const int tm = (int)(gs.M / 128), tn = (int)(gs.N / 128);
+    const int64_t nwg = (int64_t)tm * tn * sk.nsplit;
+    if (sigmoid && sk.nsplit > 1 && (sk.nsplit != 2 || (tm * tn) % 8 || gs.slice_stride < gs.M * gs.ldc))
       throw std::invalid_argument("launch_gemm: the serial split sigmoid needs 2 slices, tiles % 8 == 0 and C with "
                                   "room for the partial and the flags");
-#define MIDAGMA_GEMMP(AM, BM, EP)                                                                         \
-  hipLaunchKernelGGL((gemm_pipe_kernel<AM, BM, EP>), dim3((unsigned)nwg), dim3(NTHREADS), kGemmPipeLds, stream, K, \
-                     kslice, tm, tn, A, lda, B, ldb, C, ldc, slice_stride, loss_part, m_valid, n_valid, st)
-    if (epi == EPI_SIGMOID) {
-      if (K > N) throw std::invalid_argument("launch_gemm: sigmoid form (op(A) is X: K <= N)");
-      if (nsplit > 1 && a_trans)
-        MIDAGMA_GEMMP(1, B_PLAIN, EPI_SIGMOID_SPLIT);
-      else if (nsplit > 1)
-        MIDAGMA_GEMMP(0, B_PLAIN, EPI_SIGMOID_SPLIT);
-      else if (a_trans)
-        MIDAGMA_GEMMP(1, B_PLAIN, EPI_SIGMOID);
-      else
-        MIDAGMA_GEMMP(0, B_PLAIN, EPI_SIGMOID);
-    } else if (a_trans && bmode == B_PLAIN) {
-      MIDAGMA_GEMMP(1, B_PLAIN, EPI_STORE);
-    } else if (a_trans) {
-      MIDAGMA_GEMMP(1, B_IMINUS, EPI_STORE);
-    } else if (bmode == B_PLAIN) {
-      MIDAGMA_GEMMP(0, B_PLAIN, EPI_STORE);
-    } else {
-      MIDAGMA_GEMMP(0, B_IMINUS, EPI_STORE);
-    }
-#undef MIDAGMA_GEMMP
+    if (sigmoid && gs.K > gs.N) throw std::invalid_argument("launch_gemm: sigmoid form (op(A) is X: K <= N)");
+    const int epi = sigmoid && sk.nsplit > 1 ? (int)EPI_SIGMOID_SPLIT : gs.epi;
+    if (!gemm_dispatch(gs.a_trans, gs.bmode, epi, [&](auto a, auto b, auto e) {
+          hipLaunchKernelGGL((gemm_pipe_kernel<decltype(a)::value, decltype(b)::value, decltype(e)::value>),
+                             dim3((unsigned)nwg), dim3(NTHREADS), kGemmPipeLds, stream, gs.K, sk.kslice, tm, tn, gs.A,
+                             gs.lda, gs.B, gs.ldb, gs.C, gs.ldc, gs.slice_stride, gs.loss_part, gs.m_valid,
+                             gs.n_valid, st);
+        }))
+      throw std::invalid_argument(no_form);
     HIP_TRY(hipGetLastError());
     return;
   }
-  // the older kernels step K by 64: a k extent cut at a 16-multiple (Kd(): the operands' rows
+  // the 64-tile kernel steps K by 64: a k extent cut at a 16-multiple (Kd(): the operands' rows
   // past it are zero and allocated up to the 64-padded size) is rounded back up
-  if (K % 64) K = (K + 63) / 64 * 64;
-  if (M % 128 == 0 && N % 128 == 0 && K % 128 == 0 && !force64) {
-    const int64_t ktiles16 = K / G_BK;
-    const int64_t per16 = (ktiles16 + split - 1) / split;
-    const int nsplit = (int)((ktiles16 + per16 - 1) / per16);
-    const int tm = (int)(M / G_BM), tn = (int)(N / G_BN);
-    const int64_t nwg = (int64_t)tm * tn * nsplit;
-    const int64_t kslice = per16 * G_BK;
-#define MIDAGMA_GEMM128(AT, BM, EP)                                                                       \
-  hipLaunchKernelGGL((gemm128_kernel<AT, BM, EP>), dim3((unsigned)nwg), dim3(NTHREADS), kGemm128Lds, stream, K, \
-                     kslice, tm, tn, A, lda, B, ldb, C, ldc, slice_stride, loss_part, m_valid, n_valid, st)
-    if (epi == EPI_SIGMOID) {
-      // (a_trans: the epilogue reads X[m][n] from X^T's row n < N; X^T has D >= N rows, zero past d,
-      // so the k loop may stop short of N as in the pipelined kernel)
-      if (bmode != B_PLAIN || nsplit != 1 || (a_trans && K > N))
-        throw std::invalid_argument("launch_gemm: sigmoid form");
-      if (a_trans)
-        MIDAGMA_GEMM128(true, B_PLAIN, EPI_SIGMOID);
-      else
-        MIDAGMA_GEMM128(false, B_PLAIN, EPI_SIGMOID);
-    } else if (epi == EPI_SUB_BAND) {
-      throw std::invalid_argument("launch_gemm: use launch_trail128");
-    } else if (!a_trans && bmode == B_PLAIN) {
-      MIDAGMA_GEMM128(false, B_PLAIN, EPI_STORE);
-    } else if (!a_trans) {
-      MIDAGMA_GEMM128(false, B_IMINUS, EPI_STORE);
-    } else if (bmode == B_PLAIN) {
-      MIDAGMA_GEMM128(true, B_PLAIN, EPI_STORE);
-    } else {
-      MIDAGMA_GEMM128(true, B_IMINUS, EPI_STORE);
-    }
-#undef MIDAGMA_GEMM128
-    HIP_TRY(hipGetLastError());
-    return;
-  }
-  const int64_t ktiles = K / 64;
-  const int64_t per = (ktiles + split - 1) / split;
-  const int nsplit = (int)((ktiles + per - 1) / per);
-  dim3 grid((unsigned)(N / 64), (unsigned)(M / 64), (unsigned)nsplit);
-  const int64_t kslice = per * 64;
-#define MIDAGMA_GEMM(AT, BM, EP)                                                                         \
-  hipLaunchKernelGGL((gemm_kernel<AT, BM, EP>), grid, dim3(NTHREADS), kGemmLds, stream, K, kslice, A, lda, B, \
-                     ldb, C, ldc, slice_stride, loss_part, m_valid, n_valid, st)
-  if (epi == EPI_SIGMOID) {
-    if (a_trans || bmode != B_PLAIN || nsplit != 1) throw std::invalid_argument("launch_gemm: sigmoid form");
-    MIDAGMA_GEMM(false, B_PLAIN, EPI_SIGMOID);
-  } else if (!a_trans && bmode == B_PLAIN) {
-    MIDAGMA_GEMM(false, B_PLAIN, EPI_STORE);
-  } else if (!a_trans) {
-    MIDAGMA_GEMM(false, B_IMINUS, EPI_STORE);
-  } else if (bmode == B_PLAIN) {
-    MIDAGMA_GEMM(true, B_PLAIN, EPI_STORE);
-  } else {
-    MIDAGMA_GEMM(true, B_IMINUS, EPI_STORE);
-  }
-#undef MIDAGMA_GEMM
+  const int64_t K = (gs.K + 63) / 64 * 64;
+  const SplitK sk = split_k(K, 64, gs.split);
+  const dim3 grid((unsigned)(gs.N / 64), (unsigned)(gs.M / 64), (unsigned)sk.nsplit);
+  bool launched = false;
+  if (!sigmoid || sk.nsplit == 1)
+    gemm_dispatch(gs.a_trans, gs.bmode, gs.epi, [&](auto a, auto b, auto e) {
+      constexpr int A = decltype(a)::value, B = decltype(b)::value, E = decltype(e)::value;
+      if constexpr (gemm64_has(A, E)) {
+        hipLaunchKernelGGL((gemm_kernel<(A != 0), B, E>), grid, dim3(NTHREADS), kGemmLds, stream, K, sk.kslice, gs.A,
+                           gs.lda, gs.B, gs.ldb, gs.C, gs.ldc, gs.slice_stride, gs.loss_part, gs.m_valid, gs.n_valid,
+                           st);
+        launched = true;
+      }
+    });
+  if (!launched) throw std::invalid_argument(no_form);
   HIP_TRY(hipGetLastError());
+}
+
+void launch_gemm_summed(GemmSpec gs, double* slices, double* out, const State* st, hipStream_t stream) {
+  gs.C = gs.split > 1 ? slices : out;
+  launch_gemm(gs, st, stream);
+  if (gs.split > 1) launch_sum_slices(slices, gs.split, gs.slice_stride, gs.M * gs.ldc, out, st, stream);
 }
 
 // The EPI_SUB_MID / EPI_SUB_CROSS_MID tile bodies fold C0 over exactly 16 K-tiles of one K slice
@@ -1073,23 +825,22 @@ static void check_mid_shape(int64_t K, int64_t kslice, int64_t tiles, int64_t gr
 }
 
 bool gemm_trail_supported(const GemmSpec& gs) {
-  return gs.M % 128 == 0 && gs.N % 128 == 0 && gs.K % 16 == 0 && gs.split >= 1 &&
-         !knob_set("MIDAGMA_EXP_GEMM64") && !knob_set("MIDAGMA_EXP_NO_PIPE");
+  return gs.M % 128 == 0 && gs.N % 128 == 0 && gs.K % 16 == 0 && gs.split >= 1 && gs.a_trans &&
+         gs.epi == EPI_STORE && !knob_set("MIDAGMA_EXP_GEMM64");
 }
 
 // n_trail < 0: the trailing update of the 128-tile kind (launch_trail128's grid)
 void launch_gemm_trail(const GemmSpec& gs, const double* Ain, double* Aout, int64_t D, int B2, int g, bool check,
                        State* st, int pf, int n_trail, hipStream_t stream) {
+  if (!gs.a_trans) throw std::invalid_argument("launch_gemm_trail: op(A) must be stored [k][m] (a_trans)");
   if (!gemm_trail_supported(gs)) throw std::invalid_argument("launch_gemm_trail: shape");
-  const int64_t ktiles16 = gs.K / 16;
-  const int64_t per16 = (ktiles16 + gs.split - 1) / gs.split;
-  const int nsplit = (int)((ktiles16 + per16 - 1) / per16);
+  const SplitK sk = split_k(gs.K, 16, gs.split);
   GemmTrailArgs a{};
   a.K = gs.K;
-  a.kslice = per16 * 16;
+  a.kslice = sk.kslice;
   a.tm = (int)(gs.M / 128);
   a.tn = (int)(gs.N / 128);
-  a.n_gemm = a.tm * a.tn * nsplit;
+  a.n_gemm = a.tm * a.tn * sk.nsplit;
   a.A = gs.A;
   a.lda = gs.lda;
   a.B = gs.B;
@@ -1109,39 +860,27 @@ void launch_gemm_trail(const GemmSpec& gs, const double* Ain, double* Aout, int6
   a.bc_table = gs.ctl_table;
   a.ticket = gs.ctl_ticket;
   if (a.ticket && (!a.pr || !a.bc_table)) throw std::invalid_argument("launch_gemm_trail: folded control needs pr, table");
+  Gemm2Args a2{};
   if (n_trail < 0) {
     if (D % 128 || B2 % 128) throw std::invalid_argument("launch_gemm_trail: D, B2 must be multiples of 128");
-    Gemm2Args a2{a, (int)((D - B2) / 128), (B2 == 256 && trail_mid()) ? 1 : 0};
-    const dim3 grid2((unsigned)(a.n_gemm + a2.tm2 * a2.tm2));
-    if (a2.mid) check_mid_shape(B2, B2, (int64_t)a2.tm2 * a2.tm2, grid2.x - a.n_gemm, "launch_gemm_trail");
-#define MIDAGMA_GT2(AM, BM) \
-  hipLaunchKernelGGL((gemm_trail128_kernel<AM, BM>), grid2, dim3(NTHREADS), kGemmPipeLds, stream, a2)
-    if (gs.a_trans && gs.bmode == B_PLAIN)
-      MIDAGMA_GT2(1, B_PLAIN);
-    else if (gs.a_trans)
-      MIDAGMA_GT2(1, B_IMINUS);
-    else if (gs.bmode == B_PLAIN)
-      MIDAGMA_GT2(0, B_PLAIN);
-    else
-      MIDAGMA_GT2(0, B_IMINUS);
-#undef MIDAGMA_GT2
-    HIP_TRY(hipGetLastError());
-    return;
+    a2 = Gemm2Args{a, (int)((D - B2) / 128), (B2 == 256 && trail_mid()) ? 1 : 0};
+    if (a2.mid) check_mid_shape(B2, B2, (int64_t)a2.tm2 * a2.tm2, (int64_t)a2.tm2 * a2.tm2, "launch_gemm_trail");
   }
-  const dim3 grid((unsigned)(a.n_gemm + n_trail));
-#define MIDAGMA_GT(AM, BM) \
-  hipLaunchKernelGGL((gemm_trail_kernel<AM, BM>), grid, dim3(NTHREADS), kGemmTrailLds, stream, a)
-  if (gs.a_trans && gs.bmode == B_PLAIN)
-    MIDAGMA_GT(1, B_PLAIN);
-  else if (gs.a_trans)
-    MIDAGMA_GT(1, B_IMINUS);
-  else if (gs.bmode == B_PLAIN)
-    MIDAGMA_GT(0, B_PLAIN);
-  else
-    MIDAGMA_GT(0, B_IMINUS);
-#undef MIDAGMA_GT
+  const bool hit = gemm_dispatch(gs.a_trans, gs.bmode, gs.epi, [&](auto am, auto bm, auto e) {
+    constexpr int A = decltype(am)::value, B = decltype(bm)::value;
+    if constexpr (gemm_trail_has(A, decltype(e)::value)) {
+      if (n_trail < 0)
+        hipLaunchKernelGGL((gemm_trail128_kernel<A, B>), dim3((unsigned)(a.n_gemm + a2.tm2 * a2.tm2)), dim3(NTHREADS),
+                           kGemmPipeLds, stream, a2);
+      else
+        hipLaunchKernelGGL((gemm_trail_kernel<A, B>), dim3((unsigned)(a.n_gemm + n_trail)), dim3(NTHREADS),
+                           kGemmTrailLds, stream, a);
+    }
+  });
+  if (!hit) throw std::invalid_argument("launch_gemm_trail: no kernel of this form");
   HIP_TRY(hipGetLastError());
 }
+
 
 // B2 = 256 (16 K-tiles) folds C0 in during the K loop (EPI_SUB_MID; D = 5120: 219 -> 203 us, D =
 // 3072: 77.6 -> 68.9 us, tools/micro/trail_micro.hip), other B2 read it in the epilogue
@@ -1152,18 +891,14 @@ static void launch_trail128_epi(const double* Ain, double* Aout, int64_t D, int6
   if (tm <= 0) return;
   const int64_t G0 = g * B2;
   // A = Ain[:, G] (lda D), B = Aout[G, :] (the row panel), C = Aout, C0 = Ain; K = B2
-  static const bool no_pipe = knob_set("MIDAGMA_EXP_NO_PIPE");  // experiment knob
   const dim3 grid((unsigned)(tm * tm));
   const int64_t chk = check ? 1 : 0, b0 = G0 / 128, nb = B2 / 128;
-  if (!no_pipe && mid && B2 == 256) {
+  if (mid && B2 == 256) {
     check_mid_shape(B2, B2, (int64_t)tm * tm, grid.x, "launch_trail128");
     hipLaunchKernelGGL((gemm_pipe_kernel<0, B_PLAIN, EPI_SUB_MID>), grid, dim3(NTHREADS), kGemmPipeLds, stream, B2,
                        B2, tm, tm, Ain + G0, D, Aout + G0 * D, D, Aout, D, chk, const_cast<double*>(Ain), b0, nb, st);
-  } else if (!no_pipe)
+  } else
     hipLaunchKernelGGL((gemm_pipe_kernel<0, B_PLAIN, EPI_SUB_BAND>), grid, dim3(NTHREADS), kGemmPipeLds, stream, B2,
-                       B2, tm, tm, Ain + G0, D, Aout + G0 * D, D, Aout, D, chk, const_cast<double*>(Ain), b0, nb, st);
-  else
-    hipLaunchKernelGGL((gemm128_kernel<false, B_PLAIN, EPI_SUB_BAND>), grid, dim3(NTHREADS), kGemm128Lds, stream, B2,
                        B2, tm, tm, Ain + G0, D, Aout + G0 * D, D, Aout, D, chk, const_cast<double*>(Ain), b0, nb, st);
   HIP_TRY(hipGetLastError());
 }

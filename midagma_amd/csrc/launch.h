@@ -64,8 +64,25 @@ void launch_gj_inverse_1wg(const double* X, int64_t ldx, double* At, int64_t D, 
                            const State* st, hipStream_t stream, const LdfastEnd& end = LdfastEnd{});
 void launch_gj_step(double* A, int64_t lda, int64_t D, const GJWork& w, const State* st, int k, hipStream_t stream);
 
-// A GEMM launch's arguments (launch_gemm's meaning), for launches that carry one beside other work.
-enum GemmB : int;
+// One FP64 GEMM (gemm.hip): what launch_gemm runs, and what a launch that carries a GEMM beside
+// other work (launch_gemm_trail) is given.
+//   C[M x N] = op(A) op(B); op(A) = A ([m][k], lda) or, if a_trans, A stored [k][m] (lda);
+//   op(B) = B or, with B_IMINUS, I - B ([k][n], ldb).  M, N multiples of 64, K of 16 (the operands
+//   allocated and zero up to the next multiple of 64).  With split > 1 the K range is cut into at
+//   most `split` slices written to C + z slice_stride.
+//   EPI_SIGMOID (B_PLAIN; op(A) is X, K <= N): C = expit(acc); if loss_part != nullptr and
+//   st->ckpt_pending, per-workgroup partials of sum(logaddexp(0, acc) - X acc) over rows < m_valid,
+//   cols < n_valid go to loss_part[workgroup].  With split = 2 (128-tile grids with tiles % 8 == 0)
+//   the two K halves run in series (EPI_SIGMOID_SPLIT): C must hold the output, the first halves'
+//   partial at C + slice_stride (slice_stride >= M ldc) and one int flag per tile at
+//   C + 2 slice_stride, the flags zero before the first launch (each launch leaves them zero).
+enum GemmB : int { B_PLAIN = 0, B_IMINUS = 1 };
+enum GemmEpi : int { EPI_STORE = 0, EPI_SIGMOID = 1, EPI_SUB_BAND = 2 /* launch_trail128 only */,
+                     EPI_SUB_CROSS = 3 /* launch_trail128_split only */,
+                     EPI_SUB_PRE = 4 /* EPI_SUB_BAND with C0 preloaded into the accumulators */,
+                     EPI_SUB_MID = 5 /* EPI_SUB_BAND with C0 folded in during the 16 k-tiles (B2 = 256) */,
+                     EPI_SUB_CROSS_MID = 6 /* EPI_SUB_CROSS with the EPI_SUB_MID fold */,
+                     EPI_SIGMOID_SPLIT = 7 /* internal: launch_gemm's EPI_SIGMOID with split = 2 */ };
 struct GemmSpec {
   int64_t M, N, K;
   const double* A;
@@ -78,6 +95,9 @@ struct GemmSpec {
   int64_t ldc;
   int split;
   int64_t slice_stride;
+  int epi = EPI_STORE;  // EPI_STORE or EPI_SIGMOID
+  double* loss_part = nullptr;
+  int64_t m_valid = 0, n_valid = 0;
   // launch_gemm_trail only: the fast slot's control folded into the launch (control.h
   // control_fold_tail; null ticket: a control launch follows instead)
   const Params* ctl_pr = nullptr;
@@ -466,27 +486,14 @@ void launch_sem_slab(const SemDev& g, const std::vector<int32_t>& level_off, int
                      hipStream_t stream);
 
 // --- gemm.hip ---------------------------------------------------------------
-enum GemmB : int { B_PLAIN = 0, B_IMINUS = 1 };
-enum GemmEpi : int { EPI_STORE = 0, EPI_SIGMOID = 1, EPI_SUB_BAND = 2 /* launch_trail128 only */,
-                     EPI_SUB_CROSS = 3 /* launch_trail128_split only */,
-                     EPI_SUB_PRE = 4 /* EPI_SUB_BAND with C0 preloaded into the accumulators */,
-                     EPI_SUB_MID = 5 /* EPI_SUB_BAND with C0 folded in during the 16 k-tiles (B2 = 256) */,
-                     EPI_SUB_CROSS_MID = 6 /* EPI_SUB_CROSS with the EPI_SUB_MID fold */,
-                     EPI_SIGMOID_SPLIT = 7 /* internal: launch_gemm's EPI_SIGMOID with split = 2 */ };
 void gemm_setup_attributes();
-// C[M x N] = op(A) * op(B); op(A) = A ([m][k], lda) or, if a_trans, A stored [k][m] (lda);
-// op(B) = B or (I - B) ([k][n], ldb).  M, N, K multiples of 64.  With split > 1
-// the K range is cut into `split` slices written to C + z*slice_stride.
-// EPI_SIGMOID: C = expit(acc); if loss_part != nullptr and st->ckpt_pending,
-// per-workgroup partials of sum(logaddexp(0,acc) - X*acc) over rows < m_valid,
-// cols < n_valid go to loss_part[blockIdx.y * gridDim.x + blockIdx.x] (X = A).
-// EPI_SIGMOID with split = 2 (128-tile grids with tiles % 8 == 0): the two K halves run in
-// series (EPI_SIGMOID_SPLIT); C must hold the output, the first halves' partial at
-// C + slice_stride (slice_stride >= M ldc) and one int flag per tile at C + 2 slice_stride, the
-// flags zero before the first launch (each launch leaves them zero).
-void launch_gemm(int64_t M, int64_t N, int64_t K, const double* A, int64_t lda, bool a_trans, const double* B,
-                 int64_t ldb, GemmB bmode, double* C, int64_t ldc, GemmEpi epi, int split, int64_t slice_stride,
-                 double* loss_part, int64_t m_valid, int64_t n_valid, const State* st, hipStream_t stream);
+// The GEMM gs (GemmSpec above; its ctl_* fields unused), gated on st (nullable).  Two tiers: the
+// pipelined 128 x 128 tile kernel when M and N are multiples of 128, the 64 x 64 tile kernel
+// otherwise (which has no sigmoid form for a_trans and no serial split).
+void launch_gemm(const GemmSpec& gs, const State* st, hipStream_t stream);
+// The same with the split-K slices summed: split == 1 writes `out` itself, otherwise the slices go
+// to `slices` (gs.slice_stride apart) and launch_sum_slices adds them into `out` (gs.C unused).
+void launch_gemm_summed(GemmSpec gs, double* slices, double* out, const State* st, hipStream_t stream);
 // Trailing update of the blocked inverse's outer step g on 128 x 128 tiles:
 // Aout[i, j] = Ain[i, j] - Ain[i, G] Aout[G, j] for i, j outside G = [g B2, (g+1) B2);
 // with `check`, ORs the domain flags of the outputs into st->flags.
@@ -509,9 +516,7 @@ void launch_trail128_persist(const double* Ain, double* Aout, int64_t D, int64_t
 // claim tiles from *ctr (zeroed by a memset node before the launch, on `stream`), so the other
 // launches of the slot keep the remaining CUs to themselves (the cov score GEMM forked beside the
 // inverse, MIDAGMA_EXP_COV_FORK=2 with MIDAGMA_EXP_GEMM_SES)
-void launch_gemm_cupart(int64_t M, int64_t N, int64_t K, const double* A, int64_t lda, bool a_trans, const double* B,
-                        int64_t ldb, GemmB bmode, double* C, int64_t ldc, int split, int64_t slice_stride,
-                        const State* st, int ses, int* ctr, hipStream_t stream);
+void launch_gemm_cupart(const GemmSpec& gs, const State* st, int ses, int* ctr, hipStream_t stream);
 // The B2 = 256 update as data-parallel tiles plus a stream-K remainder: the first `dp` tiles (of
 // xcd_remap's order) one per workgroup (EPI_SUB_MID), the other ntiles - dp tiles' 16 K-tiles each
 // split evenly over `nsk` workgroups; a partial tile goes to ws (2 nsk 128 x 128 slots), the

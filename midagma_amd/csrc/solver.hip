@@ -268,15 +268,9 @@ int midagma_set_data(midagma_solver* s, const double* X, int64_t n_local, int64_
 int midagma_data_gram(midagma_solver* s) {
   if (!s || !s->has_data) return fail(s, MIDAGMA_E_STATE, "data_gram: set_data first");
   return guarded(s, [&] {
-    const int64_t D = s->D;
-    if (s->split == 1)
-      launch_gemm(D, D, s->n_pad, s->X.p, D, true, s->X.p, D, B_PLAIN, s->zbuf, D, EPI_STORE, 1, 0, nullptr, 0, 0,
-                  nullptr, s->stream);
-    else {
-      launch_gemm(D, D, s->n_pad, s->X.p, D, true, s->X.p, D, B_PLAIN, s->Zparts.p, D, EPI_STORE, s->split, D * D,
-                  nullptr, 0, 0, nullptr, s->stream);
-      launch_sum_slices(s->Zparts.p, s->split, D * D, D * D, s->zbuf, nullptr, s->stream);
-    }
+    GemmSpec gs = s->xty_spec();  // X^T X: the X^T Y GEMM with Y = X
+    gs.B = s->X.p;
+    launch_gemm_summed(gs, s->Zparts.p, s->zbuf, nullptr, s->stream);
     HIP_TRY(hipStreamSynchronize(s->stream));
     return MIDAGMA_OK;
   });
@@ -362,8 +356,8 @@ int midagma_gram(const double* X, int64_t n, int64_t d, int64_t ldx, int on_devi
                                  rows, hipMemcpyHostToDevice, st));
         launch_nonfinite_or(S.p, rows, d, D, flag, st);
       }
-      launch_gemm(D, D, rpad, S.p, D, true, S.p, D, B_PLAIN, Z.p + DD, D, EPI_STORE, p.split, DD, nullptr, 0, 0,
-                  nullptr, st);
+      // (the running sum is slice 0 of the sum, so the slices are summed at every split)
+      launch_gemm(GemmSpec{D, D, rpad, S.p, D, true, S.p, D, B_PLAIN, Z.p + DD, D, p.split, DD}, nullptr, st);
       launch_sum_slices(Z.p, p.split + 1, DD, DD, Z.p + (p.split + 1) * DD, nullptr, st);
       HIP_TRY(hipMemcpyAsync(Z.p, Z.p + (p.split + 1) * DD, DD * sizeof(double), hipMemcpyDeviceToDevice, st));
     }
@@ -509,25 +503,8 @@ int midagma_profile_parts(midagma_solver* s, int reps, double* ms_out) {
       ms_out[4] = ms_out[5] = 0.0;
     } else {
       ms_out[2] = timed([&] { s->enqueue_data_partial(s->W.p, s->d_state, s->IW.p); });
-      ms_out[4] = timed([&] {
-        if (s->loss == MIDAGMA_LOSS_L2)
-          launch_gemm(s->n_pad, D, s->Kd(), s->xw_a(), s->xw_lda(), s->use_xt, s->IW.p ? s->IW.p : s->W.p, D,
-                      s->IW.p ? B_PLAIN : B_IMINUS, s->Y.p, D, EPI_STORE, 1, 0, nullptr, 0, 0, s->d_state, s->stream);
-        else
-          launch_gemm(s->n_pad, D, s->Kd(), s->xw_a(), s->xw_lda(), s->use_xt, s->W.p, D, B_PLAIN, s->Y.p, D, EPI_SIGMOID,
-                      s->sig_split, s->sig_split > 1 ? s->n_pad * D : 0, s->loss_part.p, s->n_local, s->d,
-                      s->d_state, s->stream);
-      });
-      ms_out[5] = timed([&] {
-        if (s->split == 1)
-          launch_gemm(D, D, s->n_pad, s->X.p, D, true, s->Y.p, D, B_PLAIN, s->zbuf, D, EPI_STORE, 1, 0, nullptr, 0, 0,
-                      s->d_state, s->stream);
-        else {
-          launch_gemm(D, D, s->n_pad, s->X.p, D, true, s->Y.p, D, B_PLAIN, s->Zparts.p, D, EPI_STORE, s->split,
-                      D * D, nullptr, 0, 0, s->d_state, s->stream);
-          launch_sum_slices(s->Zparts.p, s->split, D * D, D * D, s->zbuf, s->d_state, s->stream);
-        }
-      });
+      ms_out[4] = timed([&] { s->enqueue_xw(s->W.p, s->d_state, s->IW.p); });
+      ms_out[5] = timed([&] { s->enqueue_xty(s->d_state); });
     }
     ms_out[3] = timed([&] { HIP_TRY(hipGraphLaunch(s->g_full, s->stream)); });
     ms_out[6] = ms_out[7] = 0.0;
@@ -834,7 +811,8 @@ int midagma_score(midagma_solver* s, const double* W, double* loss, double* G) {
     s->upload_matrix(s->scratch, W, d);
     DevBuf rhs;
     rhs.alloc(DD);
-    s->enqueue_cov_gemm(s->cov.p, s->scratch.p, rhs.p, nullptr);  // rhs = cov @ (I - W)   (linear.py:85-86)
+    // rhs = cov @ (I - W)   (linear.py:85-86)
+    s->enqueue_cov_gemm(s->cov_spec(s->cov.p, false, s->scratch.p, B_IMINUS), rhs.p, nullptr);
     double sd = 0;
     host_trace_l1(s, s->scratch.p, rhs.p, &sd, nullptr);
     *loss = 0.5 * sd;

@@ -79,8 +79,6 @@ struct midagma_solver {
   DevBuf W, m, v, Mt, cov, covs, minc, mexc, P, R, C, pivlog, partials, bc_table, zown, scratch, Gtmp, Pstore;
   // ((-mu) cov)^T: the cov-mode score GEMM reads its A operand k-major (coalesced tile rows)
   DevBuf covsT;
-  bool cov_at = !knob_set("MIDAGMA_EXP_COV_AMODE0");
-  bool cov_iw = knob_set("MIDAGMA_EXP_COV_IW");
   DevBuf npart;  // checkpoint-step norm partials (fused_update -> control)
   DevBuf l1w;    // float32 W: [0] numpy's float32 L1 sum, then its chunk sums (np_l1_kernel)
   // cov mode, l2, d <= 64, no trek regularizer: the one-workgroup persistent loop (small.hip)
@@ -472,22 +470,18 @@ struct midagma_solver {
   bool tcc_fastblk = knob("MIDAGMA_EXP_TCC_FASTBLK", 1) != 0;
   DevBuf ctl_ticket;
 
-  // the cov score GEMM as enqueue_cov_gemm launches it on a fast slot (split-K slices, unsummed)
+  // The product's GEMMs, each described once (launch.h GemmSpec).
+  // out = op(Cm) @ (I - W) on the d x d problem, split-K over cov_split fixed slices (in
+  // cov_parts) when the tile grid alone cannot fill the chip; a_trans: Cm holds the transpose of
+  // the left operand; B_PLAIN: Wp already holds I - W
+  GemmSpec cov_spec(const double* Cm, bool a_trans, const double* Wp, GemmB bmode) const {
+    return GemmSpec{D, D, Kd(), Cm, D, a_trans, Wp, D, bmode, cov_parts.p, D, cov_split, D * D};
+  }
+  // the slot's cov score GEMM rhs = ((-mu) cov) @ (I - W): A read k-major from ((-mu) cov)^T
+  // (coalesced tile rows), B = I - W formed by build_at (IW, plain B) when the slot keeps it; with
+  // the fast slot's folded control for launch_gemm_trail
   GemmSpec score_cov_spec() const {
-    GemmSpec gs{};
-    gs.M = D;
-    gs.N = D;
-    gs.K = Kd();
-    gs.A = cov_at ? covsT.p : covs.p;
-    gs.lda = D;
-    gs.a_trans = cov_at;
-    gs.B = IW.p ? IW.p : W.p;
-    gs.ldb = D;
-    gs.bmode = IW.p ? B_PLAIN : B_IMINUS;
-    gs.C = cov_parts.p;
-    gs.ldc = D;
-    gs.split = cov_split;
-    gs.slice_stride = D * D;
+    GemmSpec gs = cov_spec(covsT.p, true, IW.p ? IW.p : W.p, IW.p ? B_PLAIN : B_IMINUS);
     if (ctl_fold && ctl_ticket.p) {
       gs.ctl_pr = d_params;
       gs.ctl_table = bc_table.p;
@@ -495,67 +489,64 @@ struct midagma_solver {
     }
     return gs;
   }
-
-  // rhs = ((-mu) cov) @ (I - W) from the slot's operands: A read k-major from ((-mu) cov)^T
-  // (cov_at), B = I - W formed by build_at (IW, plain B) when the slot keeps it
-  void enqueue_score_cov(double* out, const State* st, bool sum) {
-    const double* A = cov_at ? covsT.p : covs.p;
-    if (IW.p)
-      enqueue_cov_gemm(A, IW.p, out, st, sum, cov_at, B_PLAIN);
-    else
-      enqueue_cov_gemm(A, W.p, out, st, sum, cov_at, B_IMINUS);
+  // data mode, l2: Y = X_k (I - W); iw (nullable): I - W already formed (build_at), the plain-B form
+  GemmSpec xw_spec(const double* Wp, const double* iw) const {
+    // (experiments build, MIDAGMA_EXP_XW_FULLK=1: the k loop over all of D, as round 4 ran it)
+    static const int64_t kfull = knob("MIDAGMA_EXP_XW_FULLK", 0);
+    return GemmSpec{n_pad, D, kfull ? D : Kd(), xw_a(), xw_lda(), use_xt, iw ? iw : Wp, D, iw ? B_PLAIN : B_IMINUS,
+                    Y.p, D, 1, 0};
+  }
+  // data mode, logistic: Y = expit(X_k W) with the loss partials (sig_split = 2: the serial split)
+  GemmSpec sigmoid_spec(const double* Wp) const {
+    GemmSpec gs{n_pad, D, Kd(), xw_a(), xw_lda(), use_xt, Wp, D, B_PLAIN, Y.p, D, sig_split,
+                sig_split > 1 ? n_pad * D : 0};
+    gs.epi = EPI_SIGMOID;
+    gs.loss_part = loss_part.p;
+    gs.m_valid = n_local;
+    gs.n_valid = d;
+    return gs;
+  }
+  // data mode: Z_k = X_k^T Y in `split` K slices (launch_gemm_summed: Zparts -> zbuf)
+  GemmSpec xty_spec() const {
+    return GemmSpec{D, D, n_pad, X.p, D, true, Y.p, D, B_PLAIN, Zparts.p, D, split, D * D};
   }
 
-  // out = Cm @ (I - Wp) on the d x d problem; split-K over fixed slices when the tile grid
-  // alone cannot fill the chip (summed in fixed order: deterministic)
-  // a_trans: Cm holds the transpose of the left operand
-  // (bmode B_PLAIN: Wp already holds I - W)
-  void enqueue_cov_gemm(const double* Cm, const double* Wp, double* out, const State* st, bool sum = true,
-                        bool a_trans = false, GemmB bmode = B_IMINUS) {
+  // the slot's cov score GEMM into out; sum = false leaves split-K slices in cov_parts
+  void enqueue_score_cov(double* out, const State* st, bool sum) { enqueue_cov_gemm(score_cov_spec(), out, st, sum); }
+
+  // the cov GEMM gs (cov_spec) into out, its slices summed in fixed order (deterministic) unless
+  // sum = false
+  void enqueue_cov_gemm(GemmSpec gs, double* out, const State* st, bool sum = true) {
 #ifdef MIDAGMA_EXPERIMENTS
     // experiment: the forked score GEMM confined to the first MIDAGMA_EXP_GEMM_SES shader engines of
     // every XCD, so the inverse's launches on the side stream keep the other CUs to themselves
     static const int gemm_ses = (int)knob("MIDAGMA_EXP_GEMM_SES", 0);
     if (gemm_ses > 0 && cov_fork_on() && D % 128 == 0) {
       if (!cupart_ctr.p) throw std::logic_error("cupart counter not allocated");
-      double* dst = cov_split > 1 ? cov_parts.p : out;
-      launch_gemm_cupart(D, D, Kd(), Cm, D, a_trans, Wp, D, bmode, dst, D, cov_split, D * D, st, gemm_ses,
-                         reinterpret_cast<int*>(cupart_ctr.p), stream);
+      if (cov_split == 1) gs.C = out;
+      launch_gemm_cupart(gs, st, gemm_ses, reinterpret_cast<int*>(cupart_ctr.p), stream);
       if (cov_split > 1 && sum) launch_sum_slices(cov_parts.p, cov_split, D * D, D * D, out, st, stream);
       return;
     }
 #endif
-    if (cov_split > 1) {
-      launch_gemm(D, D, Kd(), Cm, D, a_trans, Wp, D, bmode, cov_parts.p, D, EPI_STORE, cov_split, D * D, nullptr, 0,
-                  0, st, stream);
-      if (sum) launch_sum_slices(cov_parts.p, cov_split, D * D, D * D, out, st, stream);
-    } else {
-      launch_gemm(D, D, Kd(), Cm, D, a_trans, Wp, D, bmode, out, D, EPI_STORE, 1, 0, nullptr, 0, 0, st, stream);
-    }
+    if (cov_split > 1 && !sum)
+      launch_gemm(gs, st, stream);  // (the fast slot: fused_update sums the slices)
+    else
+      launch_gemm_summed(gs, cov_parts.p, out, st, stream);
   }
 
   // Z_k = X_k^T (X_k (I - W))  (l2)   or   X_k^T expit(X_k W)  (logistic, + loss partial)
   // iw (nullable): I - W already formed (build_at), the plain-B form of the GEMM
   void enqueue_data_partial(const double* Wp, const State* st, const double* iw = nullptr) {
-    if (loss == MIDAGMA_LOSS_L2) {
-      // (experiments build, MIDAGMA_EXP_XW_FULLK=1: the k loop over all of D, as round 4 ran it)
-      static const int64_t kfull = knob("MIDAGMA_EXP_XW_FULLK", 0);
-      launch_gemm(n_pad, D, kfull ? D : Kd(), xw_a(), xw_lda(), use_xt, iw ? iw : Wp, D, iw ? B_PLAIN : B_IMINUS, Y.p, D,
-                  EPI_STORE, 1,
-                  0, nullptr, 0, 0, st, stream);
-    } else {
-      launch_gemm(n_pad, D, Kd(), xw_a(), xw_lda(), use_xt, Wp, D, B_PLAIN, Y.p, D, EPI_SIGMOID, sig_split,
-                  sig_split > 1 ? n_pad * D : 0, loss_part.p, n_local, d, st, stream);
-      launch_sum_vector(loss_part.p, loss_part_count, zbuf + D * D, st, stream);
-    }
-    if (split == 1) {
-      launch_gemm(D, D, n_pad, X.p, D, true, Y.p, D, B_PLAIN, zbuf, D, EPI_STORE, 1, 0, nullptr, 0, 0, st, stream);
-    } else {
-      launch_gemm(D, D, n_pad, X.p, D, true, Y.p, D, B_PLAIN, Zparts.p, D, EPI_STORE, split, D * D, nullptr, 0, 0,
-                  st, stream);
-      launch_sum_slices(Zparts.p, split, D * D, D * D, zbuf, st, stream);
-    }
+    enqueue_xw(Wp, st, iw);
+    if (loss != MIDAGMA_LOSS_L2) launch_sum_vector(loss_part.p, loss_part_count, zbuf + D * D, st, stream);
+    enqueue_xty(st);
   }
+  // its two GEMMs (midagma_profile_parts times each alone)
+  void enqueue_xw(const double* Wp, const State* st, const double* iw) {
+    launch_gemm(loss == MIDAGMA_LOSS_L2 ? xw_spec(Wp, iw) : sigmoid_spec(Wp), st, stream);
+  }
+  void enqueue_xty(const State* st) { launch_gemm_summed(xty_spec(), Zparts.p, zbuf, st, stream); }
 
   // fast (blocked cov slots): the domain flags come from the inverse's last outer step and the
   // score slices are summed inside fused_update; fast slots never carry a checkpoint
@@ -852,8 +843,8 @@ struct midagma_solver {
       ctl_ticket.alloc(1);
       HIP_TRY(hipMemsetAsync(ctl_ticket.p, 0, sizeof(double), stream));
     }
-    // cov mode: build_at also writes I - W for the score GEMM's plain-B form
-    if (mode == MIDAGMA_MODE_COV && ((D % 128 == 0 && cov_iw) || w32)) IW.alloc(DD);
+    // cov mode, float32 W: build_at also writes I - W for the score GEMM's plain-B form
+    if (mode == MIDAGMA_MODE_COV && w32) IW.alloc(DD);
     // the next slot's A^T written by fused_update_at (at_fold_on)
     if (at_fold_knob < 0) at_fold = D >= 1024 && D <= 1408;
     if (at_fold && mode == MIDAGMA_MODE_COV && B2 > 0) A0.alloc(DD);

@@ -307,14 +307,9 @@ static void log_horner_forward(int K, const TrekWork& w, int64_t D, int gdd, con
 static void gemm_dd(int64_t D, const double* A, bool a_trans, const double* B, double* C, const TrekWork& w,
                     const State* gate, hipStream_t stream) {
   const int tiles = (int)((D / 128) * (D / 128));
-  if (D % 128 == 0 && tiles < 256 && w.slices) {
-    const int split = (int)std::min<int64_t>(4, D / 128);
-    launch_gemm(D, D, D, A, D, a_trans, B, D, B_PLAIN, w.slices, D, EPI_STORE, split, D * D, nullptr, 0, 0, gate,
-                stream);
-    launch_sum_slices(w.slices, split, D * D, D * D, C, gate, stream);
-  } else {
-    launch_gemm(D, D, D, A, D, a_trans, B, D, B_PLAIN, C, D, EPI_STORE, 1, 0, nullptr, 0, 0, gate, stream);
-  }
+  const int split = D % 128 == 0 && tiles < 256 && w.slices ? (int)std::min<int64_t>(4, D / 128) : 1;
+  launch_gemm_summed(GemmSpec{D, D, D, A, D, a_trans, B, D, B_PLAIN, nullptr, D, split, D * D}, w.slices, C, gate,
+                     stream);
 }
 
 int trek_taylor_degree() { return TREK_TAYLOR_M; }

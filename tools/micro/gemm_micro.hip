@@ -114,14 +114,13 @@ int main(int argc, char** argv) {
     fflush(stdout);
   };
   if (want("xw")) {
-    report("xw  lib gemm128<T,IMINUS>", time_ms([&] {
-             launch_gemm(n, D, D, XT, n, true, W, D, B_IMINUS, Y, D, EPI_STORE, 1, 0, nullptr, 0, 0, nullptr, 0);
+    report("xw  lib gemm_pipe<1,IMINUS>", time_ms([&] {
+             launch_gemm(GemmSpec{n, D, D, XT, n, true, W, D, B_IMINUS, Y, D, 1, 0}, nullptr, 0);
            }, reps));
   }
   if (want("xty")) {
-    report("xty lib gemm128<T,PLAIN>/16", time_ms([&] {
-             launch_gemm(D, D, n, X, D, true, Y, D, B_PLAIN, Z, D, EPI_STORE, split, D * D, nullptr, 0, 0, nullptr,
-                         0);
+    report("xty lib gemm_pipe<1,PLAIN>/16", time_ms([&] {
+             launch_gemm(GemmSpec{D, D, n, X, D, true, Y, D, B_PLAIN, Z, D, split, D * D}, nullptr, 0);
            }, reps));
   }
   double* Yref = nullptr;
@@ -135,7 +134,7 @@ int main(int argc, char** argv) {
     CK(hipFuncSetAttribute(reinterpret_cast<const void*>(exp::xw2_kernel<0>),
                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)exp::kXw2Lds));
     CK(hipMalloc(&Yref, sizeof(double) * D * n));
-    launch_gemm(n, D, D, XT, n, true, W, D, B_IMINUS, Yref, D, EPI_STORE, 1, 0, nullptr, 0, 0, nullptr, 0);
+    launch_gemm(GemmSpec{n, D, D, XT, n, true, W, D, B_IMINUS, Yref, D, 1, 0}, nullptr, 0);
     CK(hipDeviceSynchronize());
   }
   if (want("xw2")) {
@@ -196,8 +195,7 @@ int main(int argc, char** argv) {
     double* Zs;
     CK(hipMalloc(&Z3, sizeof(double) * D * D * split));
     CK(hipMalloc(&Zs, sizeof(double) * D * D));
-    launch_gemm(D, D, n, X, D, true, Yref, D, B_PLAIN, Z, D, EPI_STORE, split, D * D, nullptr, 0, 0, nullptr, 0);
-    launch_sum_slices(Z, split, D * D, D * D, Z2, nullptr, 0);
+    launch_gemm_summed(GemmSpec{D, D, n, X, D, true, Yref, D, B_PLAIN, nullptr, D, split, D * D}, Z, Z2, nullptr, 0);
     const int64_t per16 = (n / 16 + split - 1) / split;
     const int nsplit = (int)((n / 16 + per16 - 1) / per16);
     report("xty exp xw3<PLAIN>/16", time_ms([&] {
@@ -209,8 +207,7 @@ int main(int argc, char** argv) {
     printf("    max|Z - Zref| = %.3e (rel to max|Zref| %.3e)\n", maxdiff(Zs, Z2, D * D), 0.0);
   }
   if (want("xty2")) {
-    launch_gemm(D, D, n, X, D, true, Yref, D, B_PLAIN, Z, D, EPI_STORE, split, D * D, nullptr, 0, 0, nullptr, 0);
-    launch_sum_slices(Z, split, D * D, D * D, Z2, nullptr, 0);
+    launch_gemm_summed(GemmSpec{D, D, n, X, D, true, Yref, D, B_PLAIN, nullptr, D, split, D * D}, Z, Z2, nullptr, 0);
     CK(hipDeviceSynchronize());
     double* Z3;
     double* Zs;

@@ -61,11 +61,11 @@ int main() {
   const int reps = 200;
   const double f = 2.0 * D * D * K;
   for (int split : {1, 2, 4, 8}) {
-    const double us = time_us([&] { launch_gemm(D, D, K, A, D, true, B, D, B_PLAIN, C, D, EPI_STORE, split, D * D,
-                                                nullptr, 0, 0, nullptr, 0); }, reps);
+    const GemmSpec gs{D, D, K, A, D, true, B, D, B_PLAIN, C, D, split, D * D};
+    const double us = time_us([&] { launch_gemm(gs, nullptr, 0); }, reps);
     const double cold = time_us([&] {
       hipLaunchKernelGGL(fill_kernel, dim3(1024), dim3(256), 0, 0, B, D * D, 3, 1.0);
-      launch_gemm(D, D, K, A, D, true, B, D, B_PLAIN, C, D, EPI_STORE, split, D * D, nullptr, 0, 0, nullptr, 0);
+      launch_gemm(gs, nullptr, 0);
     }, reps);
     const double fill = time_us([&] { hipLaunchKernelGGL(fill_kernel, dim3(1024), dim3(256), 0, 0, B, D * D, 3, 1.0); },
                                 reps);

@@ -104,7 +104,7 @@ int main(int argc, char** argv) {
     const double rd = reldiff(Aout2, Aout, D * D);
     const double rd_mid = reldiff(Aout3, Aout, D * D);
     const double us_st = time_us([&] {
-      launch_gemm(t, t, B2, Ain, D, false, Aout, D, B_PLAIN, C, D, EPI_STORE, 1, 0, nullptr, 0, 0, nullptr, 0);
+      launch_gemm(GemmSpec{t, t, B2, Ain, D, false, Aout, D, B_PLAIN, C, D, 1, 0}, nullptr, 0);
     }, reps);
     // in place (Aout = Ain: the whole matrix is one 8 D^2-byte buffer, which fits the 256 MB
     // Infinity Cache up to D ~ 5600; timing only: the column band is read while other tiles write)
