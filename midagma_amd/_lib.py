@@ -149,6 +149,11 @@ EXPORTED = {
 
 GROUP_EMULATE = 1
 
+# test hooks the library exports beside the ABI (not declared in the header, so not in EXPORTED)
+DEBUG_HOOKS = {
+    "midagma_debug_slot_matrices": (_int, [_vp, _dp, _dp]),
+}
+
 _lock = threading.Lock()
 _lib = None
 
@@ -170,7 +175,7 @@ def load(path: str | None = None) -> C.CDLL:
         except Exception:
             pass
         handle = C.CDLL(p, mode=C.RTLD_GLOBAL)
-        for name, (res, args) in EXPORTED.items():
+        for name, (res, args) in list(EXPORTED.items()) + list(DEBUG_HOOKS.items()):
             fn = getattr(handle, name)
             fn.restype = res
             fn.argtypes = args

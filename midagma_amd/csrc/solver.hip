@@ -656,6 +656,28 @@ extern "C" int midagma_debug_at_fold(midagma_solver* s, int on) {
   });
 }
 
+// Test hook (not in the public header), read-only: the d x d corners of the device W and Mt as
+// dense d x d host matrices (either pointer may be null), after the solver's stream and side
+// stream have drained.  After a slot Mt holds inv(sI - W∘W)^T of the W that slot started from
+// (every inverse path ends in Mt: launch_blocked_inverse's ping-pong starts in
+// binv_build_target, so its K2 flips land there, also when outer step 0 read A0; the updates
+// only read it) and W the slot's updated W, the next slot's input.  Enqueues no kernel and
+// changes no state.  -1: no handle, no slot run since the last begin (Mt would be stale), or
+// the one-workgroup loop (small.hip), which keeps its inverse in LDS.
+extern "C" int midagma_debug_slot_matrices(midagma_solver* s, double* W_out, double* Mt_out) {
+  if (!s || s->bc_len == 0 || s->small_on()) return -1;  // (bc_len: set by the first begin)
+  if (hipSetDevice(s->device) != hipSuccess) return -1;
+  if (hipStreamSynchronize(s->stream) != hipSuccess) return -1;
+  if (s->side && hipStreamSynchronize(s->side) != hipSuccess) return -1;
+  State st{};
+  if (hipMemcpy(&st, s->d_state, sizeof(State), hipMemcpyDeviceToHost) != hipSuccess) return -1;
+  if (st.slots < 1) return -1;
+  const size_t row = (size_t)s->d * sizeof(double), pitch = (size_t)s->D * sizeof(double);
+  if (W_out && hipMemcpy2D(W_out, row, s->W.p, pitch, row, s->d, hipMemcpyDeviceToHost) != hipSuccess) return -1;
+  if (Mt_out && hipMemcpy2D(Mt_out, row, s->Mt.p, pitch, row, s->d, hipMemcpyDeviceToHost) != hipSuccess) return -1;
+  return 0;
+}
+
 // Diagnostics of the fast blocked inverse (not in the public header): per outer block g,
 // out[g*(NM_PASSES+2) + 0] = done word, out[... + 1 + p] = ||Q_p||_inf of pass p (stale for
 // passes that did not run in the last slot).

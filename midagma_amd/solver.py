@@ -271,6 +271,15 @@ class HipSolver:
         fn.restype, fn.argtypes = C.c_int64, [C.c_void_p]
         return int(fn(self.h))
 
+    def debug_slot_matrices(self):
+        """Test hook (read-only): (W, Mt) as the last slot left them on the device, d x d each.  Mt is
+        inv(sI - W∘W)^T for the W that slot started from, W the slot's updated W (the next slot's
+        input).  Waits for the solver's streams; raises when no slot has run since begin."""
+        W, Mt = np.empty((self.d, self.d)), np.empty((self.d, self.d))
+        if self.L.midagma_debug_slot_matrices(self.h, dptr(W), dptr(Mt)) != 0:
+            raise _lib.HipSolverError("debug_slot_matrices: no slot has run since begin (or no Mt buffer)")
+        return W, Mt
+
     # fit()'s device data preparation (linear.py:406-428; the CPU test doubles override these)
     def colsum(self, X):
         return colsum_dev(X)

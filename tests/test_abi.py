@@ -64,6 +64,17 @@ def test_product_library_reads_no_experiment_knobs():
         assert b"MIDAGMA_EXP_DF" in eb and b"midagma_debug_df_plan" in eb
 
 
+def test_debug_hooks_are_bound_but_not_part_of_the_abi():
+    """The test hooks _lib binds beside the ABI are exported by the library, stay out of the header
+    (so the ABI version does not move), and refuse a null handle before touching a device."""
+    from midagma_amd import _lib
+    L = _lib.load()
+    assert not set(_lib.DEBUG_HOOKS) & set(_declared())
+    for name in _lib.DEBUG_HOOKS:
+        assert hasattr(L, name), name
+    assert L.midagma_debug_slot_matrices(None, None, None) == -1
+
+
 def test_ldfast_entry_points_validate_without_a_device():
     """The ABI-6 warm-started log-det entries refuse bad arguments before touching a device."""
     import ctypes as C
