@@ -370,7 +370,23 @@ int midagma_mlp_tail_bwd(const double* Z, const double* b1, const double* w2, co
  * entry checks its arguments before it touches a device (MIDAGMA_E_ARG); the message comes from
  * midagma_indep_last_error(handle) (or (NULL) for errors raised without a handle).
  * set_data: host X (n x d row-major), 2 <= n <= 16384, d <= 65535, copied; MIDAGMA_E_ARG on inf/nan.
+ * set_data_dev: the same from device memory: X_dev is n x d row-major on the handle's device with
+ *   row stride ld >= d (checked: memory of that device), and is never written.  Its producer's work
+ *   is ordered on hip_stream (NULL: the null stream).  Ordering: the transpose kernel (which also
+ *   leaves two flags per column: holds a non-finite value, every value equals row 0's) runs on
+ *   hip_stream, behind the producer, and the entry then synchronises hip_stream to read the 2 d
+ *   flag bytes, so the handle's copy is complete before any later entry uses it; the caller
+ *   synchronises nothing.  MIDAGMA_E_ARG on inf/nan, and the handle then holds no data (every
+ *   later entry answers "set the data first" until a set_data* succeeds).
  * set_bandwidths: the RBF kernel's sigma^2 per variable (d values, finite and > 0), for hsic.
+ * median_bandwidths: sigma^2 by the reference's median heuristic (mi_tests.py:39-44: the median of
+ *   the off-diagonal squared differences of the column, 1.0 when that is not > 0), computed on the
+ *   device for the ncols listed columns (cols NULL: all d; duplicates allowed) and 1.0 for the
+ *   others, installed as set_bandwidths would and written to sigma2_out (d doubles, nullable).  The
+ *   value is numpy's np.median of the squared differences bit for bit and does not depend on which
+ *   columns are listed together.  Data from either set_data entry.
+ * bandwidth_profile (diagnostics): the last median_bandwidths' kernel time in ms (device events;
+ *   0 when no column was listed).  ms_out holds 1 double.
  * run: for each of the m pairs (i, j) (int64 m x 2; i == j and both orders allowed) the observed
  *   statistic stat[q] of (X[:, i], X[:, j]) and ge[q] = #{p < P : stat(X[:, i], X[:, j][perm_qp]) >=
  *   stat[q]}; null_out (nullable, m x P): every permuted statistic.  kind: 0 hsic, 1 dcor (dcor
@@ -395,7 +411,11 @@ int midagma_indep_create(midagma_indep** out, int device);
 void midagma_indep_destroy(midagma_indep* h);
 const char* midagma_indep_last_error(const midagma_indep* h);
 int midagma_indep_set_data(midagma_indep* h, const double* X, int64_t n, int64_t d);
+int midagma_indep_set_data_dev(midagma_indep* h, const double* X_dev, int64_t n, int64_t d, int64_t ld,
+                               void* hip_stream);
 int midagma_indep_set_bandwidths(midagma_indep* h, const double* sigma2, int64_t d);
+int midagma_indep_median_bandwidths(midagma_indep* h, const int64_t* cols, int64_t ncols, double* sigma2_out);
+int midagma_indep_bandwidth_profile(const midagma_indep* h, double* ms_out);
 int64_t midagma_indep_batch_pairs(const midagma_indep* h, int64_t P, int64_t budget_bytes);
 int midagma_indep_profile(const midagma_indep* h, double* ms_out);
 int midagma_indep_run(midagma_indep* h, int kind, const int64_t* pairs, int64_t m, int64_t P, const int32_t* perms,

@@ -141,7 +141,10 @@ EXPORTED = {
     "midagma_indep_destroy": (None, [_vp]),
     "midagma_indep_last_error": (C.c_char_p, [_vp]),
     "midagma_indep_set_data": (_int, [_vp, _dp, _i64, _i64]),
+    "midagma_indep_set_data_dev": (_int, [_vp, _vp, _i64, _i64, _i64, _vp]),
     "midagma_indep_set_bandwidths": (_int, [_vp, _dp, _i64]),
+    "midagma_indep_median_bandwidths": (_int, [_vp, _vp, _i64, _dp]),
+    "midagma_indep_bandwidth_profile": (_int, [_vp, _dp]),
     "midagma_indep_batch_pairs": (_i64, [_vp, _i64, _i64]),
     "midagma_indep_profile": (_int, [_vp, _dp]),
     "midagma_indep_run": (_int, [_vp, _int, _vp, _i64, _i64, _vp, C.c_uint64, _i64, _dp, _vp, _dp, _vp]),

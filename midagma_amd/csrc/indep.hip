@@ -26,6 +26,17 @@
 // counter = (q, p, a, 0), key = (seed low word, seed high word)): 50 random bits, then a itself
 // (a < 2^14), so the keys are distinct and one unsigned compare orders them.  rank(a) is counted
 // against every b, and pi[rank(a)] = a.
+//
+// Device data (midagma_indep_set_data_dev): indep_transpose_kernel writes XT from a row-major
+// device X and ORs two flags per column (non-finite, differs from row 0) in a fixed order.
+//
+// Median bandwidths (midagma_indep_median_bandwidths): sigma^2 of a column is the median of its
+// n (n - 1) / 2 squared differences.  With the column sorted, fl(x_b - x_a) is non-decreasing in b
+// for fixed a and fl(t t) is monotone in |t|, so the k-th smallest squared difference is the square
+// of the k-th smallest sorted-order difference, and #{a < b : fl(x_b - x_a) <= t} is a sum of
+// per-row prefix lengths, each a binary search.  One workgroup per column sorts it in LDS and
+// bisects over the bit pattern of the non-negative doubles: no n^2 values exist anywhere and the
+// result is numpy's median bit for bit.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -259,6 +270,168 @@ __global__ __launch_bounds__(256) void indep_final_kernel(const double* __restri
   }
 }
 
+// XT[v][a] = X[a][v] (X row-major n x d, row stride ld) and per-(row chunk, column) flag bytes:
+// pflag[(chunk * 2 + 0) * d + v] = the chunk's rows of column v hold a non-finite value,
+// pflag[(chunk * 2 + 1) * d + v] = one of them differs from row 0's.  grid (ceil(d / 32), chunks),
+// 256 threads = 32 columns x 8 rows, 32 x 32 tiles through LDS (stride 33).
+constexpr int TT = 32;
+constexpr int TCHUNK = 1024;  // rows per workgroup
+__global__ __launch_bounds__(256) void indep_transpose_kernel(const double* __restrict__ X, int n, int d, int64_t ld,
+                                                              double* __restrict__ XT, uint8_t* __restrict__ pflag) {
+  __shared__ double tile[TT][TT + 1];
+  __shared__ uint32_t fl[8][TT];
+  const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
+  const int c0 = blockIdx.x * TT;
+  const int rbeg = blockIdx.y * TCHUNK, rend = min(n, rbeg + TCHUNK);
+  const int col = c0 + tx;
+  const double first = col < d ? X[col] : 0.0;
+  uint32_t f = 0;
+  for (int r0 = rbeg; r0 < rend; r0 += TT) {
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      const int r = r0 + ty + 8 * u;
+      double val = 0.0;
+      if (r < rend && col < d) {
+        val = X[static_cast<int64_t>(r) * ld + col];
+        f |= (isfinite(val) ? 0u : 1u) | (val != first ? 2u : 0u);
+      }
+      tile[ty + 8 * u][tx] = val;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      const int c = c0 + ty + 8 * u, r = r0 + tx;
+      if (c < d && r < rend) XT[static_cast<int64_t>(c) * n + r] = tile[tx][ty + 8 * u];
+    }
+    __syncthreads();
+  }
+  fl[ty][tx] = f;
+  __syncthreads();
+  if (ty == 0 && col < d) {
+    uint32_t g = 0;
+#pragma unroll
+    for (int k = 0; k < 8; ++k) g |= fl[k][tx];
+    const int64_t base = static_cast<int64_t>(blockIdx.y) * 2 * d;
+    pflag[base + col] = g & 1u;
+    pflag[base + d + col] = (g >> 1) & 1u;
+  }
+}
+
+// flag[k * d + v] = OR over the chunks of pflag[(chunk * 2 + k) * d + v], k = 0, 1
+__global__ __launch_bounds__(256) void indep_flag_kernel(const uint8_t* __restrict__ pflag, int chunks, int d,
+                                                         uint8_t* __restrict__ flag) {
+  const int64_t i = static_cast<int64_t>(blockIdx.x) * 256 + threadIdx.x;
+  if (i >= 2 * static_cast<int64_t>(d)) return;
+  uint8_t g = 0;
+  for (int c = 0; c < chunks; ++c) g |= pflag[static_cast<int64_t>(c) * 2 * d + i];
+  flag[i] = g;
+}
+
+// the sum / the minimum of one value per thread over the workgroup (any multiple of 64 threads up
+// to 1024; integer sums and minima do not depend on the order); valid in every thread
+__device__ __forceinline__ long long block_sum_ll(long long v, long long* w) {
+#pragma unroll
+  for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off);
+  __syncthreads();
+  if ((threadIdx.x & 63) == 0) w[threadIdx.x >> 6] = v;
+  __syncthreads();
+  long long s = 0;
+  for (int k = 0, nw = blockDim.x >> 6; k < nw; ++k) s += w[k];
+  return s;
+}
+
+__device__ __forceinline__ double block_min(double v, double* w) {
+#pragma unroll
+  for (int off = 32; off >= 1; off >>= 1) v = fmin(v, __shfl_xor(v, off));
+  __syncthreads();
+  if ((threadIdx.x & 63) == 0) w[threadIdx.x >> 6] = v;
+  __syncthreads();
+  double s = w[0];
+  for (int k = 1, nw = blockDim.x >> 6; k < nw; ++k) s = fmin(s, w[k]);
+  return s;
+}
+
+// rows a < b of the sorted column xs[0 .. n) with fl(xs[b] - xs[a]) <= t, for this thread's rows
+// a = tid, tid + threads, ...: per row the length of the prefix of b = a + 1 .. n - 1 (the
+// differences are non-decreasing in b), by binary search.  MINNEXT: also the smallest difference
+// above t over these rows (+inf when there is none).
+template <bool MINNEXT>
+__device__ __forceinline__ long long median_count(const double* xs, int n, double t, double* next) {
+  long long cnt = 0;
+  double mn = INFINITY;
+  for (int a = threadIdx.x; a < n - 1; a += blockDim.x) {
+    const double xa = xs[a];
+    int lo = a + 1, hi = n;
+    while (lo < hi) {
+      const int mid = (lo + hi) >> 1;
+      if (xs[mid] - xa <= t)
+        lo = mid + 1;
+      else
+        hi = mid;
+    }
+    cnt += lo - (a + 1);
+    if constexpr (MINNEXT)
+      if (lo < n) mn = fmin(mn, xs[lo] - xa);
+  }
+  if constexpr (MINNEXT) *next = mn;
+  return cnt;
+}
+
+// med[v] = the reference's median-heuristic sigma^2 of column v = cols[blockIdx.x] (cols null:
+// blockIdx.x): the median of the squared differences of all pairs of rows, 1.0 when that is not
+// > 0.  One workgroup per column, blockDim.x threads (a multiple of 64), sz doubles of dynamic LDS,
+// sz the power of two >= n.  The column is sorted by a bitonic network (padding +inf), then the
+// k-th smallest sorted-order difference is the smallest non-negative double t (bisection over
+// its 63-bit pattern) with #{a < b : fl(x_b - x_a) <= t} >= k + 1.  M = n (n - 1) / 2 odd: element
+// M / 2; even: numpy's mean of elements M / 2 - 1 and M / 2, the second being the first again when
+// more than M / 2 differences are <= it, else the smallest difference above it.
+__global__ __launch_bounds__(1024) void indep_median_kernel(const double* __restrict__ XT,
+                                                            const int64_t* __restrict__ cols, int n, int sz,
+                                                            double* __restrict__ med) {
+  extern __shared__ double xs[];
+  __shared__ long long wsum[16];
+  __shared__ double wmin[16];
+  const int64_t v = cols ? cols[blockIdx.x] : blockIdx.x;
+  const double* x = XT + v * n;
+  const int tid = threadIdx.x, nthr = blockDim.x;
+  for (int i = tid; i < sz; i += nthr) xs[i] = i < n ? x[i] : INFINITY;
+  __syncthreads();
+  for (int k = 2; k <= sz; k <<= 1)
+    for (int j = k >> 1; j >= 1; j >>= 1) {
+      for (int t = tid; t < (sz >> 1); t += nthr) {
+        const int i = 2 * t - (t & (j - 1)), l = i + j;  // bit j of i is clear
+        const double p = xs[i], q = xs[l];
+        if ((p > q) == ((i & k) == 0)) {
+          xs[i] = q;
+          xs[l] = p;
+        }
+      }
+      __syncthreads();
+    }
+  const long long M = static_cast<long long>(n) * (n - 1) / 2;
+  const long long k = (M & 1) ? M / 2 : M / 2 - 1;
+  // count(+inf) = M >= k + 1: every difference of finite values is <= +inf
+  unsigned long long lo = 0, hi = 0x7ff0000000000000ull;
+  while (lo < hi) {
+    const unsigned long long mid = lo + ((hi - lo) >> 1);
+    const long long c = block_sum_ll(median_count<false>(xs, n, __longlong_as_double(mid), nullptr), wsum);
+    if (c >= k + 1)
+      hi = mid;
+    else
+      lo = mid + 1;
+  }
+  const double vk = __longlong_as_double(lo);
+  double m = vk * vk;
+  if (!(M & 1)) {
+    double next;
+    const long long c = block_sum_ll(median_count<true>(xs, n, vk, &next), wsum);
+    const double above = block_min(next, wmin);
+    const double vn = c > M / 2 ? vk : above;
+    m = (m + vn * vn) / 2.0;
+  }
+  if (tid == 0) med[v] = m > 0.0 ? m : 1.0;
+}
+
 thread_local std::string g_err;  // errors raised without a handle
 
 }  // namespace
@@ -330,11 +503,15 @@ struct midagma_indep {
   int64_t n = 0, d = 0;
   std::string err;
   hipStream_t comp = nullptr, copy = nullptr;
-  DevBuf<double> XT, rm[2], gm[2], dvar, c, rowtmp;
+  DevBuf<double> XT, rm[2], gm[2], dvar, c, rowtmp, med;
+  DevBuf<uint8_t> pflag, flag;    // set_data_dev: per-chunk and per-column flag bytes
+  DevBuf<int64_t> dcols;          // median_bandwidths: the listed columns
   std::vector<uint8_t> constant;  // zero-range columns: the reference's all-zero centred matrix
   bool have_bw = false, have_stats[2] = {false, false};
   Slot slot[2];
   double prof[4] = {0, 0, 0, 0};  // the last run's stage times (midagma_indep_profile), ms
+  hipEvent_t bw0 = nullptr, bw1 = nullptr;  // around the median kernel
+  double bw_ms = 0.0;                       // the last median_bandwidths' kernel time, ms
 };
 
 namespace {
@@ -429,6 +606,8 @@ extern "C" int midagma_indep_create(midagma_indep** out, int device) {
       HIP_TRY(hipEventCreate(&s.k2));
       HIP_TRY(hipEventCreateWithFlags(&s.done, hipEventDisableTiming));
     }
+    HIP_TRY(hipEventCreate(&h->bw0));
+    HIP_TRY(hipEventCreate(&h->bw1));
   });
   if (rc != MIDAGMA_OK) {
     midagma_indep_destroy(h);
@@ -448,7 +627,10 @@ extern "C" void midagma_indep_destroy(midagma_indep* h) {
     for (hipEvent_t e : {s.up0, s.up, s.k0, s.k1, s.k2, s.done})
       if (e) (void)hipEventDestroy(e);
   }
-  h->XT.release(), h->dvar.release(), h->c.release(), h->rowtmp.release();
+  for (hipEvent_t e : {h->bw0, h->bw1})
+    if (e) (void)hipEventDestroy(e);
+  h->XT.release(), h->dvar.release(), h->c.release(), h->rowtmp.release(), h->med.release();
+  h->pflag.release(), h->flag.release(), h->dcols.release();
   for (int k = 0; k < 2; ++k) h->rm[k].release(), h->gm[k].release();
   if (h->comp) (void)hipStreamDestroy(h->comp);
   if (h->copy) (void)hipStreamDestroy(h->copy);
@@ -480,14 +662,57 @@ extern "C" int midagma_indep_set_data(midagma_indep* h, const double* X, int64_t
   });
 }
 
-extern "C" int midagma_indep_set_bandwidths(midagma_indep* h, const double* sigma2, int64_t d) {
-  if (!h) return ifail(nullptr, MIDAGMA_E_ARG, "indep_set_bandwidths: null handle");
-  if (h->n == 0) return ifail(h, MIDAGMA_E_ARG, "indep_set_bandwidths: set the data first");
-  if (!sigma2 || d != h->d) return ifail(h, MIDAGMA_E_ARG, "indep_set_bandwidths: need d squared bandwidths");
+extern "C" int midagma_indep_set_data_dev(midagma_indep* h, const double* X_dev, int64_t n, int64_t d, int64_t ld,
+                                          void* hip_stream) {
+  if (!h) return ifail(nullptr, MIDAGMA_E_ARG, "indep_set_data_dev: null handle");
+  if (!X_dev || n < 2 || n > kMaxN || d < 1 || d > kMaxD || ld < d)
+    return ifail(h, MIDAGMA_E_ARG, "indep_set_data_dev: need X, 2 <= n <= 16384, 1 <= d <= 65535 and ld >= d");
+  hipStream_t s = static_cast<hipStream_t>(hip_stream);
+  std::vector<uint8_t> flags(2 * d);
+  h->n = h->d = 0;  // the handle holds no data until the new one is checked
+  h->have_bw = h->have_stats[0] = h->have_stats[1] = false;
+  const int rc = iguarded(h, [&] {
+    HIP_TRY(hipSetDevice(h->device));
+    hipPointerAttribute_t attr;
+    if (hipPointerGetAttributes(&attr, X_dev) != hipSuccess || attr.type != hipMemoryTypeDevice ||
+        attr.device != h->device) {
+      (void)hipGetLastError();
+      throw std::invalid_argument("indep_set_data_dev: X is not memory of the handle's device");
+    }
+    HIP_TRY(hipStreamSynchronize(h->comp));  // nothing of an earlier run still reads XT
+    const int chunks = static_cast<int>((n + TCHUNK - 1) / TCHUNK);
+    h->XT.need(static_cast<size_t>(n) * d);
+    h->pflag.need(static_cast<size_t>(chunks) * 2 * d);
+    h->flag.need(2 * d);
+    // on the caller's stream, behind X's producer; the synchronise below (the flags are read on the
+    // host) also orders XT before everything the handle's own streams run later
+    hipLaunchKernelGGL(indep_transpose_kernel, dim3((d + TT - 1) / TT, chunks), dim3(256), 0, s, X_dev,
+                       static_cast<int>(n), static_cast<int>(d), ld, h->XT.p, h->pflag.p);
+    hipLaunchKernelGGL(indep_flag_kernel, dim3((2 * d + 255) / 256), dim3(256), 0, s, h->pflag.p, chunks,
+                       static_cast<int>(d), h->flag.p);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(flags.data(), h->flag.p, 2 * d, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+  });
+  if (rc != MIDAGMA_OK) return rc;
+  for (int64_t v = 0; v < d; ++v)
+    if (flags[v]) return ifail(h, MIDAGMA_E_ARG, "indep_set_data_dev: X holds inf or nan");
+  h->constant.assign(d, 0);
+  for (int64_t v = 0; v < d; ++v) h->constant[v] = flags[d + v] ? 0 : 1;
+  h->n = n;
+  h->d = d;
+  return MIDAGMA_OK;
+}
+
+namespace {
+
+// c = 1 / (2 sigma^2) per variable on the device; the HSIC pre-pass is redone
+int install_bandwidths(midagma_indep* h, const double* sigma2, const char* who) {
+  const int64_t d = h->d;
   std::vector<double> c(d);
   for (int64_t v = 0; v < d; ++v) {
     if (!(sigma2[v] > 0.0) || !std::isfinite(sigma2[v]))
-      return ifail(h, MIDAGMA_E_ARG, "indep_set_bandwidths: squared bandwidths must be finite and > 0");
+      return ifail(h, MIDAGMA_E_ARG, std::string(who) + ": squared bandwidths must be finite and > 0");
     c[v] = 1.0 / (2.0 * sigma2[v]);
   }
   return iguarded(h, [&] {
@@ -498,6 +723,81 @@ extern "C" int midagma_indep_set_bandwidths(midagma_indep* h, const double* sigm
     h->have_bw = true;
     h->have_stats[KIND_HSIC] = false;
   });
+}
+
+}  // namespace
+
+extern "C" int midagma_indep_set_bandwidths(midagma_indep* h, const double* sigma2, int64_t d) {
+  if (!h) return ifail(nullptr, MIDAGMA_E_ARG, "indep_set_bandwidths: null handle");
+  if (h->n == 0) return ifail(h, MIDAGMA_E_ARG, "indep_set_bandwidths: set the data first");
+  if (!sigma2 || d != h->d) return ifail(h, MIDAGMA_E_ARG, "indep_set_bandwidths: need d squared bandwidths");
+  return install_bandwidths(h, sigma2, "indep_set_bandwidths");
+}
+
+extern "C" int midagma_indep_median_bandwidths(midagma_indep* h, const int64_t* cols, int64_t ncols,
+                                               double* sigma2_out) {
+  if (!h) return ifail(nullptr, MIDAGMA_E_ARG, "indep_median_bandwidths: null handle");
+  if (h->n == 0) return ifail(h, MIDAGMA_E_ARG, "indep_median_bandwidths: set the data first");
+  if (cols && ncols < 0) return ifail(h, MIDAGMA_E_ARG, "indep_median_bandwidths: ncols < 0");
+  const int64_t n = h->n, d = h->d;
+  // the listed columns, each once, ascending (a column's value does not depend on the list)
+  std::vector<int64_t> list;
+  if (cols) {
+    std::vector<uint8_t> mark(d, 0);
+    for (int64_t k = 0; k < ncols; ++k) {
+      if (cols[k] < 0 || cols[k] >= d)
+        return ifail(h, MIDAGMA_E_ARG, "indep_median_bandwidths: column index outside [0, d)");
+      mark[cols[k]] = 1;
+    }
+    for (int64_t v = 0; v < d; ++v)
+      if (mark[v]) list.push_back(v);
+  }
+  const int64_t m = cols ? static_cast<int64_t>(list.size()) : d;
+  std::vector<double> med(d), s2(d, 1.0);
+  h->bw_ms = 0.0;
+  if (m > 0) {
+    const int rc = iguarded(h, [&] {
+      HIP_TRY(hipSetDevice(h->device));
+      int sz = 2;
+      while (sz < n) sz <<= 1;
+      const int threads = sz <= 2048 ? 256 : 1024;
+      const size_t lds = static_cast<size_t>(sz) * sizeof(double);
+      if (lds > (size_t(48) << 10))
+        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(indep_median_kernel),
+                                    hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds)));
+      h->med.need(d);
+      if (cols) {
+        h->dcols.need(list.size());
+        HIP_TRY(hipMemcpyAsync(h->dcols.p, list.data(), list.size() * sizeof(int64_t), hipMemcpyHostToDevice,
+                               h->comp));
+      }
+      HIP_TRY(hipEventRecord(h->bw0, h->comp));
+      hipLaunchKernelGGL(indep_median_kernel, dim3(m), dim3(threads), lds, h->comp, h->XT.p,
+                         cols ? h->dcols.p : nullptr, static_cast<int>(n), sz, h->med.p);
+      HIP_TRY(hipGetLastError());
+      HIP_TRY(hipEventRecord(h->bw1, h->comp));
+      HIP_TRY(hipMemcpyAsync(med.data(), h->med.p, d * sizeof(double), hipMemcpyDeviceToHost, h->comp));
+      HIP_TRY(hipStreamSynchronize(h->comp));
+      float ms = 0.f;
+      HIP_TRY(hipEventElapsedTime(&ms, h->bw0, h->bw1));
+      h->bw_ms = ms;
+    });
+    if (rc != MIDAGMA_OK) return rc;
+    if (cols)
+      for (int64_t v : list) s2[v] = med[v];
+    else
+      s2 = med;
+  }
+  const int rc = install_bandwidths(h, s2.data(), "indep_median_bandwidths");
+  if (rc != MIDAGMA_OK) return rc;
+  if (sigma2_out) std::copy(s2.begin(), s2.end(), sigma2_out);
+  return MIDAGMA_OK;
+}
+
+extern "C" int midagma_indep_bandwidth_profile(const midagma_indep* h, double* ms_out) {
+  if (!h || !ms_out) return ifail(nullptr, MIDAGMA_E_ARG, "indep_bandwidth_profile: bad arguments");
+  *ms_out = h->bw_ms;
+  return MIDAGMA_OK;
 }
 
 extern "C" int64_t midagma_indep_batch_pairs(const midagma_indep* h, int64_t P, int64_t budget_bytes) {

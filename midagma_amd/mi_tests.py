@@ -15,6 +15,18 @@ One keyword is added, ``perms``:
     tests").  The p-values are valid permutation p-values but come from another stream than the
     reference's.
 
+The RBF kernels' median-heuristic bandwidths of 'hsic' are computed on the device
+(`HipIndep.median_bandwidths`, no O(n^2) host work).  `permutation_null` has a keyword
+``bandwidths`` for it: ``"device"`` (default) or ``"host"`` (`median_sigma2`, numpy).  The two give
+the same bits, so no result depends on it; `test_pairwise_independence` and
+`get_I_from_full_pairwise_tests` keep the reference's parameter lists (plus ``perms``) and use the
+default.
+
+X (x and y for the two `_stat` functions) may be a float64 torch CUDA tensor: 'hsic' and 'dcor' then
+read it on its device, on torch's current stream, without a host copy and without writing it
+(``perms="numpy"`` still draws on the host and uploads the permutations); 'pearson' and 'spearman'
+copy it to the host.
+
 Not mirrored: `permutation_pvalue(stat_fn, ...)`, which takes an arbitrary Python callable.
 """
 from __future__ import annotations
@@ -25,7 +37,7 @@ from typing import Iterable, List, Literal, Optional, Tuple
 
 import numpy as np
 
-from .solver import HipIndep
+from .solver import HipIndep, is_device_tensor
 
 __all__ = ["IndepTestResult", "hsic_stat", "dcor_stat", "permutation_null", "test_pairwise_independence",
            "get_I_from_full_pairwise_tests", "summarize_I", "median_sigma2"]
@@ -65,8 +77,21 @@ def _sigma2(x, sigma) -> float:
     return s2 if s2 > 0 else 1.0
 
 
-def _as_data(X) -> np.ndarray:
-    """A C-contiguous float64 copy (the caller's X is never touched), checked."""
+def _as_data(X):
+    """A C-contiguous float64 copy (the caller's X is never touched), checked; a device tensor is
+    checked for dtype and shape and returned as it is (the engine only reads it, and checks it for
+    inf and nan on the device)."""
+    if is_device_tensor(X):
+        import torch
+        if X.dtype != torch.float64:
+            raise ValueError("a device X must be a float64 tensor")
+        if X.dim() != 2:
+            raise ValueError("X must be a 2-d array (n samples x d variables)")
+        if X.shape[0] < 2:
+            raise ValueError("need at least 2 samples")
+        if X.shape[0] > HipIndep.MAX_N:
+            raise ValueError(f"at most {HipIndep.MAX_N} samples are supported, got {X.shape[0]}")
+        return X
     X = np.array(X, dtype=np.float64, order="C", copy=True)
     if X.ndim != 2:
         raise ValueError("X must be a 2-d array (n samples x d variables)")
@@ -86,7 +111,19 @@ def _as_pairs(pairs, d: int) -> np.ndarray:
     return P
 
 
-def _two_columns(x, y) -> np.ndarray:
+def _host(X) -> np.ndarray:
+    return X.detach().cpu().numpy() if is_device_tensor(X) else X
+
+
+def _two_columns(x, y):
+    if is_device_tensor(x) or is_device_tensor(y):
+        import torch
+        dev = x.device if is_device_tensor(x) else y.device
+        x = torch.as_tensor(x, dtype=torch.float64, device=dev).reshape(-1)
+        y = torch.as_tensor(y, dtype=torch.float64, device=dev).reshape(-1)
+        if x.shape != y.shape:
+            raise ValueError("x and y must have the same length")
+        return _as_data(torch.stack([x, y], dim=1))
     x = np.asarray(x, dtype=np.float64).ravel()
     y = np.asarray(y, dtype=np.float64).ravel()
     if x.shape != y.shape:
@@ -100,7 +137,14 @@ def hsic_stat(x: np.ndarray, y: np.ndarray, sigma_x: Optional[float] = None, sig
     X = _two_columns(x, y)
     eng = HipIndep(X)
     try:
-        eng.set_bandwidths([_sigma2(X[:, 0], sigma_x), _sigma2(X[:, 1], sigma_y)])
+        given = (sigma_x, sigma_y)
+        auto = [v for v in (0, 1) if given[v] is None]
+        s2 = eng.median_bandwidths(auto) if auto else np.ones(2)
+        for v in (0, 1):
+            if given[v] is not None:
+                s2[v] = _sigma2(None, given[v])
+        if len(auto) < 2:
+            eng.set_bandwidths(s2)
         stat, _ = eng.run("hsic", [(0, 1)], 0)
     finally:
         eng.close()
@@ -127,15 +171,18 @@ def _numpy_perms(rng: np.random.Generator, m: int, P: int, n: int) -> np.ndarray
 
 
 def permutation_null(X, pairs, *, test: str = "hsic", num_perm: int = 200, seed: int = 0, perms: str = "numpy",
-                     device: int = 0, budget_bytes: int = 0, return_null: bool = True):
+                     device: int = 0, budget_bytes: int = 0, return_null: bool = True, bandwidths: str = "device"):
     """(stat, ge, null): per pair the observed statistic, ge = #{p : stat_p >= stat} and (m x
     num_perm, or None) the permuted statistics of the 'hsic' / 'dcor' permutation test.
     budget_bytes: the device's byte budget per pair batch (0: the library's default); results do
-    not depend on it."""
+    not depend on it.  bandwidths: where the 'hsic' medians are computed ('device' or 'host'; the
+    same bits).  A device X makes its device the engine's (`device` is ignored)."""
     if test not in HipIndep.KINDS:
         raise ValueError("test must be 'hsic' or 'dcor'")
     if perms not in ("numpy", "device"):
         raise ValueError("perms must be 'numpy' or 'device'")
+    if bandwidths not in ("device", "host"):
+        raise ValueError("bandwidths must be 'device' or 'host'")
     X = _as_data(X)
     n, d = X.shape
     pairs = _as_pairs(pairs, d)
@@ -144,10 +191,12 @@ def permutation_null(X, pairs, *, test: str = "hsic", num_perm: int = 200, seed:
         raise ValueError("num_perm must be >= 0")
     eng = HipIndep(X, device)
     try:
-        if test == "hsic":
+        if test == "hsic" and bandwidths == "device":
+            eng.median_bandwidths(np.unique(pairs))
+        elif test == "hsic":
             s2 = np.ones(d)
             for v in np.unique(pairs):
-                s2[v] = median_sigma2(X[:, v])
+                s2[v] = median_sigma2(_host(X[:, v]))
             eng.set_bandwidths(s2)
         if perms == "device":
             out = eng.run(test, pairs, P, None, seed, budget_bytes, return_null=return_null)
@@ -208,7 +257,7 @@ def test_pairwise_independence(X: np.ndarray, pairs: Iterable[Tuple[int, int]], 
         raise ValueError("test must be one of 'hsic', 'dcor', 'pearson', 'spearman'")
     pairs = [(int(i), int(j)) for (i, j) in pairs]
     if test in ("pearson", "spearman"):
-        X = _as_data(X)
+        X = _as_data(_host(X))
         _as_pairs(pairs, X.shape[1])
         fn = _pearson_stat_pvalue if test == "pearson" else _spearman_stat_pvalue
         out = []
@@ -230,7 +279,8 @@ def get_I_from_full_pairwise_tests(X: np.ndarray, *, alpha: float = 0.05, test: 
                                    perms: str = "numpy") -> np.ndarray:
     """Test all pairs and return I = {(i, j): p > alpha_eff}, the pairs whose independence is not
     rejected (alpha_eff = alpha / #pairs under Bonferroni), in the reference's pair order."""
-    X = np.asarray(X)
+    if not is_device_tensor(X):
+        X = np.asarray(X)
     n, d = X.shape
     pairs: List[Tuple[int, int]] = []
     if undirected:

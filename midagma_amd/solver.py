@@ -603,25 +603,71 @@ class HipGroup:
 
 class HipIndep:
     """Pairwise permutation independence tests on one GPU (`midagma_indep_*`, csrc/indep.hip):
-    the engine under `midagma_amd.mi_tests`.  Holds a device copy of X (n x d)."""
+    the engine under `midagma_amd.mi_tests`.  Holds a device copy of X (n x d).
+
+    X is a host array, or a 2-d float64 torch CUDA tensor: the engine then lives on the tensor's
+    device (`device` is ignored), reads X there on torch's current stream for that device without
+    a host copy (a unit column stride is used as it is, anything else through `.contiguous()`) and
+    never writes it.  No synchronise is needed around the call."""
 
     KINDS = {"hsic": 0, "dcor": 1}
     MAX_N = 16384
 
-    def __init__(self, X: np.ndarray, device: int = 0):
+    def __init__(self, X, device: int = 0):
         self.L = _lib.lib()
-        X = _as_f64(X)  # (the library copies it to the device and never writes it)
-        if X.ndim != 2:
-            raise ValueError("X must be n x d")
-        self.n, self.d = int(X.shape[0]), int(X.shape[1])
-        if self.n < 2 or self.n > self.MAX_N:
-            raise ValueError(f"need 2 <= n <= {self.MAX_N} samples, got {self.n}")
-        if not np.isfinite(X).all():
-            raise ValueError("X holds inf or nan")
+        self.h = None
+        self.n = self.d = 0
+        on_device = is_device_tensor(X)
+        if on_device:
+            self._check_tensor(X)
+            device = X.device.index
+        else:
+            X = self._check_array(X)
         h = C.c_void_p()
         self._check(self.L.midagma_indep_create(C.byref(h), int(device)), None, "indep_create")
         self.h = h
-        self._check(self.L.midagma_indep_set_data(self.h, dptr(X), self.n, self.d), self.h, "indep_set_data")
+        try:
+            self.set_data(X)
+        except Exception:
+            self.close()
+            raise
+
+    def _check_tensor(self, X):
+        import torch
+        if X.dtype != torch.float64 or X.dim() != 2:
+            raise ValueError("a device X must be a 2-d float64 tensor (n x d)")
+        if int(X.shape[0]) < 2 or int(X.shape[0]) > self.MAX_N:
+            raise ValueError(f"need 2 <= n <= {self.MAX_N} samples, got {int(X.shape[0])}")
+        if int(X.shape[1]) < 1:
+            raise ValueError("need at least one variable")
+
+    def _check_array(self, X) -> np.ndarray:
+        X = _as_f64(X)  # (the library copies it to the device and never writes it)
+        if X.ndim != 2:
+            raise ValueError("X must be n x d")
+        if X.shape[0] < 2 or X.shape[0] > self.MAX_N:
+            raise ValueError(f"need 2 <= n <= {self.MAX_N} samples, got {X.shape[0]}")
+        if not np.isfinite(X).all():
+            raise ValueError("X holds inf or nan")
+        return X
+
+    def set_data(self, X):
+        """Replace the engine's data (bandwidths and pre-passes are dropped).  A device tensor must
+        live on the engine's device.  When the library rejects a device X (inf or nan), the engine
+        holds no data: every later call raises ValueError until a set_data succeeds."""
+        self.n = self.d = 0
+        if is_device_tensor(X):
+            self._check_tensor(X)
+            if X.stride(1) != 1 or X.stride(0) < X.shape[1]:
+                X = X.contiguous()
+            n, d, ld = _rows(X)
+            rc = self.L.midagma_indep_set_data_dev(self.h, C.c_void_p(X.data_ptr()), n, d, ld, _cur_stream(X.device))
+            self._check(rc, self.h, "indep_set_data_dev")
+        else:
+            X = self._check_array(X)
+            n, d = int(X.shape[0]), int(X.shape[1])
+            self._check(self.L.midagma_indep_set_data(self.h, dptr(X), n, d), self.h, "indep_set_data")
+        self.n, self.d = n, d
 
     def _check(self, rc, handle, what):
         if rc >= 0:
@@ -647,6 +693,32 @@ class HipIndep:
         """The RBF kernels' sigma^2 per variable (hsic)."""
         s2 = _as_f64(sigma2).ravel()
         self._check(self.L.midagma_indep_set_bandwidths(self.h, dptr(s2), s2.size), self.h, "indep_set_bandwidths")
+
+    def median_bandwidths(self, cols=None) -> np.ndarray:
+        """sigma^2 per variable by the reference's median heuristic, computed on the device (bit for
+        bit `mi_tests.median_sigma2` of the column) for the listed columns (None: all) and 1.0 for
+        the others; installed as `set_bandwidths` would.  Returns all d values."""
+        if not self.d:
+            raise ValueError("indep_median_bandwidths: set the data first")
+        s2 = np.zeros(self.d)
+        if cols is None:
+            cp, nc = None, 0
+        else:
+            cols = np.ascontiguousarray(cols, dtype=np.int64).ravel()
+            if cols.size == 0:  # (an empty array has no usable address)
+                s2[:] = 1.0
+                self.set_bandwidths(s2)
+                return s2
+            cp, nc = C.c_void_p(cols.ctypes.data), int(cols.size)
+        self._check(self.L.midagma_indep_median_bandwidths(self.h, cp, nc, dptr(s2)), self.h,
+                    "indep_median_bandwidths")
+        return s2
+
+    def bandwidth_ms(self) -> float:
+        """The last `median_bandwidths`' kernel time in ms (device events; diagnostics)."""
+        ms = np.zeros(1)
+        self._check(self.L.midagma_indep_bandwidth_profile(self.h, dptr(ms)), self.h, "indep_bandwidth_profile")
+        return float(ms[0])
 
     def batch_pairs(self, P: int, budget_bytes: int = 0) -> int:
         """Pairs per device batch under a byte budget (0: the library's default)."""
