@@ -155,6 +155,7 @@ GROUP_EMULATE = 1
 # test hooks the library exports beside the ABI (not declared in the header, so not in EXPORTED)
 DEBUG_HOOKS = {
     "midagma_debug_slot_matrices": (_int, [_vp, _dp, _dp]),
+    "midagma_debug_live_bytes": (_i64, []),
 }
 
 _lock = threading.Lock()

@@ -85,25 +85,6 @@ bool all_finite_w(const double* p, int64_t n) {
   return true;
 }
 
-// an exception from a member's work as a C ABI code (solver.hip's `guarded` mapping)
-int classify(std::exception_ptr e, std::string& msg) {
-  try {
-    std::rethrow_exception(e);
-  } catch (const HipError& x) {
-    msg = x.what();
-    return MIDAGMA_E_HIP;
-  } catch (const std::invalid_argument& x) {
-    msg = x.what();
-    return MIDAGMA_E_ARG;
-  } catch (const std::exception& x) {
-    msg = x.what();
-    return MIDAGMA_E_STATE;
-  } catch (...) {
-    msg = "unknown error";
-    return MIDAGMA_E_STATE;
-  }
-}
-
 // the members' meeting point before any collective: every member arrives with whether its setup
 // succeeded; all leave with the conjunction
 class SetupBarrier {
@@ -242,7 +223,7 @@ hipGraphExec_t group_capture(midagma_group* g, const midagma_solver* caller, int
 void group_clear_handback(midagma_group* g) {
   static const int32_t running = ST_RUNNING;
   for (midagma_solver* s : g->m)
-    HIP_TRY(hipMemcpyAsync(&s->d_state->status, &running, sizeof(int32_t), hipMemcpyHostToDevice, g->s0()));
+    HIP_TRY(hipMemcpyAsync(&s->d_state.p->status, &running, sizeof(int32_t), hipMemcpyHostToDevice, g->s0()));
 }
 
 }  // namespace midagma
@@ -323,7 +304,7 @@ int midagma_group_create(midagma_group** out, int loss, int64_t d, const int* de
         s->comm = comms[(size_t)k];
         s->comm_ranks = ndev;
         s->agree.alloc(8);
-        if (!s->h_agree) HIP_TRY(hipHostMalloc(&s->h_agree, 8 * sizeof(double), hipHostMallocDefault));
+        s->h_agree.alloc(8);
         s->graphs_valid = false;  // its slot graphs now carry the all-reduce
       }
     }

@@ -48,6 +48,7 @@
 #include <vector>
 
 #include "../../include/midagma_hip.h"
+#include "devmem.h"
 #include "launch.h"
 #include "philox.h"
 
@@ -444,40 +445,6 @@ namespace {
 constexpr int64_t kMaxN = 16384, kMaxD = 65535, kMaxP = 65535, kMaxBatchPairs = 32768;
 constexpr int64_t kDefaultBudget = int64_t(128) << 20;
 
-template <class T>
-struct DevBuf {
-  T* p = nullptr;
-  size_t cap = 0;
-  void need(size_t count) {
-    if (count <= cap) return;
-    release();
-    HIP_TRY(hipMalloc(reinterpret_cast<void**>(&p), std::max<size_t>(count, 1) * sizeof(T)));
-    cap = count;
-  }
-  void release() {
-    if (p) (void)hipFree(p);
-    p = nullptr;
-    cap = 0;
-  }
-};
-
-template <class T>
-struct PinBuf {
-  T* p = nullptr;
-  size_t cap = 0;
-  void need(size_t count) {
-    if (count <= cap) return;
-    release();
-    HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&p), std::max<size_t>(count, 1) * sizeof(T), hipHostMallocDefault));
-    cap = count;
-  }
-  void release() {
-    if (p) (void)hipHostFree(p);
-    p = nullptr;
-    cap = 0;
-  }
-};
-
 struct Slot {
   PinBuf<int32_t> hperm;
   PinBuf<int64_t> hpairs, hge;
@@ -487,13 +454,9 @@ struct Slot {
   DevBuf<double> partial, dvals;
   // up0 .. up: the batch's upload (copy stream); k0 .. k1: its permutation kernel; k1 .. k2: its
   // statistic kernels; done: its results are on the host (compute stream)
-  hipEvent_t up0 = nullptr, up = nullptr, k0 = nullptr, k1 = nullptr, k2 = nullptr, done = nullptr;
+  Event up0, up, k0, k1, k2, done;
   int64_t q0 = 0, mb = 0;
   bool busy = false;
-  void release() {
-    hperm.release(), hpairs.release(), hge.release(), hvals.release();
-    dperm.release(), dpairs.release(), dge.release(), partial.release(), dvals.release();
-  }
 };
 
 }  // namespace
@@ -510,8 +473,8 @@ struct midagma_indep {
   bool have_bw = false, have_stats[2] = {false, false};
   Slot slot[2];
   double prof[4] = {0, 0, 0, 0};  // the last run's stage times (midagma_indep_profile), ms
-  hipEvent_t bw0 = nullptr, bw1 = nullptr;  // around the median kernel
-  double bw_ms = 0.0;                       // the last median_bandwidths' kernel time, ms
+  Event bw0, bw1;      // around the median kernel
+  double bw_ms = 0.0;  // the last median_bandwidths' kernel time, ms
 };
 
 namespace {
@@ -526,14 +489,10 @@ int iguarded(midagma_indep* h, F&& f) {
   try {
     f();
     return MIDAGMA_OK;
-  } catch (const HipError& x) {
-    return ifail(h, MIDAGMA_E_HIP, x.what());
-  } catch (const std::invalid_argument& x) {
-    return ifail(h, MIDAGMA_E_ARG, x.what());
-  } catch (const std::exception& x) {
-    return ifail(h, MIDAGMA_E_STATE, x.what());
   } catch (...) {
-    return ifail(h, MIDAGMA_E_STATE, "unknown error");
+    std::string msg;
+    const int rc = classify(std::current_exception(), msg);
+    return ifail(h, rc, msg);
   }
 }
 
@@ -557,8 +516,8 @@ void prepare_stats(midagma_indep* h, int kind) {
   if (h->have_stats[kind]) return;
   const int n = static_cast<int>(h->n), d = static_cast<int>(h->d);
   const size_t nd = static_cast<size_t>(n) * d;
-  h->rm[kind].need(nd);
-  h->gm[kind].need(d);
+  h->rm[kind].alloc(nd);
+  h->gm[kind].alloc(d);
   const dim3 grid(n, d);
   if (kind == KIND_HSIC) {
     hipLaunchKernelGGL((indep_row_kernel<KIND_HSIC, 0>), grid, dim3(256), 0, h->comp, h->XT.p, h->c.p, nullptr, nullptr,
@@ -566,8 +525,8 @@ void prepare_stats(midagma_indep* h, int kind) {
     hipLaunchKernelGGL(indep_col_kernel, dim3(d), dim3(256), 0, h->comp, h->rm[kind].p, n, static_cast<double>(n),
                        h->gm[kind].p);
   } else {
-    h->dvar.need(d);
-    h->rowtmp.need(nd);
+    h->dvar.alloc(d);
+    h->rowtmp.alloc(nd);
     hipLaunchKernelGGL((indep_row_kernel<KIND_DCOR, 0>), grid, dim3(256), 0, h->comp, h->XT.p, nullptr, nullptr,
                        nullptr, n, h->rm[kind].p);
     hipLaunchKernelGGL(indep_col_kernel, dim3(d), dim3(256), 0, h->comp, h->rm[kind].p, n, static_cast<double>(n),
@@ -599,15 +558,11 @@ extern "C" int midagma_indep_create(midagma_indep** out, int device) {
     HIP_TRY(hipStreamCreateWithFlags(&h->comp, hipStreamNonBlocking));
     HIP_TRY(hipStreamCreateWithFlags(&h->copy, hipStreamNonBlocking));
     for (Slot& s : h->slot) {
-      HIP_TRY(hipEventCreate(&s.up0));
-      HIP_TRY(hipEventCreate(&s.up));
-      HIP_TRY(hipEventCreate(&s.k0));
-      HIP_TRY(hipEventCreate(&s.k1));
-      HIP_TRY(hipEventCreate(&s.k2));
-      HIP_TRY(hipEventCreateWithFlags(&s.done, hipEventDisableTiming));
+      for (Event* e : {&s.up0, &s.up, &s.k0, &s.k1, &s.k2}) e->create();
+      s.done.create(hipEventDisableTiming);
     }
-    HIP_TRY(hipEventCreate(&h->bw0));
-    HIP_TRY(hipEventCreate(&h->bw1));
+    h->bw0.create();
+    h->bw1.create();
   });
   if (rc != MIDAGMA_OK) {
     midagma_indep_destroy(h);
@@ -622,16 +577,6 @@ extern "C" void midagma_indep_destroy(midagma_indep* h) {
   (void)hipSetDevice(h->device);
   if (h->comp) (void)hipStreamSynchronize(h->comp);
   if (h->copy) (void)hipStreamSynchronize(h->copy);
-  for (Slot& s : h->slot) {
-    s.release();
-    for (hipEvent_t e : {s.up0, s.up, s.k0, s.k1, s.k2, s.done})
-      if (e) (void)hipEventDestroy(e);
-  }
-  for (hipEvent_t e : {h->bw0, h->bw1})
-    if (e) (void)hipEventDestroy(e);
-  h->XT.release(), h->dvar.release(), h->c.release(), h->rowtmp.release(), h->med.release();
-  h->pflag.release(), h->flag.release(), h->dcols.release();
-  for (int k = 0; k < 2; ++k) h->rm[k].release(), h->gm[k].release();
   if (h->comp) (void)hipStreamDestroy(h->comp);
   if (h->copy) (void)hipStreamDestroy(h->copy);
   delete h;
@@ -653,7 +598,7 @@ extern "C" int midagma_indep_set_data(midagma_indep* h, const double* X, int64_t
   return iguarded(h, [&] {
     HIP_TRY(hipSetDevice(h->device));
     HIP_TRY(hipStreamSynchronize(h->comp));
-    h->XT.need(xt.size());
+    h->XT.alloc(xt.size());
     HIP_TRY(hipMemcpy(h->XT.p, xt.data(), xt.size() * sizeof(double), hipMemcpyHostToDevice));
     h->n = n;
     h->d = d;
@@ -681,9 +626,9 @@ extern "C" int midagma_indep_set_data_dev(midagma_indep* h, const double* X_dev,
     }
     HIP_TRY(hipStreamSynchronize(h->comp));  // nothing of an earlier run still reads XT
     const int chunks = static_cast<int>((n + TCHUNK - 1) / TCHUNK);
-    h->XT.need(static_cast<size_t>(n) * d);
-    h->pflag.need(static_cast<size_t>(chunks) * 2 * d);
-    h->flag.need(2 * d);
+    h->XT.alloc(static_cast<size_t>(n) * d);
+    h->pflag.alloc(static_cast<size_t>(chunks) * 2 * d);
+    h->flag.alloc(2 * d);
     // on the caller's stream, behind X's producer; the synchronise below (the flags are read on the
     // host) also orders XT before everything the handle's own streams run later
     hipLaunchKernelGGL(indep_transpose_kernel, dim3((d + TT - 1) / TT, chunks), dim3(256), 0, s, X_dev,
@@ -718,7 +663,7 @@ int install_bandwidths(midagma_indep* h, const double* sigma2, const char* who) 
   return iguarded(h, [&] {
     HIP_TRY(hipSetDevice(h->device));
     HIP_TRY(hipStreamSynchronize(h->comp));
-    h->c.need(d);
+    h->c.alloc(d);
     HIP_TRY(hipMemcpy(h->c.p, c.data(), d * sizeof(double), hipMemcpyHostToDevice));
     h->have_bw = true;
     h->have_stats[KIND_HSIC] = false;
@@ -765,9 +710,9 @@ extern "C" int midagma_indep_median_bandwidths(midagma_indep* h, const int64_t* 
       if (lds > (size_t(48) << 10))
         HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(indep_median_kernel),
                                     hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds)));
-      h->med.need(d);
+      h->med.alloc(d);
       if (cols) {
-        h->dcols.need(list.size());
+        h->dcols.alloc(list.size());
         HIP_TRY(hipMemcpyAsync(h->dcols.p, list.data(), list.size() * sizeof(int64_t), hipMemcpyHostToDevice,
                                h->comp));
       }
@@ -871,16 +816,16 @@ extern "C" int midagma_indep_run(midagma_indep* h, int kind, const int64_t* pair
       const int64_t mb = std::min(mbmax, m - q0);
       s.q0 = q0;
       s.mb = mb;
-      s.hpairs.need(2 * mb), s.dpairs.need(2 * mb);
-      s.hge.need(mb), s.dge.need(mb);
-      s.hvals.need(mb * P1), s.dvals.need(mb * P1);
-      s.partial.need(mb * P1 * ntiles);
-      s.dperm.need(mb * P * n);
+      s.hpairs.alloc(2 * mb), s.dpairs.alloc(2 * mb);
+      s.hge.alloc(mb), s.dge.alloc(mb);
+      s.hvals.alloc(mb * P1), s.dvals.alloc(mb * P1);
+      s.partial.alloc(mb * P1 * ntiles);
+      s.dperm.alloc(mb * P * n);
       std::memcpy(s.hpairs.p, pairs + 2 * q0, 2 * mb * sizeof(int64_t));
       HIP_TRY(hipEventRecord(s.up0, h->copy));
       HIP_TRY(hipMemcpyAsync(s.dpairs.p, s.hpairs.p, 2 * mb * sizeof(int64_t), hipMemcpyHostToDevice, h->copy));
       if (!device_perms && P > 0) {
-        s.hperm.need(mb * P * n);
+        s.hperm.alloc(mb * P * n);
         const clock::time_point t_stage = clock::now();
         std::memcpy(s.hperm.p, perms + q0 * P * n, mb * P * n * sizeof(int32_t));
         h->prof[0] += ms_since(t_stage);

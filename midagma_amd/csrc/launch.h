@@ -2,10 +2,12 @@
 // no allocation: safe to capture into a hipGraph).
 #pragma once
 
+#include <exception>
 #include <stdexcept>
 #include <string>
 #include <vector>
 
+#include "../../include/midagma_hip.h"
 #include "common.h"
 #include "knobs.h"
 
@@ -18,6 +20,25 @@ struct HipError : std::runtime_error {
                            std::to_string(line) + " (" + what + ")"),
         code(e) {}
 };
+
+// an exception as a C ABI code with its message: what every entry point returns for a throw
+inline int classify(std::exception_ptr e, std::string& msg) {
+  try {
+    std::rethrow_exception(e);
+  } catch (const HipError& x) {
+    msg = x.what();
+    return MIDAGMA_E_HIP;
+  } catch (const std::invalid_argument& x) {
+    msg = x.what();
+    return MIDAGMA_E_ARG;
+  } catch (const std::exception& x) {
+    msg = x.what();
+    return MIDAGMA_E_STATE;
+  } catch (...) {
+    msg = "unknown error";
+    return MIDAGMA_E_STATE;
+  }
+}
 
 struct GJWork {
   double* P;       // >= 2 x 32 x 32  (double-buffered inverse of the diagonal block)

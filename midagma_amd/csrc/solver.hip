@@ -46,12 +46,10 @@ int guarded(midagma_solver* s, F&& f) {
   try {
     if (s) HIP_TRY(hipSetDevice(s->device));
     return f();
-  } catch (const HipError& e) {
-    return fail(s, MIDAGMA_E_HIP, e.what());
-  } catch (const std::invalid_argument& e) {
-    return fail(s, MIDAGMA_E_ARG, e.what());
-  } catch (const std::exception& e) {
-    return fail(s, MIDAGMA_E_STATE, e.what());
+  } catch (...) {
+    std::string msg;
+    const int rc = classify(std::current_exception(), msg);
+    return fail(s, rc, msg);
   }
 }
 
@@ -306,7 +304,7 @@ int midagma_colsum_dev(const double* X, int64_t n, int64_t d, int64_t ldx, doubl
     return fail(nullptr, MIDAGMA_E_ARG, "colsum_dev: bad arguments");
   return guarded(nullptr, [&] {
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    DevBuf part;
+    DevBuf<> part;
     part.alloc((size_t)colsum_parts(n) * d);
     launch_colsum(X, n, d, ldx, part.p, out_dev, st);
     HIP_TRY(hipStreamSynchronize(st));  // the partials are freed on return
@@ -337,7 +335,7 @@ int midagma_gram(const double* X, int64_t n, int64_t d, int64_t ldx, int on_devi
     }();
     const GramPlan p = gram_plan(n, d, chunk_rows);
     const int64_t D = p.D, DD = D * D;
-    DevBuf S, Z, fl;
+    DevBuf<> S, Z, fl;
     S.alloc((size_t)p.chunk * D);
     Z.alloc((size_t)(p.split + 2) * DD);  // [0] the running sum, [1..split] a chunk's slices, [split+1] the new sum
     fl.alloc(1);
@@ -402,7 +400,7 @@ int midagma_comm_init(midagma_solver* s, const void* id, int64_t id_len, int nra
     s->comm = comm_create(id, nranks, rank);
     s->comm_ranks = nranks;
     s->agree.alloc(8);
-    if (!s->h_agree) HIP_TRY(hipHostMalloc(&s->h_agree, 8 * sizeof(double), hipHostMallocDefault));
+    s->h_agree.alloc(8);
     s->graphs_valid = false;  // the slot graphs now carry the all-reduce
     return MIDAGMA_OK;
   });
@@ -480,9 +478,9 @@ int midagma_sync(midagma_solver* s) {
 int midagma_profile_parts(midagma_solver* s, int reps, double* ms_out) {
   if (!s || !s->begun || reps < 1 || !ms_out) return fail(s, MIDAGMA_E_STATE, "profile_parts: call begin first");
   return guarded(s, [&] {
-    hipEvent_t a, b;
-    HIP_TRY(hipEventCreate(&a));
-    HIP_TRY(hipEventCreate(&b));
+    Event a, b;
+    a.create();
+    b.create();
     auto timed = [&](auto&& body) {
       HIP_TRY(hipEventRecord(a, s->stream));
       for (int r = 0; r < reps; ++r) body();
@@ -495,16 +493,16 @@ int midagma_profile_parts(midagma_solver* s, int reps, double* ms_out) {
     const int64_t D = s->D;
     // [0] build (sI - W o W)^T   [1] GJ inverse   [2] score GEMM(s)   [3] whole slot (graph)
     // data mode: [4] Y = X (I - W) GEMM   [5] Z = X^T Y GEMM (+ slice sum)
-    ms_out[0] = timed([&] { launch_build_at(s->W.p, D, true, s->Mt.p, D, s->d, 0.0, s->d_params, s->d_state,
+    ms_out[0] = timed([&] { launch_build_at(s->W.p, D, true, s->Mt.p, D, s->d, 0.0, s->d_params.p, s->d_state.p,
                                             s->stream, s->IW.p); });
-    ms_out[1] = timed([&] { launch_gj_inverse(s->Mt.p, D, D, s->gj(), s->d_state, s->stream); });
+    ms_out[1] = timed([&] { launch_gj_inverse(s->Mt.p, D, D, s->gj(), s->d_state.p, s->stream); });
     if (s->mode == MIDAGMA_MODE_COV) {
-      ms_out[2] = timed([&] { s->enqueue_score_cov(s->zbuf, s->d_state, true); });
+      ms_out[2] = timed([&] { s->enqueue_score_cov(s->zbuf, s->d_state.p, true); });
       ms_out[4] = ms_out[5] = 0.0;
     } else {
-      ms_out[2] = timed([&] { s->enqueue_data_partial(s->W.p, s->d_state, s->IW.p); });
-      ms_out[4] = timed([&] { s->enqueue_xw(s->W.p, s->d_state, s->IW.p); });
-      ms_out[5] = timed([&] { s->enqueue_xty(s->d_state); });
+      ms_out[2] = timed([&] { s->enqueue_data_partial(s->W.p, s->d_state.p, s->IW.p); });
+      ms_out[4] = timed([&] { s->enqueue_xw(s->W.p, s->d_state.p, s->IW.p); });
+      ms_out[5] = timed([&] { s->enqueue_xty(s->d_state.p); });
     }
     ms_out[3] = timed([&] { HIP_TRY(hipGraphLaunch(s->g_full, s->stream)); });
     ms_out[6] = ms_out[7] = 0.0;
@@ -515,16 +513,14 @@ int midagma_profile_parts(midagma_solver* s, int reps, double* ms_out) {
       ms_out[6] = timed([&] { s->enqueue_build_inverse(/*fast=*/true, 2); }) - ms_out[0];
       ms_out[7] = timed([&] { HIP_TRY(hipGraphLaunch(s->g_fast, s->stream)); });
       State st{};
-      HIP_TRY(hipMemcpy(&st, s->d_state, sizeof(State), hipMemcpyDeviceToHost));
+      HIP_TRY(hipMemcpy(&st, s->d_state.p, sizeof(State), hipMemcpyDeviceToHost));
       if (st.status == ST_NEED_GJ) {  // the fast path did not run: report it, leave a clean state
         ms_out[6] = ms_out[7] = -1.0;
         static const int32_t running = ST_RUNNING;
-        HIP_TRY(hipMemcpy(&s->d_state->status, &running, sizeof(int32_t), hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(&s->d_state.p->status, &running, sizeof(int32_t), hipMemcpyHostToDevice));
         s->fast_ready = false;
       }
     }
-    HIP_TRY(hipEventDestroy(a));
-    HIP_TRY(hipEventDestroy(b));
     return MIDAGMA_OK;
   });
 }
@@ -548,10 +544,10 @@ int midagma_step_finish(midagma_solver* s) {
 int midagma_poll(midagma_solver* s, midagma_result* res) {
   if (!s) return fail(s, MIDAGMA_E_ARG, "null solver");
   return guarded(s, [&] {
-    HIP_TRY(hipMemcpyAsync(&s->h_state[1], s->d_state, sizeof(State), hipMemcpyDeviceToHost, s->stream));
+    HIP_TRY(hipMemcpyAsync(&s->h_state.p[1], s->d_state.p, sizeof(State), hipMemcpyDeviceToHost, s->stream));
     HIP_TRY(hipStreamSynchronize(s->stream));
-    s->check_handoff(s->h_state[1]);
-    midagma_solver::fill_result(s->h_state[1], res);
+    s->check_handoff(s->h_state.p[1]);
+    midagma_solver::fill_result(s->h_state.p[1], res);
     return MIDAGMA_OK;
   });
 }
@@ -582,6 +578,10 @@ int midagma_set_w_float32(midagma_solver* s, int float32) {
   });
 }
 
+// Test hook (not in the public header): the bytes of every live device and pinned buffer of the
+// process (devmem.h), the deliberate log-det workspace cache included.
+extern "C" int64_t midagma_debug_live_bytes(void) { return g_live_bytes.load(); }
+
 // Test hook (not in the public header): choose the logistic sigmoid GEMM's form for the next
 // set_data (0: the size rule, 1: the one-pass kernel, 2: the serial K split wherever the shape
 // allows it; -1: no change).  Returns the form the current data uses (1 or 2).
@@ -599,7 +599,7 @@ extern "C" int midagma_debug_sig_split(midagma_solver* s, int mode) {
 extern "C" int midagma_debug_spoil_warm(midagma_solver* s) {
   if (!s || !s->blocked()) return -1;
   return guarded(s, [&] {
-    for (DevBuf* b : {&s->Pst2, &s->Pst2b})
+    for (DevBuf<>* b : {&s->Pst2, &s->Pst2b})
       if (b->p) HIP_TRY(hipMemsetAsync(b->p, 0, b->n * sizeof(double), s->stream));
     HIP_TRY(hipStreamSynchronize(s->stream));
     return MIDAGMA_OK;
@@ -670,7 +670,7 @@ extern "C" int midagma_debug_slot_matrices(midagma_solver* s, double* W_out, dou
   if (hipStreamSynchronize(s->stream) != hipSuccess) return -1;
   if (s->side && hipStreamSynchronize(s->side) != hipSuccess) return -1;
   State st{};
-  if (hipMemcpy(&st, s->d_state, sizeof(State), hipMemcpyDeviceToHost) != hipSuccess) return -1;
+  if (hipMemcpy(&st, s->d_state.p, sizeof(State), hipMemcpyDeviceToHost) != hipSuccess) return -1;
   if (st.slots < 1) return -1;
   const size_t row = (size_t)s->d * sizeof(double), pitch = (size_t)s->D * sizeof(double);
   if (W_out && hipMemcpy2D(W_out, row, s->W.p, pitch, row, s->d, hipMemcpyDeviceToHost) != hipSuccess) return -1;
@@ -707,14 +707,14 @@ extern "C" int midagma_debug_blocked(midagma_solver* s, double* out, int64_t cap
 }
 
 int64_t midagma_checkpoints(midagma_solver* s, midagma_ckpt* out, int64_t cap) {
-  if (!s || !s->d_ckpt) return 0;
+  if (!s || !s->d_ckpt.p) return 0;
   int64_t n = 0;
   int rc = guarded(s, [&] {
     State st{};
-    HIP_TRY(hipMemcpy(&st, s->d_state, sizeof(State), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(&st, s->d_state.p, sizeof(State), hipMemcpyDeviceToHost));
     n = std::min<int64_t>(std::min<int64_t>(st.n_ckpt, s->ckpt_cap), cap);
     static_assert(sizeof(midagma_ckpt) == sizeof(CkptRec), "ckpt layout");
-    if (n > 0 && out) HIP_TRY(hipMemcpy(out, s->d_ckpt, n * sizeof(CkptRec), hipMemcpyDeviceToHost));
+    if (n > 0 && out) HIP_TRY(hipMemcpy(out, s->d_ckpt.p, n * sizeof(CkptRec), hipMemcpyDeviceToHost));
     return MIDAGMA_OK;
   });
   return rc == MIDAGMA_OK ? n : rc;
@@ -756,12 +756,12 @@ int midagma_trek(midagma_solver* s, const double* W, double* value, double* G) {
     if (s->trek_tcc) {
       TccCfg c = s->ccfg;
       c.weight = 1.0;  // the bare gradient, as trek_value_grad returns it
-      launch_trek_tcc(s->scratch.p, d, D, c, s->cw, s->d_state_probe, s->Gtrek.p, s->stream);
+      launch_trek_tcc(s->scratch.p, d, D, c, s->cw, s->d_state_probe.p, s->Gtrek.p, s->stream);
       scal = s->cw.scal;
     } else {
       TrekCfg c = s->tcfg;
       c.weight = 1.0;
-      launch_trek_pst(s->scratch.p, d, D, c, s->tw, s->d_state_probe, s->Gtrek.p, s->stream);
+      launch_trek_pst(s->scratch.p, d, D, c, s->tw, s->d_state_probe.p, s->Gtrek.p, s->stream);
       scal = s->tw.scal;
     }
     HIP_TRY(hipMemcpyAsync(value, scal, sizeof(double), hipMemcpyDeviceToHost, s->stream));
@@ -786,7 +786,7 @@ int midagma_h(midagma_solver* s, const double* W, double s_dom, double* h, doubl
     s->scratch.alloc(DD);
     HIP_TRY(hipMemsetAsync(s->scratch.p, 0, DD * sizeof(double), s->stream));
     s->upload_matrix(s->scratch, W, d);
-    DevBuf work;
+    DevBuf<> work;
     work.alloc(DD);
     launch_build_at(s->scratch.p, D, true, work.p, D, d, s_dom, nullptr, nullptr, s->stream);
     GJWork gw = s->gj();
@@ -800,7 +800,6 @@ int midagma_h(midagma_solver* s, const double* W, double s_dom, double* h, doubl
       HIP_TRY(hipMemcpyAsync(G, s->Gtmp.p, (size_t)d * d * sizeof(double), hipMemcpyDeviceToHost, s->stream));
     }
     HIP_TRY(hipStreamSynchronize(s->stream));
-    work.release();
     double ld = 0.0;
     for (int64_t i = 0; i < d; ++i) ld += pl[i];
     *h = -ld + (double)d * std::log(s_dom);
@@ -831,7 +830,7 @@ int midagma_score(midagma_solver* s, const double* W, double* loss, double* G) {
     s->scratch.alloc(DD);
     HIP_TRY(hipMemsetAsync(s->scratch.p, 0, DD * sizeof(double), s->stream));
     s->upload_matrix(s->scratch, W, d);
-    DevBuf rhs;
+    DevBuf<> rhs;
     rhs.alloc(DD);
     // rhs = cov @ (I - W)   (linear.py:85-86)
     s->enqueue_cov_gemm(s->cov_spec(s->cov.p, false, s->scratch.p, B_IMINUS), rhs.p, nullptr);
@@ -844,7 +843,6 @@ int midagma_score(midagma_solver* s, const double* W, double* loss, double* G) {
       s->download_matrix(G, rhs.p);
     }
     HIP_TRY(hipStreamSynchronize(s->stream));
-    rhs.release();
     return MIDAGMA_OK;
   });
 }
@@ -905,18 +903,19 @@ namespace {
 struct LogdetWorkspace {
   int device = -1;
   int64_t D = 0;
-  DevBuf A, P, R, C, piv;
+  DevBuf<> A, P, R, C, piv;
 };
 std::mutex g_ws_mu;
+// The per-device cache, kept for the life of the process.  Pointers that are never deleted, on
+// purpose: an owning object with static storage would free its buffers from a static destructor,
+// when the HIP runtime may already be gone (devmem.h).
 std::vector<LogdetWorkspace*> g_ws;
 }  // namespace
 
-// the 32-padded workspace of the h log-det for this device (created on first use)
-static LogdetWorkspace* logdet_h_ws(int64_t d) {
+// the workspace of padded size D for the current device, created on first use (g_ws_mu held)
+static LogdetWorkspace* logdet_ws(int64_t D) {
   int dev = 0;
   HIP_TRY(hipGetDevice(&dev));
-  const int64_t D = (d + 31) / 32 * 32;  // the 32-block Gauss-Jordan's own granularity
-  std::lock_guard<std::mutex> lock(g_ws_mu);
   for (auto* w : g_ws)
     if (w->device == dev && w->D == D) return w;
   LogdetWorkspace* ws = new LogdetWorkspace();
@@ -929,6 +928,12 @@ static LogdetWorkspace* logdet_h_ws(int64_t d) {
   ws->piv.alloc(D);
   g_ws.push_back(ws);
   return ws;
+}
+
+// the h log-det's: 32-padded, the 32-block Gauss-Jordan's own granularity
+static LogdetWorkspace* logdet_h_ws(int64_t d) {
+  std::lock_guard<std::mutex> lock(g_ws_mu);
+  return logdet_ws((d + 31) / 32 * 32);
 }
 
 // part 0: build + the Gauss-Jordan prologue; parts 1 .. D/32: its block steps; part D/32 + 1: the
@@ -967,18 +972,12 @@ struct midagma_ldfast {
   int device = 0;
   int64_t d = 0, Dgj = 0;  // Gauss-Jordan workspace: 32-padded, as midagma_logdet_h_dev
   int B = 0;               // series block: 128 or 256 (0: d > 256, every step exact)
-  DevBuf ring0, ring1, Y0, Y1, Q0, Q1, P, part, done, hlast;
-  DevBuf A, Pgj, Rgj, Cgj, piv;
-  State* st = nullptr;    // the ring's state (slots: step index; warm_run; status of the series)
-  State* gjst = nullptr;  // the Gauss-Jordan gate of a fast step (ST_RUNNING: run the chain)
+  DevBuf<> ring0, ring1, Y0, Y1, Q0, Q1, P, part, done, hlast;
+  DevBuf<> A, Pgj, Rgj, Cgj, piv;
+  DevBuf<State> st;    // the ring's state (slots: step index; warm_run; status of the series)
+  DevBuf<State> gjst;  // the Gauss-Jordan gate of a fast step (ST_RUNNING: run the chain)
   int64_t* counter = nullptr;  // advanced by a fast step's end (midagma_ldfast_set_counter)
   std::string err;
-  ~midagma_ldfast() {
-    for (DevBuf* b : {&ring0, &ring1, &Y0, &Y1, &Q0, &Q1, &P, &part, &done, &hlast, &A, &Pgj, &Rgj, &Cgj, &piv})
-      b->release();
-    if (st) (void)hipFree(st);
-    if (gjst) (void)hipFree(gjst);
-  }
   GJWork gjw() const { return GJWork{Pgj.p, Rgj.p, Cgj.p, piv.p}; }
   SeriesWork sw() const {
     return SeriesWork{ring0.p, ring1.p, {Y0.p, Y1.p}, {Q0.p, Q1.p}, P.p, part.p, reinterpret_cast<int*>(done.p)};
@@ -1003,12 +1002,12 @@ extern "C" int midagma_ldfast_create(midagma_ldfast** out, int64_t d) {
     h->hlast.alloc(1);
     if (h->B) {
       const size_t BB = (size_t)h->B * h->B;
-      for (DevBuf* b : {&h->ring0, &h->ring1, &h->Y0, &h->Y1, &h->Q0, &h->Q1, &h->P}) b->alloc(BB);
+      for (DevBuf<>* b : {&h->ring0, &h->ring1, &h->Y0, &h->Y1, &h->Q0, &h->Q1, &h->P}) b->alloc(BB);
       h->part.alloc((size_t)(NM_PASSES + 1) * PART_STRIDE);
       h->done.alloc(1);
     }
-    HIP_TRY(hipMalloc(&h->st, sizeof(State)));
-    HIP_TRY(hipMalloc(&h->gjst, sizeof(State)));
+    h->st.alloc(1);
+    h->gjst.alloc(1);
     return midagma_ldfast_reset(h);
   });
   if (rc != MIDAGMA_OK) {
@@ -1036,8 +1035,8 @@ extern "C" int midagma_ldfast_reset(midagma_ldfast* h) {
     st.ckpt_pending = 1;  // no warm start: the first step runs the Gauss-Jordan chain
     State gj{};
     gj.status = ST_DONE;
-    HIP_TRY(hipMemcpy(h->st, &st, sizeof(State), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(h->gjst, &gj, sizeof(State), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(h->st.p, &st, sizeof(State), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(h->gjst.p, &gj, sizeof(State), hipMemcpyHostToDevice));
     HIP_TRY(hipMemset(h->hlast.p, 0, sizeof(double)));
     if (h->done.p) HIP_TRY(hipMemset(h->done.p, 0, sizeof(double)));
     return MIDAGMA_OK;
@@ -1068,7 +1067,7 @@ extern "C" int midagma_ldfast_enqueue(midagma_ldfast* h, const double* A, int64_
     auto want = [&](int64_t p) { return part < 0 || part == p; };
     if (ex) {  // the Gauss-Jordan chain, ungated
       if (want(0)) {
-        launch_ldfast_begin(h->st, h->gjst, st);
+        launch_ldfast_begin(h->st.p, h->gjst.p, st);
         launch_build_at(A, lda, false, h->A.p, D, d, s, nullptr, nullptr, st);
         launch_gj_prologue(h->A.p, D, D, h->gjw(), nullptr, st);
       }
@@ -1076,24 +1075,24 @@ extern "C" int midagma_ldfast_enqueue(midagma_ldfast* h, const double* A, int64_
         if (want(k + 1)) launch_gj_step(h->A.p, D, D, h->gjw(), nullptr, k, st);
       if (want(K + 1))
         launch_ldfast_post(h->piv.p, d, dls, h_dev, h->A.p, D, Mt_dev, ldm, h->P.p, h->B, h->ring0.p, h->ring1.p,
-                           h->st, h->gjst, h->hlast.p, true, st);
+                           h->st.p, h->gjst.p, h->hlast.p, true, st);
       return MIDAGMA_OK;
     }
     const SeriesWork w = h->sw();
-    if (want(0)) launch_ldfast_resid(A, lda, d, s, h->B, w, h->st, h->gjst, st);
+    if (want(0)) launch_ldfast_resid(A, lda, d, s, h->B, w, h->st.p, h->gjst.p, st);
     // the passes one by one (each its own part: the caller interleaves them)
     for (int p = 1; p <= kLdfastPasses; ++p)
-      if (want(p)) launch_series_pass(h->B, w, h->st, p, st);
+      if (want(p)) launch_series_pass(h->B, w, h->st.p, p, st);
     if (want(kLdfastPasses + 1)) {
-      launch_ldfast_certify(h->P.p, h->B, d, Mt_dev, ldm, h->st, reinterpret_cast<const int*>(h->done.p), h->gjst,
+      launch_ldfast_certify(h->P.p, h->B, d, Mt_dev, ldm, h->st.p, reinterpret_cast<const int*>(h->done.p), h->gjst.p,
                             h->ring0.p, h->ring1.p, st);
       // gated: opened by the certificate.  One launch, the whole Gauss-Jordan chain in one
       // workgroup (bit-identical; slow when open, which the bench window never is): a closed gate
       // costs one launch instead of the chain's 2 + D/32, and that launch also ends the step
       // (ldfast_post's fast-step work in the same workgroup: one dependent launch fewer)
-      const LdfastEnd end{h->piv.p, d, dls, h_dev, Mt_dev, ldm, h->B, h->ring0.p, h->ring1.p, h->st, h->hlast.p,
+      const LdfastEnd end{h->piv.p, d, dls, h_dev, Mt_dev, ldm, h->B, h->ring0.p, h->ring1.p, h->st.p, h->hlast.p,
                           h->counter};
-      launch_gj_inverse_1wg(A, lda, h->A.p, D, d, s, h->gjw(), h->gjst, st, end);
+      launch_gj_inverse_1wg(A, lda, h->A.p, D, d, s, h->gjw(), h->gjst.p, st, end);
     }
     return MIDAGMA_OK;
   });
@@ -1114,7 +1113,7 @@ extern "C" int midagma_ldfast_stats(midagma_ldfast* h, int64_t* steps, int64_t* 
     HIP_TRY(hipSetDevice(h->device));
     HIP_TRY(hipDeviceSynchronize());
     State st{};
-    HIP_TRY(hipMemcpy(&st, h->st, sizeof(State), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(&st, h->st.p, sizeof(State), hipMemcpyDeviceToHost));
     if (steps) *steps = st.iter;
     if (exact_steps) *exact_steps = st.halvings;
     return MIDAGMA_OK;
@@ -1138,24 +1137,9 @@ extern "C" int midagma_logdet_inv_dev(const double* A, int64_t d, int64_t lda, d
     return fail(nullptr, MIDAGMA_E_ARG, "logdet_inv_dev: bad arguments");
   return guarded(nullptr, [&] {
     setup_attributes_once();
-    int dev = 0;
-    HIP_TRY(hipGetDevice(&dev));
     const int64_t D = round_up64(d);
     std::lock_guard<std::mutex> lock(g_ws_mu);
-    LogdetWorkspace* ws = nullptr;
-    for (auto* w : g_ws)
-      if (w->device == dev && w->D == D) ws = w;
-    if (!ws) {
-      ws = new LogdetWorkspace();
-      ws->device = dev;
-      ws->D = D;
-      ws->A.alloc((size_t)D * D);
-      ws->P.alloc(64 * 64);
-      ws->R.alloc((size_t)64 * D);
-      ws->C.alloc((size_t)D * 64);
-      ws->piv.alloc(D);
-      g_ws.push_back(ws);
-    }
+    LogdetWorkspace* ws = logdet_ws(D);
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     launch_build_at(A, lda, false, ws->A.p, D, d, s_dom, nullptr, nullptr, st);
     launch_gj_inverse(ws->A.p, D, D, GJWork{ws->P.p, ws->R.p, ws->C.p, ws->piv.p}, nullptr, st);
@@ -1190,18 +1174,13 @@ extern "C" int midagma_sem_linear(const double* W, int64_t d, int64_t row0, int6
     S = std::min<int64_t>(S, (end - first + 1) & ~int64_t(1));
     S = (S + 1) & ~int64_t(1);
     const size_t nnz = g.pidx.size();
-    struct Raw {
-      void* p = nullptr;
-      ~Raw() {
-        if (p) (void)hipFree(p);
-      }
-    } ints, dbls, xt;
-    const size_t n_int = g.nodes.size() + g.pptr.size() + std::max<size_t>(nnz, 1);
-    HIP_TRY(hipMalloc(&ints.p, n_int * sizeof(int32_t)));
-    HIP_TRY(hipMalloc(&dbls.p, (std::max<size_t>(nnz, 1) + d) * sizeof(double)));
-    HIP_TRY(hipMalloc(&xt.p, static_cast<size_t>(S) * d * sizeof(double)));
-    int32_t* ip = static_cast<int32_t*>(ints.p);
-    double* dp = static_cast<double*>(dbls.p);
+    DevBuf<int32_t> ints;
+    DevBuf<double> dbls, xt;
+    ints.alloc(g.nodes.size() + g.pptr.size() + std::max<size_t>(nnz, 1));
+    dbls.alloc(std::max<size_t>(nnz, 1) + d);
+    xt.alloc(static_cast<size_t>(S) * d);
+    int32_t* ip = ints.p;
+    double* dp = dbls.p;
     SemDev dev{ip, ip + g.nodes.size(), ip + g.nodes.size() + g.pptr.size(), dp, dp + std::max<size_t>(nnz, 1)};
     HIP_TRY(hipMemcpyAsync(ip, g.nodes.data(), g.nodes.size() * sizeof(int32_t), hipMemcpyHostToDevice, st));
     HIP_TRY(hipMemcpyAsync(ip + g.nodes.size(), g.pptr.data(), g.pptr.size() * sizeof(int32_t),
@@ -1216,7 +1195,7 @@ extern "C" int midagma_sem_linear(const double* W, int64_t d, int64_t row0, int6
     for (int64_t a = first; a < end; a += S) {
       const int64_t rows = std::min<int64_t>(S, end - a);
       const int64_t skip = a < row0 ? row0 - a : 0;
-      launch_sem_slab(dev, g.level_off, d, sem_type, seed, a, rows, skip, static_cast<double*>(xt.p), S,
+      launch_sem_slab(dev, g.level_off, d, sem_type, seed, a, rows, skip, xt.p, S,
                       X_dev + (a + skip - row0) * ldx, ldx, st);
     }
     HIP_TRY(hipGetLastError());

@@ -23,36 +23,11 @@
 #include <vector>
 
 #include "../../include/midagma_hip.h"
+#include "devmem.h"
 #include "launch.h"
 #include "slot_sched.h"
 
 namespace midagma {
-
-struct DevBuf {
-  double* p = nullptr;
-  size_t n = 0;
-  double* base = nullptr;  // the allocation (p = base + an offset, alloc_shifted)
-  void alloc(size_t count) {
-    if (count <= n && p && p == base) return;
-    release();
-    HIP_TRY(hipMalloc(&base, std::max<size_t>(count, 1) * sizeof(double)));
-    p = base;
-    n = count;
-  }
-  // count entries starting `off` entries into a fresh allocation (placement experiments)
-  void alloc_shifted(size_t count, size_t off) {
-    if (off == 0) return alloc(count);
-    release();
-    HIP_TRY(hipMalloc(&base, (count + off) * sizeof(double)));
-    p = base + off;
-    n = count;
-  }
-  void release() {
-    if (base) (void)hipFree(base);
-    base = p = nullptr;
-    n = 0;
-  }
-};
 
 // group.hip: the slot graphs of an emulated group (every member on one device, the score sum a
 // fixed-order device sum) are captured over all members' streams at once, and a hand-back clears
@@ -72,17 +47,17 @@ struct midagma_solver {
   // data mode: the inverse runs on a high-priority side stream beside the score GEMMs (it
   // depends on W only); fork / join are events inside the captured slot graph
   hipStream_t side = nullptr;
-  hipEvent_t ev_fork = nullptr, ev_join = nullptr;
+  Event ev_fork, ev_join;
   bool fork_inv = !knob_set("MIDAGMA_EXP_NO_FORK");  // experiment knobs: knobs.h
   std::string err;
 
-  DevBuf W, m, v, Mt, cov, covs, minc, mexc, P, R, C, pivlog, partials, bc_table, zown, scratch, Gtmp, Pstore;
+  DevBuf<> W, m, v, Mt, cov, covs, minc, mexc, P, R, C, pivlog, partials, bc_table, zown, scratch, Gtmp, Pstore;
   // ((-mu) cov)^T: the cov-mode score GEMM reads its A operand k-major (coalesced tile rows)
-  DevBuf covsT;
-  DevBuf npart;  // checkpoint-step norm partials (fused_update -> control)
-  DevBuf l1w;    // float32 W: [0] numpy's float32 L1 sum, then its chunk sums (np_l1_kernel)
+  DevBuf<> covsT;
+  DevBuf<> npart;  // checkpoint-step norm partials (fused_update -> control)
+  DevBuf<> l1w;    // float32 W: [0] numpy's float32 L1 sum, then its chunk sums (np_l1_kernel)
   // cov mode, l2, d <= 64, no trek regularizer: the one-workgroup persistent loop (small.hip)
-  DevBuf scarry, sprev;  // between two small-loop launches: pending norms + warm count, last inverses
+  DevBuf<> scarry, sprev;  // between two small-loop launches: pending norms + warm count, last inverses
   bool use_small = !knob_set("MIDAGMA_EXP_NO_SMALL");
   bool small_tcc = knob("MIDAGMA_EXP_SMALL_TCC", 1) != 0;  // experiments: 0 keeps TCC on the graph slots
   // (the TCC regularizer runs inside it up to d = 32, tcc_blk.h; PST keeps the graph-replayed slots)
@@ -94,56 +69,56 @@ struct midagma_solver {
   // PST trek regularizer (trek.hip)
   TrekCfg tcfg{};
   bool trek_on = false;
-  std::vector<DevBuf> tbufs;  // every D x D work buffer of the regularizer
-  DevBuf tpairs, tsmall, Gtrek, tslices;
-  State* tgates = nullptr;
-  State* d_state_probe = nullptr;  // RUNNING + checkpoint: gates the API-call (midagma_trek) path
+  std::vector<DevBuf<>> tbufs;  // every D x D work buffer of the regularizer
+  DevBuf<> tpairs, tsmall, Gtrek, tslices;
+  DevBuf<State> tgates;
+  DevBuf<State> d_state_probe;  // RUNNING + checkpoint: gates the API-call (midagma_trek) path
   TrekWork tw{};
   // TCC trek regularizer (tcc.hip): trek_tcc selects it; mode / weight live in tcfg as for PST
   bool trek_tcc = false;
   TccCfg ccfg{};
   TccWork cw{};
-  DevBuf cA, cMi, cS, cvec, cpart, cP, cR, cC, cAalt, cPst, cPst1;
-  DevBuf cY0, cY1, cQ0, cQ1, cPb, cPart2, cDone;  // the TCC fast-block inverse's series buffers
-  State* cgates = nullptr;
+  DevBuf<> cA, cMi, cS, cvec, cpart, cP, cR, cC, cAalt, cPst, cPst1;
+  DevBuf<> cY0, cY1, cQ0, cQ1, cPb, cPart2, cDone;  // the TCC fast-block inverse's series buffers
+  DevBuf<State> cgates;
   // cov mode, D >= 256: two-level blocked inverse (blockinv.hip) with the warm-started fast path
   int B2 = 0;
-  DevBuf Malt, Pst2, Pst2b, nmY0, nmY1, nmQ0, nmQ1, nmP, nmPart, nmDone, nmLW, nmLZ, nmLPZ, nmSync;
+  DevBuf<> Malt, Pst2, Pst2b, nmY0, nmY1, nmQ0, nmQ1, nmP, nmPart, nmDone, nmLW, nmLZ, nmLPZ, nmSync;
   // the fast slot's inverse as one dataflow launch (dfinv.hip; experiments build only,
   // MIDAGMA_EXP_DF=1: measured slower than the launch-per-phase inverse)
   bool df_on = false;
 #ifdef MIDAGMA_EXPERIMENTS
-  DevBuf dfA, dfY, dfQ, dfP, dfCtl, dfTasks[2], dfWoff[2], dfStamps;
+  DevBuf<> dfA, dfY, dfQ, dfP, dfCtl, dfTasks[2], dfWoff[2], dfStamps;
   DfWork dfw{};
 #endif
   bool fast_ready = false;  // Pst2 holds the previous slot's outer-block inverses
   double* zbuf = nullptr;  // d x d (+64 tail) score partial; internal or bound
   int64_t zbuf_cap = 0;
   // data mode
-  DevBuf X, Y, Zparts, loss_part, cov_parts;
+  DevBuf<> X, Y, Zparts, loss_part, cov_parts;
   int cov_split = 1;
   int64_t n_local = 0, n_pad = 0, n_global = 0;
   // X^T (D x n_pad), the xw GEMM's A operand in the m-contiguous layout (the X^T Y GEMM reads
   // X itself that way); kept when the device has the room (MIDAGMA_NO_XT disables it)
-  DevBuf XT;
-  DevBuf prepad;  // (experiments: MIDAGMA_EXP_PREPAD_MB)
-  DevBuf IW;  // I - W of the slot, written by build_at for the data-mode X (I - W) GEMM
+  DevBuf<> XT;
+  DevBuf<> prepad;  // (experiments: MIDAGMA_EXP_PREPAD_MB)
+  DevBuf<> IW;  // I - W of the slot, written by build_at for the data-mode X (I - W) GEMM
   bool use_xt = false;
   const double* xw_a() const { return use_xt ? XT.p : X.p; }
   int64_t xw_lda() const { return use_xt ? n_pad : D; }
   int split = 1;
   int sig_split = 1;  // the logistic sigmoid GEMM's serial split-K (launch_gemm; 2: Y holds the partial too)
   int sig_split_force = 0;
-  DevBuf cupart_ctr;  // experiments: launch_gemm_cupart's tile counter
+  DevBuf<> cupart_ctr;  // experiments: launch_gemm_cupart's tile counter
   bool w32 = false;  // midagma_set_w_float32: the reference's float32 W arithmetic (common.h f32r)  // midagma_debug_sig_split: 0 the size rule, 1 never split, 2 split where the shape allows
   int64_t loss_part_count = 0;
 
-  Params* d_params = nullptr;
-  State* d_state = nullptr;
-  CkptRec* d_ckpt = nullptr;
+  DevBuf<Params> d_params;
+  DevBuf<State> d_state;
+  DevBuf<CkptRec> d_ckpt;
   int64_t ckpt_cap = 0;
-  State* h_state = nullptr;  // pinned, 2 snapshots
-  hipEvent_t ev[2] = {nullptr, nullptr};
+  PinBuf<State> h_state;  // 2 snapshots
+  Event ev[2];
 
   double bc_b1 = -1, bc_b2 = -1;
   int64_t bc_len = 0;
@@ -168,8 +143,8 @@ struct midagma_solver {
   void* comm = nullptr;
   int comm_ranks = 1;
   bool inslot_comm = false;  // set while capturing a whole slot
-  DevBuf agree;               // 2 x 4 doubles (double-buffered polls)
-  double* h_agree = nullptr;  // pinned 2 x 4
+  DevBuf<> agree;          // 2 x 4 doubles (double-buffered polls)
+  PinBuf<double> h_agree;  // 2 x 4
   // ABI 11: member of a single-process device group (group.hip).  group: set in an emulated group
   // (its slot graphs are the group's, captured over every member's stream); group_stop: set while a
   // threaded group's minimize runs, raised when another member failed (checked at every poll)
@@ -179,40 +154,14 @@ struct midagma_solver {
     if (group_stop && group_stop->load()) throw std::runtime_error("device group: another member failed");
   }
 
+  // The graphs go before the buffers they name; every buffer and event frees itself afterwards.
   ~midagma_solver() {
     destroy_graphs();
     if (stream) (void)hipStreamSynchronize(stream);
     comm_destroy(comm);
-    agree.release();
-    if (h_agree) (void)hipHostFree(h_agree);
-    for (DevBuf* b : {&W, &m, &v, &Mt, &cov, &covs, &covsT, &minc, &mexc, &P, &R, &C, &pivlog, &partials, &bc_table,
-                      &zown, &scratch, &Gtmp, &X, &Y, &Zparts, &loss_part, &cov_parts, &Pstore, &Malt, &Pst2, &Pst2b,
-                      &nmY0, &nmY1, &nmQ0, &nmQ1, &nmP, &nmPart, &nmDone, &nmLW, &nmLZ, &nmLPZ, &nmSync, &npart, &XT, &IW, &scarry,
-                      &sprev, &cupart_ctr, &l1w, &ctl_ticket, &A0, &prepad})
-      b->release();
-#ifdef MIDAGMA_EXPERIMENTS
-    for (DevBuf* b : {&dfA, &dfY, &dfQ, &dfP, &dfCtl, &dfTasks[0], &dfTasks[1], &dfWoff[0], &dfWoff[1], &dfStamps})
-      b->release();
-#endif
-    for (DevBuf& b : tbufs) b.release();
-    for (DevBuf* b : {&tpairs, &tsmall, &Gtrek, &tslices, &cA, &cMi, &cS, &cvec, &cpart, &cP, &cR, &cC, &cAalt, &cPst,
-                      &cPst1, &cY0, &cY1, &cQ0, &cQ1, &cPb, &cPart2, &cDone})
-      b->release();
-    if (cgates) (void)hipFree(cgates);
-    if (tgates) (void)hipFree(tgates);
-    if (d_state_probe) (void)hipFree(d_state_probe);
-    if (d_params) (void)hipFree(d_params);
-    if (d_state) (void)hipFree(d_state);
-    if (d_ckpt) (void)hipFree(d_ckpt);
-    if (h_state) (void)hipHostFree(h_state);
-    for (auto& e : ev)
-      if (e) (void)hipEventDestroy(e);
     if (own_stream && stream) (void)hipStreamDestroy(stream);
     if (side) (void)hipStreamDestroy(side);
     if (cap) (void)hipStreamDestroy(cap);
-    for (hipEvent_t e : {ev_fork, ev_join})
-      if (e) (void)hipEventDestroy(e);
-    for (hipEvent_t e : la_ev) (void)hipEventDestroy(e);
   }
 
   void destroy_graphs() {
@@ -252,7 +201,8 @@ struct midagma_solver {
   // cov mode at large D, fast slots: the trailing-update look-ahead on two streams (blockinv.hip
   // blocked_inverse_lookahead; experiment knob MIDAGMA_EXP_COV_LA: 1 on, 0 off)
   bool cov_la = knob("MIDAGMA_EXP_COV_LA", 0) != 0;
-  std::vector<hipEvent_t> la_ev;
+  std::vector<Event> la_own;      // the look-ahead's events ...
+  std::vector<hipEvent_t> la_ev;  // ... and their handles as one array (TrailLookAhead)
   // blocked slots enqueued launch by launch instead of replayed graphs (experiment knob
   // MIDAGMA_EXP_EAGER: at large D the host runs far ahead of a multi-ms slot, and cross-stream
   // waits are plain queue barriers instead of graph edges)
@@ -284,25 +234,25 @@ struct midagma_solver {
       // large D, cov mode: the score GEMM (W and cov only) on the main stream beside the inverse
       // on the high-priority side stream, so its tiles fill the CUs the inverse's serial
       // series / panel phases leave idle; joined before anything reads Mt
-      launch_build_at(W.p, D, /*square=*/true, binv_build_target(Mt.p, D, binv()), D, d, 0.0, d_params, d_state,
+      launch_build_at(W.p, D, /*square=*/true, binv_build_target(Mt.p, D, binv()), D, d, 0.0, d_params.p, d_state.p,
                       stream, IW.p);
       HIP_TRY(hipEventRecord(ev_fork, stream));
       HIP_TRY(hipStreamWaitEvent(side, ev_fork, 0));
-      launch_blocked_inverse(Mt.p, D, binv(), fast, gj(), d_state, side, passes, nullptr);
+      launch_blocked_inverse(Mt.p, D, binv(), fast, gj(), d_state.p, side, passes, nullptr);
       HIP_TRY(hipEventRecord(ev_join, side));
-      enqueue_score_cov(zbuf, d_state, /*sum=*/!fast);
+      enqueue_score_cov(zbuf, d_state.p, /*sum=*/!fast);
       HIP_TRY(hipStreamWaitEvent(stream, ev_join, 0));
       gemm_done = true;
     } else if (blocked() && data_fork_fast && side != nullptr && mode == MIDAGMA_MODE_DATA) {
       // small data-mode shard: the blocked inverse (fast or pivoted) on the side stream beside
       // the n x d GEMMs, joined before the update
-      launch_build_at(W.p, D, /*square=*/true, binv_build_target(Mt.p, D, binv()), D, d, 0.0, d_params, d_state,
+      launch_build_at(W.p, D, /*square=*/true, binv_build_target(Mt.p, D, binv()), D, d, 0.0, d_params.p, d_state.p,
                       stream, IW.p);
       HIP_TRY(hipEventRecord(ev_fork, stream));
       HIP_TRY(hipStreamWaitEvent(side, ev_fork, 0));
-      launch_blocked_inverse(Mt.p, D, binv(), fast, gj(), d_state, side, passes, nullptr);
+      launch_blocked_inverse(Mt.p, D, binv(), fast, gj(), d_state.p, side, passes, nullptr);
       HIP_TRY(hipEventRecord(ev_join, side));
-      enqueue_data_partial(W.p, d_state, IW.p);
+      enqueue_data_partial(W.p, d_state.p, IW.p);
       enqueue_slot_allreduce();
       HIP_TRY(hipStreamWaitEvent(stream, ev_join, 0));
       gemm_done = true;
@@ -313,7 +263,7 @@ struct midagma_solver {
       // slot does not change any result
       if (fast && tcc_fast_steps > 0 && trek_on && trek_tcc && tcfg.mode == 2 && 2 * d > 128 &&
           mode == MIDAGMA_MODE_COV) {
-        launch_trek_tcc(W.p, d, D, ccfg, cw, d_state, Gtrek.p, stream, d_state, tcc_fast_steps);
+        launch_trek_tcc(W.p, d, D, ccfg, cw, d_state.p, Gtrek.p, stream, d_state.p, tcc_fast_steps);
         trek_done = true;
       }
       // cov fast slot: the score GEMM rides in the last trailing update's launch (its split-K
@@ -329,27 +279,27 @@ struct midagma_solver {
       // slow (pivoted, no warm start) two-level inverse: ~5x fewer workgroup-microseconds
       // taken from the GEMMs than the flat Gauss-Jordan's 32 x 1024 workgroups
       const bool bl = data_binv_on();
-      launch_build_at(W.p, D, /*square=*/true, bl ? binv_build_target(Mt.p, D, binv()) : Mt.p, D, d, 0.0, d_params,
-                      d_state, stream, IW.p);
+      launch_build_at(W.p, D, /*square=*/true, bl ? binv_build_target(Mt.p, D, binv()) : Mt.p, D, d, 0.0, d_params.p,
+                      d_state.p, stream, IW.p);
       HIP_TRY(hipEventRecord(ev_fork, stream));
       HIP_TRY(hipStreamWaitEvent(side, ev_fork, 0));
       if (bl)
-        launch_blocked_inverse(Mt.p, D, binv(), /*fast=*/false, gj(), d_state, side);
+        launch_blocked_inverse(Mt.p, D, binv(), /*fast=*/false, gj(), d_state.p, side);
       else
-        launch_gj_inverse(Mt.p, D, D, gj(), d_state, side);
+        launch_gj_inverse(Mt.p, D, D, gj(), d_state.p, side);
       HIP_TRY(hipEventRecord(ev_join, side));
     } else {
-      launch_build_at(W.p, D, /*square=*/true, Mt.p, D, d, 0.0, d_params, d_state, stream, IW.p);
-      launch_gj_inverse(Mt.p, D, D, gj(), d_state, stream);
+      launch_build_at(W.p, D, /*square=*/true, Mt.p, D, d, 0.0, d_params.p, d_state.p, stream, IW.p);
+      launch_gj_inverse(Mt.p, D, D, gj(), d_state.p, stream);
     }
     // (a fork/join of the score GEMMs onto a second stream inside the graph measured slower:
     // the cross-queue dependencies cost more than the overlap gains)
     if (mode == MIDAGMA_MODE_COV) {
       // rhs = ((-mu) cov) @ (I - W)    (linear.py:244); a fast slot leaves the split-K slices
       // for fused_update to sum (its only reader there)
-      if (!gemm_done) enqueue_score_cov(zbuf, d_state, /*sum=*/!(fast && blocked()));
+      if (!gemm_done) enqueue_score_cov(zbuf, d_state.p, /*sum=*/!(fast && blocked()));
     } else if (!gemm_done) {
-      enqueue_data_partial(W.p, d_state, IW.p);
+      enqueue_data_partial(W.p, d_state.p, IW.p);
       enqueue_slot_allreduce();  // beside the forked inverse, before the join
       if (forked_inverse()) HIP_TRY(hipStreamWaitEvent(stream, ev_join, 0));
     }
@@ -357,9 +307,9 @@ struct midagma_solver {
     // mode only checkpoint slots, which are never fast slots
     if (trek_on && !trek_done && (tcfg.mode == 2 || !(fast && blocked()))) {
       if (trek_tcc)
-        launch_trek_tcc(W.p, d, D, ccfg, cw, d_state, Gtrek.p, stream);
+        launch_trek_tcc(W.p, d, D, ccfg, cw, d_state.p, Gtrek.p, stream);
       else
-        launch_trek_pst(W.p, d, D, tcfg, tw, d_state, Gtrek.p, stream);
+        launch_trek_pst(W.p, d, D, tcfg, tw, d_state.p, Gtrek.p, stream);
     }
   }
 
@@ -372,13 +322,14 @@ struct midagma_solver {
   // every rank's (status, iters) at a poll: one max all-reduce into agree[slot], copied to h_agree
   void enqueue_agree(int slot) {
     if (!comm) return;
-    launch_agree_pack(d_state, agree.p + 4 * slot, stream);
+    launch_agree_pack(d_state.p, agree.p + 4 * slot, stream);
     comm_allreduce(comm, agree.p + 4 * slot, 4, true, stream);
-    HIP_TRY(hipMemcpyAsync(h_agree + 4 * slot, agree.p + 4 * slot, 4 * sizeof(double), hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipMemcpyAsync(h_agree.p + 4 * slot, agree.p + 4 * slot, 4 * sizeof(double), hipMemcpyDeviceToHost,
+                           stream));
   }
   void check_agree(int slot) const {
     if (!comm) return;
-    const double* a = h_agree + 4 * slot;
+    const double* a = h_agree.p + 4 * slot;
     if (a[0] != -a[2] || a[1] != -a[3])
       throw std::runtime_error("data-parallel replicas diverged: (status, iters) ranges over ranks [" +
                                std::to_string(-a[2]) + ", " + std::to_string(a[0]) + "], [" + std::to_string(-a[3]) +
@@ -391,8 +342,8 @@ struct midagma_solver {
   bool enqueue_build_inverse(bool fast, int passes, const GemmSpec* fuse = nullptr) {
 #ifdef MIDAGMA_EXPERIMENTS
     if (fast && df_on) {
-      launch_build_at(W.p, D, /*square=*/true, dfw.A[0], D, d, 0.0, d_params, d_state, stream, IW.p);
-      launch_df_inverse(Mt.p, D, dfw, binv(), passes <= 2 ? 2 : 3, d_state, stream);
+      launch_build_at(W.p, D, /*square=*/true, dfw.A[0], D, d, 0.0, d_params.p, d_state.p, stream, IW.p);
+      launch_df_inverse(Mt.p, D, dfw, binv(), passes <= 2 ? 2 : 3, d_state.p, stream);
       return false;
     }
 #endif
@@ -402,27 +353,25 @@ struct midagma_solver {
 #ifdef MIDAGMA_EXPERIMENTS
     const bool resid0 = fast && IW.p == nullptr && binv_block(D) == 256 && !cov_la_on() && build_resid0_on();
     if (resid0)
-      launch_build_resid0(W.p, D, binv_build_target(Mt.p, D, binv()), D, d, d_params, binv(), d_state, stream);
+      launch_build_resid0(W.p, D, binv_build_target(Mt.p, D, binv()), D, d, d_params.p, binv(), d_state.p, stream);
     else
 #else
     const bool resid0 = false;
 #endif
     if (!ain0)
-      launch_build_at(W.p, D, /*square=*/true, binv_build_target(Mt.p, D, binv()), D, d, 0.0, d_params, d_state,
+      launch_build_at(W.p, D, /*square=*/true, binv_build_target(Mt.p, D, binv()), D, d, 0.0, d_params.p, d_state.p,
                       stream, IW.p);
     if (fast && cov_la_on()) {
       const int64_t K2 = D / B2;
-      if ((int64_t)la_ev.size() < 2 * K2 + 2) {
-        for (size_t i = la_ev.size(); i < (size_t)(2 * K2 + 2); ++i) {
-          hipEvent_t e = nullptr;
-          HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-          la_ev.push_back(e);
-        }
+      while ((int64_t)la_ev.size() < 2 * K2 + 2) {
+        la_own.emplace_back();
+        la_own.back().create(hipEventDisableTiming);
+        la_ev.push_back(la_own.back());
       }
       const TrailLookAhead tla{side, la_ev.data()};
-      return launch_blocked_inverse(Mt.p, D, binv(), fast, gj(), d_state, stream, passes, fuse, &tla, false, ain0);
+      return launch_blocked_inverse(Mt.p, D, binv(), fast, gj(), d_state.p, stream, passes, fuse, &tla, false, ain0);
     }
-    return launch_blocked_inverse(Mt.p, D, binv(), fast, gj(), d_state, stream, passes, fuse, nullptr, resid0, ain0);
+    return launch_blocked_inverse(Mt.p, D, binv(), fast, gj(), d_state.p, stream, passes, fuse, nullptr, resid0, ain0);
   }
 #ifdef MIDAGMA_EXPERIMENTS
   // experiment knob MIDAGMA_EXP_BUILD_RESID0=1: build_at and block 0's residual in one launch
@@ -439,7 +388,7 @@ struct midagma_solver {
   // workgroups of 8 rows x 256 columns), 2048 -1.2 %; on for 1024 <= D <= 1408 (-1: that rule)
   long at_fold_knob = knob("MIDAGMA_EXP_AT_FOLD", -1);
   bool at_fold = at_fold_knob > 0;
-  DevBuf A0;
+  DevBuf<> A0;
   bool at_fold_on() const {
     if (!at_fold || !A0.p || cov_fork_on()) return false;
 #ifdef MIDAGMA_EXPERIMENTS
@@ -468,7 +417,7 @@ struct midagma_solver {
   // (profiles/r06_probe_tccfastblk.log): 1.83 -> 1.40 ms a step after 1300 steps; from W = 0, where
   // the warm starts are poor, 8.0 -> 10.4 ms over the first 30-odd steps
   bool tcc_fastblk = knob("MIDAGMA_EXP_TCC_FASTBLK", 1) != 0;
-  DevBuf ctl_ticket;
+  DevBuf<> ctl_ticket;
 
   // The product's GEMMs, each described once (launch.h GemmSpec).
   // out = op(Cm) @ (I - W) on the d x d problem, split-K over cov_split fixed slices (in
@@ -483,7 +432,7 @@ struct midagma_solver {
   GemmSpec score_cov_spec() const {
     GemmSpec gs = cov_spec(covsT.p, true, IW.p ? IW.p : W.p, IW.p ? B_PLAIN : B_IMINUS);
     if (ctl_fold && ctl_ticket.p) {
-      gs.ctl_pr = d_params;
+      gs.ctl_pr = d_params.p;
       gs.ctl_table = bc_table.p;
       gs.ctl_ticket = reinterpret_cast<int*>(ctl_ticket.p);
     }
@@ -552,27 +501,27 @@ struct midagma_solver {
   // score slices are summed inside fused_update; fast slots never carry a checkpoint
   void enqueue_part2(bool fast = false) {
     const bool lean = fast && blocked();
-    if (!lean) launch_reduce_check(Mt.p, W.p, zbuf, d_params, d_state, partials.p, d, D, stream);
+    if (!lean) launch_reduce_check(Mt.p, W.p, zbuf, d_params.p, d_state.p, partials.p, d, D, stream);
     // float32 W: numpy's float32 L1 sum for the checkpoint objective (np_sum.h; checkpoint slots
     // are never lean)
     const bool l1f = w32 && l1w.p && !lean;
-    if (l1f) launch_np_l1(W.p, d, D, d_state, reinterpret_cast<float*>(l1w.p + 1), l1w.p, stream);
+    if (l1f) launch_np_l1(W.p, d, D, d_state.p, reinterpret_cast<float*>(l1w.p + 1), l1w.p, stream);
     if (!(lean && ctl_folded))  // (else decided at the end of the slot's last trailing launch)
-      launch_control(d_params, d_state, partials.p, pivlog.p, zbuf + D * D, bc_table.p, d_ckpt, ckpt_cap, npart.p, d,
-                     trek_on ? (trek_tcc ? cw.scal : tw.scal) : nullptr, stream, l1f ? l1w.p : nullptr);
+      launch_control(d_params.p, d_state.p, partials.p, pivlog.p, zbuf + D * D, bc_table.p, d_ckpt.p, ckpt_cap,
+                     npart.p, d, trek_on ? (trek_tcc ? cw.scal : tw.scal) : nullptr, stream, l1f ? l1w.p : nullptr);
     const bool slices = lean && mode == MIDAGMA_MODE_COV && cov_split > 1;
     const double* trek = trek_on && tcfg.mode == 2 ? Gtrek.p : nullptr;
     if (lean && at_fold_on()) {  // the next slot's build_at in the update
-      launch_fused_update_at(d_params, d_state, W.p, m.p, v.p, Mt.p, slices ? cov_parts.p : zbuf, slices ? cov_split : 1,
-                             D * D, cov.p, has_inc ? minc.p : nullptr, has_exc ? mexc.p : nullptr, trek, d, D, A0.p,
-                             IW.p, npart.p, stream);
+      launch_fused_update_at(d_params.p, d_state.p, W.p, m.p, v.p, Mt.p, slices ? cov_parts.p : zbuf,
+                             slices ? cov_split : 1, D * D, cov.p, has_inc ? minc.p : nullptr,
+                             has_exc ? mexc.p : nullptr, trek, d, D, A0.p, IW.p, npart.p, stream);
       return;
     }
-    launch_fused_update(d_params, d_state, W.p, m.p, v.p, Mt.p, slices ? cov_parts.p : zbuf,
+    launch_fused_update(d_params.p, d_state.p, W.p, m.p, v.p, Mt.p, slices ? cov_parts.p : zbuf,
                         slices ? cov_split : 1, D * D, cov.p, has_inc ? minc.p : nullptr, has_exc ? mexc.p : nullptr,
                         trek, d, D, npart.p, stream);
     if (blocked() && at_fold_on())  // slow slot: the next (fast) slot's A^T and I - W from the new W
-      launch_build_at(W.p, D, /*square=*/true, A0.p, D, d, 0.0, d_params, d_state, stream, IW.p);
+      launch_build_at(W.p, D, /*square=*/true, A0.p, D, d, 0.0, d_params.p, d_state.p, stream, IW.p);
   }
 
   // Slot graphs are captured on a stream of the solver's own and launched on `stream`: a caller
@@ -669,9 +618,9 @@ struct midagma_solver {
     w.part = tsmall.p + (D / 64) * D;
     w.scal = w.part + 4 * 256;
     HIP_TRY(hipMemsetAsync(tsmall.p, 0, tsmall.n * sizeof(double), stream));
-    if (!tgates) HIP_TRY(hipMalloc(&tgates, (1 + 2 * TREK_SMAX) * sizeof(State)));
-    HIP_TRY(hipMemsetAsync(tgates, 0, (1 + 2 * TREK_SMAX) * sizeof(State), stream));
-    w.gates = tgates;
+    tgates.alloc(1 + 2 * TREK_SMAX);
+    HIP_TRY(hipMemsetAsync(tgates.p, 0, (1 + 2 * TREK_SMAX) * sizeof(State), stream));
+    w.gates = tgates.p;
     Gtrek.alloc(DD);
     HIP_TRY(hipMemsetAsync(Gtrek.p, 0, DD * sizeof(double), stream));
     std::vector<int32_t> pr(2 * mpairs);
@@ -700,12 +649,12 @@ struct midagma_solver {
   }
 
   void ensure_probe() {
-    if (!d_state_probe) {
-      HIP_TRY(hipMalloc(&d_state_probe, sizeof(State)));
+    if (!d_state_probe.p) {
+      d_state_probe.alloc(1);
       State probe{};
       probe.status = ST_RUNNING;
       probe.ckpt_pending = 1;
-      HIP_TRY(hipMemcpy(d_state_probe, &probe, sizeof(State), hipMemcpyHostToDevice));
+      HIP_TRY(hipMemcpy(d_state_probe.p, &probe, sizeof(State), hipMemcpyHostToDevice));
     }
   }
 
@@ -735,8 +684,8 @@ struct midagma_solver {
     cC.alloc((size_t)2 * D2 * 32);
     HIP_TRY(hipMemcpy(cS.p, S.data(), S.size() * sizeof(double), hipMemcpyHostToDevice));
     HIP_TRY(hipMemset(cvec.p, 0, cvec.n * sizeof(double)));  // warm flag off, vectors 0
-    if (!cgates) HIP_TRY(hipMalloc(&cgates, TCC_GATES * sizeof(State)));
-    HIP_TRY(hipMemset(cgates, 0, TCC_GATES * sizeof(State)));
+    cgates.alloc(TCC_GATES);
+    HIP_TRY(hipMemset(cgates.p, 0, TCC_GATES * sizeof(State)));
     TccWork w{};
     w.gj = GJWork{cP.p, cR.p, cC.p, nullptr, nullptr};
     w.D2 = D2;
@@ -750,7 +699,7 @@ struct midagma_solver {
     }
     w.scal = v;
     w.part = cpart.p;
-    w.gates = cgates;
+    w.gates = cgates.p;
     w.fix = tcc_fix != 0 ? 1 : 0;
     w.fix_pre = tcc_fix_pre;
     w.fix_hold = tcc_fix_hold;
@@ -771,7 +720,7 @@ struct midagma_solver {
       // fast slots: every outer block but the last on the product-form series (tcc.hip
       // tcc_inverse_fix; MIDAGMA_EXP_TCC_FASTBLK=0 off); one warm-start slot (Pst1 = Pst)
       if (tcc_fastblk) {
-        for (DevBuf* b : {&cY0, &cY1, &cQ0, &cQ1, &cPb}) b->alloc((size_t)b2 * b2);
+        for (DevBuf<>* b : {&cY0, &cY1, &cQ0, &cQ1, &cPb}) b->alloc((size_t)b2 * b2);
         cPart2.alloc((size_t)(D2 / b2) * (NM_PASSES + 1) * PART_STRIDE);
         cDone.alloc((size_t)(D2 / b2));
         HIP_TRY(hipMemset(cPst.p, 0, (size_t)D2 * b2 * sizeof(double)));
@@ -802,7 +751,7 @@ struct midagma_solver {
   // ---- buffers -------------------------------------------------------------
   void alloc_core() {
     const size_t DD = (size_t)D * D;
-    for (DevBuf* b : {&W, &m, &v, &Mt, &cov, &covs, &covsT}) {
+    for (DevBuf<>* b : {&W, &m, &v, &Mt, &cov, &covs, &covsT}) {
       b->alloc(DD);
       HIP_TRY(hipMemsetAsync(b->p, 0, DD * sizeof(double), stream));
     }
@@ -853,11 +802,15 @@ struct midagma_solver {
       Malt.alloc(DD);
       Pst2.alloc((size_t)D * b2);
       Pst2b.alloc((size_t)D * b2);
-      for (DevBuf* b : {&nmY0, &nmY1, &nmQ0, &nmQ1, &nmP, &nmLW, &nmLZ, &nmLPZ}) b->alloc((size_t)b2 * b2);
+      for (DevBuf<>* b : {&nmY0, &nmY1, &nmQ0, &nmQ1, &nmP, &nmLW, &nmLZ, &nmLPZ}) b->alloc((size_t)b2 * b2);
       nmPart.alloc((size_t)(D / b2) * (NM_PASSES + 1) * PART_STRIDE);
       nmDone.alloc(D / b2);
       nmSync.alloc((size_t)(D / b2) * 128);  // 256 ints per block (launch_trail128_series' counters)
-      HIP_TRY(hipMemsetAsync(nmSync.p, 0, (size_t)(D / b2) * 128 * sizeof(double), stream));
+      // the counters must start at 0; the others so that no slot's result depends on what the
+      // memory held before (which buffer a solver gets back follows the order of earlier frees)
+      for (DevBuf<>* b : {&nmSync, &Malt, &Pst2, &Pst2b, &nmY0, &nmY1, &nmQ0, &nmQ1, &nmP, &nmLW, &nmLZ, &nmLPZ,
+                          &nmPart, &nmDone})
+        HIP_TRY(hipMemsetAsync(b->p, 0, b->n * sizeof(double), stream));
     }
 #ifdef MIDAGMA_EXPERIMENTS
     if (blocked() && mode == MIDAGMA_MODE_COV && df_available(D) && knob("MIDAGMA_EXP_DF", 0) != 0) setup_df();
@@ -866,10 +819,10 @@ struct midagma_solver {
     HIP_TRY(hipMemsetAsync(zown.p, 0, (DD + 64) * sizeof(double), stream));
     zbuf = zown.p;
     zbuf_cap = (int64_t)DD + 64;
-    HIP_TRY(hipMalloc(&d_params, sizeof(Params)));
-    HIP_TRY(hipMalloc(&d_state, sizeof(State)));
-    HIP_TRY(hipHostMalloc(&h_state, 2 * sizeof(State), hipHostMallocDefault));
-    for (auto& e : ev) HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    d_params.alloc(1);
+    d_state.alloc(1);
+    h_state.alloc(2);
+    for (Event& e : ev) e.create(hipEventDisableTiming);
     if ((mode == MIDAGMA_MODE_DATA && fork_inv) ||
         (mode == MIDAGMA_MODE_COV && (cov_fork || cov_la) && B2 > 0 && (D - B2 >= 1792 || cov_fork_all))) {
       // Default priority: a fork / join between a high-priority stream and another one left the
@@ -878,8 +831,8 @@ struct midagma_solver {
       // and the forked inverse hides just as well without it (config 4: 17.46 vs 17.50 steps/s
       // at n = 1e6, 133.8 vs 133.5 at the 8-GPU shard n = 125k)
       HIP_TRY(hipStreamCreateWithFlags(&side, hipStreamNonBlocking));
-      HIP_TRY(hipEventCreateWithFlags(&ev_fork, hipEventDisableTiming));
-      HIP_TRY(hipEventCreateWithFlags(&ev_join, hipEventDisableTiming));
+      ev_fork.create(hipEventDisableTiming);
+      ev_join.create(hipEventDisableTiming);
       if (kExperiments) cupart_ctr.alloc(1);  // (launch_gemm_cupart's counter; not while capturing)
     }
   }
@@ -933,7 +886,7 @@ struct midagma_solver {
   int df_timeouts() { return 0; }
 #endif
 
-  void upload_matrix(DevBuf& dst, const double* src, int64_t ld_src) {
+  void upload_matrix(DevBuf<>& dst, const double* src, int64_t ld_src) {
     HIP_TRY(hipMemcpy2DAsync(dst.p, D * sizeof(double), src, ld_src * sizeof(double), d * sizeof(double), d,
                              hipMemcpyHostToDevice, stream));
   }
@@ -962,8 +915,7 @@ struct midagma_solver {
   void ensure_ckpt(int64_t max_iter, int64_t checkpoint) {
     const int64_t need = max_iter / std::max<int64_t>(checkpoint, 1) + 4;
     if (need <= ckpt_cap) return;
-    if (d_ckpt) HIP_TRY(hipFree(d_ckpt));
-    HIP_TRY(hipMalloc(&d_ckpt, need * sizeof(CkptRec)));
+    d_ckpt.alloc(need);
     ckpt_cap = need;
     graphs_valid = false;
   }
@@ -1016,20 +968,20 @@ struct midagma_solver {
       p.logit_scale = 1.0 / n;
     }
     hp = p;
-    HIP_TRY(hipMemcpyAsync(d_params, &hp, sizeof(Params), hipMemcpyHostToDevice, stream));
+    HIP_TRY(hipMemcpyAsync(d_params.p, &hp, sizeof(Params), hipMemcpyHostToDevice, stream));
     State st{};
     st.status = ST_RUNNING;
     st.lr = lr;
     st.obj_prev = 1e16;
-    h_state[0] = st;
-    HIP_TRY(hipMemcpyAsync(d_state, &h_state[0], sizeof(State), hipMemcpyHostToDevice, stream));
+    h_state.p[0] = st;
+    HIP_TRY(hipMemcpyAsync(d_state.p, &h_state.p[0], sizeof(State), hipMemcpyHostToDevice, stream));
     if (mode == MIDAGMA_MODE_COV) {
       launch_scale(cov.p, -mu_, covs.p, D * D, stream);  // (-mu) * cov
       launch_transpose(covs.p, D, D, D, covsT.p, D, stream);
     }
     upload_matrix(W, Wh, d);
     const size_t DD = (size_t)D * D;
-    for (DevBuf* b : {&m, &v}) HIP_TRY(hipMemsetAsync(b->p, 0, DD * sizeof(double), stream));
+    for (DevBuf<>* b : {&m, &v}) HIP_TRY(hipMemsetAsync(b->p, 0, DD * sizeof(double), stream));
     HIP_TRY(hipMemsetAsync(scarry.p, 0, scarry.n * sizeof(double), stream));  // no warm start yet
     HIP_TRY(hipStreamSynchronize(stream));  // h_state[0] reused as a snapshot slot below
     fast_ready = false;  // the first slot of a call runs the GJ path (warm starts are stale)
@@ -1038,7 +990,7 @@ struct midagma_solver {
   }
 
   void snapshot(int slot) {
-    HIP_TRY(hipMemcpyAsync(&h_state[slot], d_state, sizeof(State), hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipMemcpyAsync(&h_state.p[slot], d_state.p, sizeof(State), hipMemcpyDeviceToHost, stream));
     HIP_TRY(hipEventRecord(ev[slot], stream));
   }
 
@@ -1056,9 +1008,9 @@ struct midagma_solver {
     carry.three_pass_left = three_pass_left;
     carry.fast_ready = fast_ready;
     BlockedScheduler sc(hp.max_iter, hp.checkpoint, n_slots, fast_group, g_fast2 != nullptr, carry);
-    HIP_TRY(hipMemcpyAsync(&h_state[1], d_state, sizeof(State), hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipMemcpyAsync(&h_state.p[1], d_state.p, sizeof(State), hipMemcpyDeviceToHost, stream));
     HIP_TRY(hipStreamSynchronize(stream));
-    for (SlotView cur = view(h_state[1]);;) {
+    for (SlotView cur = view(h_state.p[1]);;) {
       const BlockedPlan p = sc.next(cur);
       if (p.done) break;
       if (p.clear_handback) {
@@ -1066,7 +1018,7 @@ struct midagma_solver {
         if (group)
           group_clear_handback(group);
         else
-          HIP_TRY(hipMemcpyAsync(&d_state->status, &running, sizeof(int32_t), hipMemcpyHostToDevice, stream));
+          HIP_TRY(hipMemcpyAsync(&d_state.p->status, &running, sizeof(int32_t), hipMemcpyHostToDevice, stream));
       }
       if (eager) {
         if (p.slow) run_eager(false, NM_PASSES_RUN, 1);
@@ -1078,12 +1030,12 @@ struct midagma_solver {
         for (int64_t b = 0; b < p.groups; ++b) HIP_TRY(hipGraphLaunch(grp, stream));
         for (int64_t b = 0; b < p.singles; ++b) HIP_TRY(hipGraphLaunch(one, stream));
       }
-      HIP_TRY(hipMemcpyAsync(&h_state[1], d_state, sizeof(State), hipMemcpyDeviceToHost, stream));
+      HIP_TRY(hipMemcpyAsync(&h_state.p[1], d_state.p, sizeof(State), hipMemcpyDeviceToHost, stream));
       enqueue_agree(0);
       HIP_TRY(hipStreamSynchronize(stream));
       check_agree(0);
       check_group_stop();
-      cur = view(h_state[1]);
+      cur = view(h_state.p[1]);
       sc.observe(cur);
     }
     fast_batch = sc.carry().bmax;
@@ -1119,13 +1071,13 @@ struct midagma_solver {
       if (trek_on && trek_tcc)
         tc = SmallTcc{cw.S, ccfg.w, ccfg.eps, (double)ccfg.m, ccfg.weight, ccfg.mode, cw.scal, cw.vprev, cw.uprev,
                       cw.fix};
-      launch_small_minimize(d_params, d_state, W.p, m.p, v.p, covs.p, has_inc ? minc.p : nullptr,
-                            has_exc ? mexc.p : nullptr, bc_table.p, d_ckpt, ckpt_cap, scarry.p, sprev.p, d, B,
+      launch_small_minimize(d_params.p, d_state.p, W.p, m.p, v.p, covs.p, has_inc ? minc.p : nullptr,
+                            has_exc ? mexc.p : nullptr, bc_table.p, d_ckpt.p, ckpt_cap, scarry.p, sprev.p, d, B,
                             stream, trek_on && trek_tcc ? &tc : nullptr, w32);
       launched += B;
-      HIP_TRY(hipMemcpyAsync(&h_state[1], d_state, sizeof(State), hipMemcpyDeviceToHost, stream));
+      HIP_TRY(hipMemcpyAsync(&h_state.p[1], d_state.p, sizeof(State), hipMemcpyDeviceToHost, stream));
       HIP_TRY(hipStreamSynchronize(stream));
-      if (terminal(h_state[1])) break;
+      if (terminal(h_state.p[1])) break;
     }
   }
 
@@ -1153,8 +1105,8 @@ struct midagma_solver {
         HIP_TRY(hipEventSynchronize(ev[pending]));
         check_agree(pending);
         check_group_stop();
-        known_iter = h_state[pending].iter;
-        if (terminal(h_state[pending])) stop = true;
+        known_iter = h_state.p[pending].iter;
+        if (terminal(h_state.p[pending])) stop = true;
       }
       pending = cur;
       cur ^= 1;
@@ -1164,12 +1116,12 @@ struct midagma_solver {
   }
 
   void finish(double* Wh, midagma_result* res) {
-    HIP_TRY(hipMemcpyAsync(&h_state[0], d_state, sizeof(State), hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipMemcpyAsync(&h_state.p[0], d_state.p, sizeof(State), hipMemcpyDeviceToHost, stream));
     download_matrix(Wh, W.p);
     HIP_TRY(hipStreamSynchronize(stream));
     begun = false;
-    check_handoff(h_state[0]);
-    fill_result(h_state[0], res);
+    check_handoff(h_state.p[0]);
+    fill_result(h_state.p[0], res);
   }
 
   // the serial split sigmoid GEMM's per-tile hand-off words (gemm.hip, sig_split_take): after the
