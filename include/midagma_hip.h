@@ -421,6 +421,38 @@ int midagma_indep_profile(const midagma_indep* h, double* ms_out);
 int midagma_indep_run(midagma_indep* h, int kind, const int64_t* pairs, int64_t m, int64_t P, const int32_t* perms,
                       uint64_t seed, int64_t budget_bytes, double* stat, int64_t* ge, double* null_out,
                       int32_t* perms_out);
+
+/* A batch of B independent small-d problems (1 <= d <= 64, l2, cov mode, float64 W, no trek
+ * regularizer) that share d, the device and the loop settings and each have their own covariance,
+ * lambda1, mu, s and lr: one launch of the small-d persistent loop runs them with one workgroup per
+ * problem, so bootstrap resamples, a lambda1 grid or a table over seeds fill the device instead of
+ * one compute unit.  Purely additive: MIDAGMA_ABI_VERSION stays 11.
+ * Problem b's W, result and checkpoint records are bit-identical to what a cov-mode l2
+ * midagma_solver gives for that problem alone with the same arguments.
+ * Every entry checks its arguments before it touches a device (MIDAGMA_E_ARG); the message comes
+ * from midagma_batch_last_error(handle) (or (NULL) for errors raised without a handle).  A handle
+ * owns one stream and its device and pinned buffers; one host thread drives it at a time.
+ * create: 1 <= d <= 64, 1 <= B <= 16384.
+ * set_cov: host B x d x d row-major, copied; MIDAGMA_E_ARG on inf/nan.
+ * set_masks: host B x d x d each, or NULL to switch that mask off (as midagma_set_masks).
+ * minimize: W is B x d x d host, in/out; mu, s_dom, lr, lambda1 hold B values each; res holds B
+ *   results.  active (B bytes, NULL: all): a problem whose byte is 0 does not run, and its W and
+ *   res entry are left untouched.  The host relaunches only the problems still running, so a
+ *   finished problem costs nothing afterwards.  A problem that ends MIDAGMA_ST_SINGULAR (or any
+ *   other status) reports it in res[b].status and the call returns MIDAGMA_OK.  MIDAGMA_E_ARG:
+ *   max_iter < 1, checkpoint < 1, a null pointer, a non-finite active W, a call before set_cov.
+ * checkpoints: the records of problem b from the last minimize call (0 when b was inactive in
+ *   it), at most cap; returns their number. */
+typedef struct midagma_batch midagma_batch;
+int midagma_batch_create(midagma_batch** out, int64_t d, int64_t B, int device);
+void midagma_batch_destroy(midagma_batch* h);
+const char* midagma_batch_last_error(const midagma_batch* h);
+int midagma_batch_set_cov(midagma_batch* h, const double* cov);
+int midagma_batch_set_masks(midagma_batch* h, const double* mask_inc, const double* mask_exc);
+int midagma_batch_minimize(midagma_batch* h, double* W, const double* mu, const double* s_dom, const double* lr,
+                           const double* lambda1, int64_t max_iter, double tol, double beta1, double beta2,
+                           int64_t checkpoint, const uint8_t* active, midagma_result* res);
+int64_t midagma_batch_checkpoints(midagma_batch* h, int64_t b, midagma_ckpt* out, int64_t cap);
 #ifdef __cplusplus
 }
 #endif

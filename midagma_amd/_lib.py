@@ -148,6 +148,15 @@ EXPORTED = {
     "midagma_indep_batch_pairs": (_i64, [_vp, _i64, _i64]),
     "midagma_indep_profile": (_int, [_vp, _dp]),
     "midagma_indep_run": (_int, [_vp, _int, _vp, _i64, _i64, _vp, C.c_uint64, _i64, _dp, _vp, _dp, _vp]),
+    # additive to ABI 11: a batch of small-d problems, one workgroup each (midagma_amd.solver.HipBatch)
+    "midagma_batch_create": (_int, [C.POINTER(_vp), _i64, _i64, _int]),
+    "midagma_batch_destroy": (None, [_vp]),
+    "midagma_batch_last_error": (C.c_char_p, [_vp]),
+    "midagma_batch_set_cov": (_int, [_vp, _dp]),
+    "midagma_batch_set_masks": (_int, [_vp, _dp, _dp]),
+    "midagma_batch_minimize": (_int, [_vp, _dp, _dp, _dp, _dp, _dp, _i64, _d, _d, _d, _i64, _vp,
+                                      C.POINTER(MidagmaResult)]),
+    "midagma_batch_checkpoints": (_i64, [_vp, _i64, C.POINTER(MidagmaCkpt), _i64]),
 }
 
 GROUP_EMULATE = 1

@@ -1,0 +1,211 @@
+"""`DagmaLinearBatch`: many small-d DAGMA fits at once, one persistent workgroup per problem.
+
+One l2 fit at d <= 64 runs its whole inner loop in one workgroup, on one compute unit of the
+GPU.  Bootstrap resamples, a `lambda1` grid or a table over seeds and datasets are B such fits;
+this class runs them as one batch (`HipBatch`, csrc/batch.hip) instead of a Python loop over
+`DagmaLinear.fit`:
+
+    W = DagmaLinearBatch().fit([X0, X1, ...], lambda1=0.03)        # (B, d, d)
+    W = DagmaLinearBatch().fit(X, lambda1=[0.01, 0.03, 0.1])       # a lambda1 grid on one X
+
+Problem b returns exactly (bit for bit) what `DagmaLinear("l2").fit(Xs[b].copy(), lambda1[b], ...)`
+returns with the same arguments: the stages of the path-following loop (linear.py:441-453) run
+in lockstep over the problems, and within a stage the problems that have not yet succeeded are
+re-run, each with its own halved lr and enlarged s, until none is left.
+
+Not in the batch: a trek regularizer, float32 W, d > 64, the logistic loss and data mode, several
+devices, a device X.
+"""
+from __future__ import annotations
+
+import time
+import typing
+
+import numpy as np
+
+from . import _lib
+from .solver import HipBatch, HipSolver, is_device_tensor
+
+__all__ = ["DagmaLinearBatch"]
+
+
+def _edges(edges):
+    """(rows, cols) of a tuple of 2-tuples; anything else is ignored, as the reference ignores it
+    (linear.py:416-426)."""
+    if edges is not None and type(edges) is tuple and len(edges) > 0 and type(edges[0]) is tuple and \
+            all(len(e) == 2 for e in edges):
+        return tuple(zip(*edges))
+    return None
+
+
+class DagmaLinearBatch:
+    """B independent `DagmaLinear('l2')` fits with a common d <= 64 on one GPU."""
+
+    def __init__(self, loss_type: str = "l2", verbose: bool = False, dtype: type = np.float64, *,
+                 device: int | None = None, trek_reg=None, batch_factory=None, solver_factory=None) -> None:
+        if loss_type != "l2":
+            raise ValueError("DagmaLinearBatch runs the l2 loss (cov mode) only")
+        if np.dtype(dtype).type is not np.float64:
+            raise ValueError("DagmaLinearBatch runs a float64 W only")
+        if trek_reg is not None and trek_reg.enabled():
+            raise ValueError("DagmaLinearBatch runs no trek regularizer")
+        self.loss_type = loss_type
+        self.dtype = np.float64
+        self.vprint = print if verbose else (lambda *a, **k: None)
+        self.device = 0 if device is None else int(device)
+        # the backends (tests pass CPU doubles): the batch, and one ordinary solver for h / score
+        self._batch_factory = batch_factory or HipBatch
+        self._solver_factory = solver_factory or HipSolver
+        self.minimize_log: list = []
+
+    # ------------------------------------------------------------------ inputs
+    def _problems(self, Xs, lambda1):
+        """(list of B host X, B lambda1 values), checked; no device work."""
+        def host2d(X):
+            if is_device_tensor(X) or hasattr(X, "data_ptr"):
+                raise ValueError("DagmaLinearBatch takes host arrays, not device tensors")
+            if not isinstance(X, np.ndarray) or X.dtype != np.float64 or X.ndim != 2:
+                raise ValueError("every X must be a 2-d float64 host array (n x d)")
+            return X
+
+        lam_seq = None if np.ndim(lambda1) == 0 else [float(x) for x in lambda1]
+        if is_device_tensor(Xs) or hasattr(Xs, "data_ptr"):
+            raise ValueError("DagmaLinearBatch takes host arrays, not device tensors")
+        if isinstance(Xs, np.ndarray) and Xs.ndim == 2:
+            # one X: a lambda1 grid (X centred once, cov formed once, shared by the problems)
+            X = host2d(Xs)
+            xs = [X] * (1 if lam_seq is None else len(lam_seq))
+        elif isinstance(Xs, np.ndarray):
+            if Xs.ndim != 3 or Xs.dtype != np.float64:
+                raise ValueError("Xs must be a sequence of (n_b, d) float64 arrays, a (B, n, d) array or one (n, d) X")
+            xs = [Xs[b] for b in range(Xs.shape[0])]
+        else:
+            xs = [host2d(X) for X in Xs]
+        B = len(xs)
+        if B == 0:
+            raise ValueError("an empty batch")
+        if B > HipBatch.MAX_B:
+            raise ValueError(f"at most {HipBatch.MAX_B} problems in a batch, got {B}")
+        ds = {int(X.shape[1]) for X in xs}
+        if len(ds) != 1:
+            raise ValueError(f"the problems must share d, got {sorted(ds)}")
+        d = ds.pop()
+        if d < 1 or d > HipBatch.MAX_D:
+            raise ValueError(f"DagmaLinearBatch needs 1 <= d <= {HipBatch.MAX_D}, got d = {d}")
+        if any(X.shape[0] < 1 for X in xs):
+            raise ValueError("every X needs at least one row")
+        if lam_seq is None:
+            lam_seq = [lambda1] * B
+        elif len(lam_seq) != B:
+            raise ValueError(f"lambda1 holds {len(lam_seq)} values for {B} problems")
+        return xs, lam_seq, d
+
+    def _masks(self, mu: float, lam, inc, exc, B: int, d: int):
+        """linear.py:217-222 per problem (mask_inc depends on the problem's lambda1)."""
+        mask_inc = mask_exc = None
+        if inc is not None:
+            mask_inc = np.zeros((B, d, d))
+            for b in range(B):
+                mask_inc[b][inc[0], inc[1]] = -2 * mu * lam[b]
+        if exc is not None:
+            mask_exc = np.ones((B, d, d))
+            mask_exc[:, exc[0], exc[1]] = 0.
+        return mask_inc, mask_exc
+
+    # --------------------------------------------------------------------- fit
+    def fit(self, Xs, lambda1: typing.Union[float, typing.Sequence[float]] = 0.03, w_threshold: float = 0.3,
+            T: int = 5, mu_init: float = 1.0, mu_factor: float = 0.1,
+            s: typing.Union[typing.List[float], float] = [1.0, .9, .8, .7, .6],
+            warm_iter: int = 3e4, max_iter: int = 6e4, lr: float = 0.0003, checkpoint: int = 1000,
+            beta_1: float = 0.99, beta_2: float = 0.999,
+            exclude_edges: typing.Optional[typing.Tuple[typing.Tuple[int, int], ...]] = None,
+            include_edges: typing.Optional[typing.Tuple[typing.Tuple[int, int], ...]] = None) -> np.ndarray:
+        """Runs DAGMA (linear.py:335-462) on every problem and returns the thresholded weighted
+        adjacencies, (B, d, d).
+
+        Xs: a sequence of B host float64 arrays (n_b, d) with a common d (the n_b may differ), a
+        (B, n, d) array, or one (n, d) X with `lambda1` a length-B sequence (a lambda1 grid).
+        lambda1: a scalar or a length-B sequence.  The other arguments are `DagmaLinear.fit`'s and
+        shared by the problems.  Every distinct X is centred in place, once, as the reference
+        centres its X; the caller's `s` list is not changed.
+
+        Leaves W_est (B, d, d), h_final (B,), score_final (B,), minimize_log (B lists with
+        `DagmaLinear.minimize_log`'s fields) and fit_timing.  Raises np.linalg.LinAlgError naming
+        the problems whose s I - W o W became singular."""
+        t_start = time.perf_counter()
+        xs, lam, d = self._problems(Xs, lambda1)
+        B, T = len(xs), int(T)
+        if isinstance(s, (list, tuple)):
+            s0 = list(s) + max(0, T - len(s)) * [s[-1]]  # linear.py:431-434
+        elif type(s) in (int, float):
+            s0 = T * [s]
+        else:
+            raise ValueError("s should be a list, int, or float.")
+        inc, exc = _edges(include_edges), _edges(exclude_edges)
+        self.B, self.d, self.lambda1, self.checkpoint = B, d, lam, checkpoint
+        # centring and cov = X^T X / n on the host, once per distinct X (linear.py:411, 428)
+        covs: dict = {}
+        for X in xs:
+            if id(X) not in covs:
+                X -= X.mean(axis=0, keepdims=True)
+                covs[id(X)] = X.T @ X / float(X.shape[0])
+        self.cov = [covs[id(X)] for X in xs]
+        batch = self._batch_factory(d, B, device=self.device)
+        try:
+            batch.set_cov(np.stack(self.cov))
+            t_prep = time.perf_counter()
+            self.W_est = np.zeros((B, d, d))
+            self.minimize_log = [[] for _ in range(B)]
+            s_of = [list(s0) for _ in range(B)]  # each problem enlarges its own s on a failure
+            mu = mu_init
+            for i in range(T):
+                self.vprint(f'\nIteration -- {i+1}:')
+                inner_iters = int(max_iter) if i == T - 1 else int(warm_iter)
+                lr_of = [lr] * B
+                todo = np.ones(B, dtype=bool)
+                batch.set_masks(*self._masks(mu, lam, inc, exc, B, d))
+                while todo.any():
+                    t0 = time.time()
+                    W_try = self.W_est.copy()
+                    s_now = [s_of[b][i] for b in range(B)]
+                    res = batch.minimize(W_try, mu, s_now, lr_of, lam, inner_iters, beta_1=beta_1, beta_2=beta_2,
+                                         checkpoint=checkpoint, active=todo)
+                    seconds = time.time() - t0
+                    singular = [b for b in np.flatnonzero(todo) if res[b].status == _lib.ST_SINGULAR]
+                    if singular:
+                        raise np.linalg.LinAlgError(
+                            f"singular matrix: inverse of sI - W*W is not finite in problems {singular}")
+                    for b in np.flatnonzero(todo):
+                        r = res[b]
+                        self.minimize_log[b].append(dict(mu=mu, s=s_now[b], lr=lr_of[b], max_iter=inner_iters,
+                                                         iters=r.iters, success=r.success, early_stop=r.early_stop,
+                                                         halvings=r.halvings, seconds=seconds))
+                        if r.success:
+                            self.W_est[b] = W_try[b]
+                            todo[b] = False
+                        else:  # this problem alone: a smaller lr and a larger s (linear.py:449-452)
+                            self.vprint(f'problem {b}: W went out of domain for s={s_now[b]} at iteration '
+                                        f'{r.iters + 1}; retrying with larger s')
+                            lr_of[b] *= 0.5
+                            s_of[b][i] += 0.1
+                mu *= mu_factor
+        finally:
+            batch.close()
+        t_loop = time.perf_counter()
+        # h and the score of every problem's W from one ordinary solver: the kernels of the single fit
+        self.h_final, self.score_final = np.empty(B), np.empty(B)
+        solver = self._solver_factory(d, "l2", "cov", device=self.device)
+        try:
+            last = None
+            for b in range(B):
+                if self.cov[b] is not last:
+                    solver.set_cov(self.cov[b])
+                    last = self.cov[b]
+                self.h_final[b], _ = solver.h_value(self.W_est[b], 1.0, grad=True)
+                self.score_final[b], _ = solver.score_value(self.W_est[b])
+        finally:
+            solver.close()
+        self.fit_timing = dict(prep_s=t_prep - t_start, loop_s=t_loop - t_prep,
+                               final_s=time.perf_counter() - t_loop, cov_on="host")
+        self.W_est[np.abs(self.W_est) < w_threshold] = 0
+        return self.W_est

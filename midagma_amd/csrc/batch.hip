@@ -1,0 +1,318 @@
+// A batch of B independent small-d problems (d <= 64, l2, cov mode, float64, no trek regularizer)
+// behind the midagma_batch_* entries of the C ABI: the small-d persistent loop (small.hip) with
+// one workgroup per problem.  Problem b's result is bit-identical to what a midagma_solver gives
+// for that problem alone: the same kernel instantiation runs it, on Params / State / (-mu) cov /
+// W / m / v filled as midagma_solver::begin fills them (solver_impl.h's shared helpers), and the
+// kernel's results do not depend on how the host splits slots over launches.
+//
+// Device layout: every per-problem array of the single solver with a leading problem index
+// (D x D slabs with D = 64, as the single solver pads d <= 64).  The host relaunches only the
+// problems still ST_RUNNING, through a device index list, so a finished problem costs nothing in
+// later launches; workgroups never wait on each other, and a grid beyond the device's residency
+// queues.
+#include <hip/hip_runtime.h>
+
+#include <cmath>
+#include <string>
+#include <vector>
+
+#include "../../include/midagma_hip.h"
+#include "solver_impl.h"
+
+namespace {
+
+thread_local std::string g_batch_err;
+constexpr int64_t kMaxBatch = 16384;
+
+// The listed problems' d x d blocks between the compact host layout (B x d x d) and the padded
+// slabs (B x D x D, zero padding).  grid (D * D / NTHREADS, problems listed).
+__global__ void batch_pad_kernel(const double* __restrict__ src, double* __restrict__ dst, int64_t d, int64_t D,
+                                 const int32_t* __restrict__ index) {
+  const int64_t b = index ? index[blockIdx.y] : blockIdx.y;
+  const int64_t e = (int64_t)blockIdx.x * NTHREADS + threadIdx.x;
+  if (e >= D * D) return;
+  const int64_t i = e / D, j = e % D;
+  dst[b * D * D + e] = (i < d && j < d) ? src[b * d * d + i * d + j] : 0.0;
+}
+__global__ void batch_unpad_kernel(const double* __restrict__ src, double* __restrict__ dst, int64_t d, int64_t D,
+                                   const int32_t* __restrict__ index) {
+  const int64_t b = index[blockIdx.y];
+  const int64_t e = (int64_t)blockIdx.x * NTHREADS + threadIdx.x;
+  if (e >= d * d) return;
+  dst[b * d * d + e] = src[b * D * D + (e / d) * D + e % d];
+}
+// What midagma_solver::begin enqueues, for the listed problems: (-mu) cov (launch_scale's
+// a * x), m = v = 0, no pending norms and no warm start.
+__global__ void batch_begin_kernel(const Params* __restrict__ pr, const double* __restrict__ cov,
+                                   double* __restrict__ covs, double* __restrict__ m, double* __restrict__ v,
+                                   double* __restrict__ carry, int64_t DD, const int32_t* __restrict__ index) {
+  const int64_t b = index[blockIdx.y];
+  const int64_t e = (int64_t)blockIdx.x * NTHREADS + threadIdx.x;
+  if (e < NORM_FIELDS + 1) carry[b * (NORM_FIELDS + 1) + e] = 0.0;
+  if (e >= DD) return;
+  const double a = -pr[b].mu;
+  covs[b * DD + e] = a * cov[b * DD + e];
+  m[b * DD + e] = 0.0;
+  v[b * DD + e] = 0.0;
+}
+
+bool finite_block(const double* p, int64_t count) {
+  for (int64_t i = 0; i < count; ++i)
+    if (!std::isfinite(p[i])) return false;
+  return true;
+}
+
+}  // namespace
+
+struct midagma_batch {
+  int64_t d = 0, D = 0, B = 0;
+  int device = 0;
+  hipStream_t stream = nullptr;
+  std::string err;
+
+  DevBuf<> W, m, v, cov, covs, minc, mexc, carry, pstore, bc_table;
+  DevBuf<> stage;  // B x d x d: the compact host layout on the device
+  DevBuf<Params> d_params;
+  DevBuf<State> d_state;
+  DevBuf<CkptRec> d_ckpt;
+  DevBuf<int32_t> d_index;
+  PinBuf<Params> h_params;  // host mirrors of d_params, d_state; the index list of the next launch
+  PinBuf<State> h_state;
+  PinBuf<int32_t> h_index;
+  int64_t ckpt_cap = 0, bc_len = 0;
+  double bc_b1 = -1, bc_b2 = -1;
+  bool has_cov = false, has_inc = false, has_exc = false;
+  std::vector<uint8_t> last_active;  // the problems of the last minimize call (their checkpoints)
+
+  ~midagma_batch() {
+    if (stream) {
+      (void)hipStreamSynchronize(stream);
+      (void)hipStreamDestroy(stream);
+    }
+  }
+
+  dim3 grid(int64_t elems, int64_t problems) const {
+    return dim3((unsigned)((elems + NTHREADS - 1) / NTHREADS), (unsigned)problems);
+  }
+
+  void alloc() {
+    const size_t DD = (size_t)D * D, ds = (size_t)small_block(d);
+    for (DevBuf<>* b : {&W, &m, &v, &cov, &covs}) b->alloc((size_t)B * DD);
+    carry.alloc((size_t)B * (NORM_FIELDS + 1));
+    pstore.alloc((size_t)B * 2 * ds * ds);
+    stage.alloc((size_t)B * d * d);
+    d_params.alloc(B);
+    d_state.alloc(B);
+    d_index.alloc(B);
+    h_params.alloc(B);
+    h_state.alloc(B);
+    h_index.alloc(B);
+    for (int64_t b = 0; b < B; ++b) {
+      h_params.p[b] = Params{};
+      h_state.p[b] = State{};
+    }
+    last_active.assign(B, 0);
+  }
+
+  // host B x d x d -> every problem's padded slab of dst
+  void upload_all(DevBuf<>& dst, const double* src) {
+    HIP_TRY(hipMemcpyAsync(stage.p, src, (size_t)B * d * d * sizeof(double), hipMemcpyHostToDevice, stream));
+    hipLaunchKernelGGL(batch_pad_kernel, grid(D * D, B), dim3(NTHREADS), 0, stream, stage.p, dst.p, d, D, nullptr);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(stream));
+  }
+
+  void ensure_tables(double b1, double b2, int64_t max_iter, int64_t checkpoint) {
+    if (!(b1 == bc_b1 && b2 == bc_b2 && max_iter <= bc_len)) {  // midagma_solver::ensure_bc_table
+      const int64_t len = std::max<int64_t>(max_iter, 1);
+      const std::vector<double> t = bc_table_values(b1, b2, len);
+      bc_table.alloc(2 * len);
+      HIP_TRY(hipMemcpy(bc_table.p, t.data(), t.size() * sizeof(double), hipMemcpyHostToDevice));
+      bc_b1 = b1;
+      bc_b2 = b2;
+      bc_len = len;
+    }
+    const int64_t need = max_iter / checkpoint + 4;  // midagma_solver::ensure_ckpt
+    if (need > ckpt_cap) {
+      d_ckpt.alloc((size_t)B * need);
+      ckpt_cap = need;
+    }
+  }
+
+  void minimize(double* Wh, const double* mu, const double* s_dom, const double* lr, const double* lambda1,
+                int64_t max_iter, double tol, double b1, double b2, int64_t checkpoint, const uint8_t* active,
+                midagma_result* res) {
+    ensure_tables(b1, b2, max_iter, checkpoint);
+    int64_t n_run = 0;
+    for (int64_t b = 0; b < B; ++b) {
+      last_active[b] = !active || active[b];
+      if (!last_active[b]) continue;
+      h_params.p[b] = cov_l2_params(d, D, mu[b], s_dom[b], lambda1[b], tol, b1, b2, max_iter, checkpoint, bc_len,
+                                    has_inc, has_exc);
+      h_state.p[b] = initial_state(lr[b]);
+      h_index.p[n_run++] = (int32_t)b;
+    }
+    if (n_run == 0) return;
+    const int64_t DD = D * D;
+    HIP_TRY(hipMemcpyAsync(d_params.p, h_params.p, B * sizeof(Params), hipMemcpyHostToDevice, stream));
+    HIP_TRY(hipMemcpyAsync(d_state.p, h_state.p, B * sizeof(State), hipMemcpyHostToDevice, stream));
+    HIP_TRY(hipMemcpyAsync(d_index.p, h_index.p, n_run * sizeof(int32_t), hipMemcpyHostToDevice, stream));
+    // (the stage keeps the caller's W of the inactive problems, which the download hands back)
+    HIP_TRY(hipMemcpyAsync(stage.p, Wh, (size_t)B * d * d * sizeof(double), hipMemcpyHostToDevice, stream));
+    hipLaunchKernelGGL(batch_pad_kernel, grid(DD, n_run), dim3(NTHREADS), 0, stream, stage.p, W.p, d, D, d_index.p);
+    hipLaunchKernelGGL(batch_begin_kernel, grid(DD, n_run), dim3(NTHREADS), 0, stream, d_params.p, cov.p, covs.p, m.p,
+                       v.p, carry.p, DD, d_index.p);
+    HIP_TRY(hipGetLastError());
+    const int64_t n_active = n_run;
+
+    // drive_small over the problems still running: one launch of up to kSmallBatch slots, one
+    // copy of every State, one sync
+    const int64_t cap = slot_cap(max_iter, checkpoint);
+    for (int64_t launched = 0; n_run > 0;) {
+      const int64_t slots = small_next_batch(-1, launched, cap, midagma_solver::kSmallBatch);
+      launch_small_minimize(d_params.p, d_state.p, W.p, m.p, v.p, covs.p, has_inc ? minc.p : nullptr,
+                            has_exc ? mexc.p : nullptr, bc_table.p, d_ckpt.p, ckpt_cap, carry.p, pstore.p, d, slots,
+                            stream, nullptr, false, d_index.p, n_run);
+      launched += slots;
+      HIP_TRY(hipMemcpyAsync(h_state.p, d_state.p, B * sizeof(State), hipMemcpyDeviceToHost, stream));
+      HIP_TRY(hipStreamSynchronize(stream));
+      int64_t still = 0;
+      for (int64_t k = 0; k < n_run; ++k) {
+        const int32_t b = h_index.p[k];
+        if (h_state.p[b].status == ST_RUNNING) h_index.p[still++] = b;
+      }
+      n_run = still;
+      if (n_run > 0)
+        HIP_TRY(hipMemcpyAsync(d_index.p, h_index.p, n_run * sizeof(int32_t), hipMemcpyHostToDevice, stream));
+    }
+
+    // hand back the active problems' W (the index list of the call again)
+    int64_t k = 0;
+    for (int64_t b = 0; b < B; ++b)
+      if (last_active[b]) h_index.p[k++] = (int32_t)b;
+    HIP_TRY(hipMemcpyAsync(d_index.p, h_index.p, n_active * sizeof(int32_t), hipMemcpyHostToDevice, stream));
+    hipLaunchKernelGGL(batch_unpad_kernel, grid(d * d, n_active), dim3(NTHREADS), 0, stream, W.p, stage.p, d, D,
+                       d_index.p);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(Wh, stage.p, (size_t)B * d * d * sizeof(double), hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
+    for (int64_t b = 0; b < B; ++b)
+      if (last_active[b]) midagma_solver::fill_result(h_state.p[b], &res[b]);
+  }
+};
+
+namespace {
+
+int bfail(midagma_batch* h, int code, const std::string& msg) {
+  (h ? h->err : g_batch_err) = msg;
+  return code;
+}
+
+template <class F>
+int bguarded(midagma_batch* h, F&& f) {
+  try {
+    if (h) HIP_TRY(hipSetDevice(h->device));
+    f();
+    return MIDAGMA_OK;
+  } catch (...) {
+    std::string msg;
+    const int rc = classify(std::current_exception(), msg);
+    return bfail(h, rc, msg);
+  }
+}
+
+}  // namespace
+
+extern "C" const char* midagma_batch_last_error(const midagma_batch* h) {
+  return (h ? h->err : g_batch_err).c_str();
+}
+
+extern "C" int midagma_batch_create(midagma_batch** out, int64_t d, int64_t B, int device) {
+  if (!out || d < 1 || d > 64 || B < 1 || B > kMaxBatch || device < 0)
+    return bfail(nullptr, MIDAGMA_E_ARG, "batch_create: need 1 <= d <= 64, 1 <= B <= 16384 and a device");
+  *out = nullptr;
+  midagma_batch* h = nullptr;
+  const int rc = bguarded(nullptr, [&] {
+    int count = 0;
+    HIP_TRY(hipGetDeviceCount(&count));
+    if (device >= count) throw std::invalid_argument("batch_create: no such device");
+    HIP_TRY(hipSetDevice(device));
+    h = new midagma_batch;
+    h->d = d;
+    h->D = round_up64(d);
+    h->B = B;
+    h->device = device;
+    HIP_TRY(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
+    h->alloc();
+  });
+  if (rc != MIDAGMA_OK) {
+    midagma_batch_destroy(h);
+    return rc;
+  }
+  *out = h;
+  return MIDAGMA_OK;
+}
+
+extern "C" void midagma_batch_destroy(midagma_batch* h) {
+  if (!h) return;
+  (void)hipSetDevice(h->device);
+  delete h;
+}
+
+extern "C" int midagma_batch_set_cov(midagma_batch* h, const double* cov) {
+  if (!h || !cov) return bfail(h, MIDAGMA_E_ARG, "batch_set_cov: null argument");
+  if (!finite_block(cov, h->B * h->d * h->d))
+    return bfail(h, MIDAGMA_E_ARG, "batch_set_cov: array must not contain infs or NaNs");
+  return bguarded(h, [&] {
+    h->upload_all(h->cov, cov);
+    h->has_cov = true;
+  });
+}
+
+extern "C" int midagma_batch_set_masks(midagma_batch* h, const double* mask_inc, const double* mask_exc) {
+  if (!h) return bfail(h, MIDAGMA_E_ARG, "batch_set_masks: null handle");
+  return bguarded(h, [&] {
+    const size_t n = (size_t)h->B * h->D * h->D;
+    if (mask_inc) {
+      h->minc.alloc(n);
+      h->upload_all(h->minc, mask_inc);
+    }
+    if (mask_exc) {
+      h->mexc.alloc(n);
+      h->upload_all(h->mexc, mask_exc);
+    }
+    h->has_inc = mask_inc != nullptr;
+    h->has_exc = mask_exc != nullptr;
+  });
+}
+
+extern "C" int midagma_batch_minimize(midagma_batch* h, double* W, const double* mu, const double* s_dom,
+                                      const double* lr, const double* lambda1, int64_t max_iter, double tol,
+                                      double beta1, double beta2, int64_t checkpoint, const uint8_t* active,
+                                      midagma_result* res) {
+  if (!h) return bfail(h, MIDAGMA_E_ARG, "batch_minimize: null handle");
+  if (!W || !mu || !s_dom || !lr || !lambda1 || !res) return bfail(h, MIDAGMA_E_ARG, "batch_minimize: null argument");
+  if (max_iter < 1 || checkpoint < 1)
+    return bfail(h, MIDAGMA_E_ARG, "batch_minimize: max_iter and checkpoint must be >= 1");
+  if (!h->has_cov) return bfail(h, MIDAGMA_E_ARG, "batch_minimize: set_cov before minimize");
+  const int64_t dd = h->d * h->d;
+  for (int64_t b = 0; b < h->B; ++b)
+    if ((!active || active[b]) && !finite_block(W + b * dd, dd))
+      return bfail(h, MIDAGMA_E_ARG, "batch_minimize: array must not contain infs or NaNs");
+  return bguarded(h, [&] {
+    h->minimize(W, mu, s_dom, lr, lambda1, max_iter, tol, beta1, beta2, checkpoint, active, res);
+  });
+}
+
+extern "C" int64_t midagma_batch_checkpoints(midagma_batch* h, int64_t b, midagma_ckpt* out, int64_t cap) {
+  if (!h || b < 0 || b >= h->B) return bfail(h, MIDAGMA_E_ARG, "batch_checkpoints: bad arguments");
+  if (!h->last_active[b] || !h->d_ckpt.p) return 0;
+  int64_t n = 0;
+  const int rc = bguarded(h, [&] {
+    n = std::max<int64_t>(0, std::min<int64_t>(std::min<int64_t>(h->h_state.p[b].n_ckpt, h->ckpt_cap), cap));
+    static_assert(sizeof(midagma_ckpt) == sizeof(CkptRec), "ckpt layout");
+    if (n > 0 && out)
+      HIP_TRY(hipMemcpy(out, h->d_ckpt.p + b * h->ckpt_cap, n * sizeof(CkptRec), hipMemcpyDeviceToHost));
+  });
+  return rc == MIDAGMA_OK ? n : rc;
+}

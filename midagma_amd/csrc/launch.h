@@ -287,6 +287,9 @@ int small_block(int64_t d);
 // tcc (nullable; d <= 32): the TCC trek regularizer inside every slot ('opt') or every
 // checkpoint slot ('log'), tcc_blk.h's body on the workgroup, its state words read at entry and
 // written back at exit (the graph-replayed slots' TccWork words, so the two paths interleave).
+// index (nullable; float64, no tcc): a batch (batch.hip).  n_problems workgroups, workgroup g on
+// problem index[g] of per-problem arrays: pr and st by 1, the matrices by pr->D * pr->D, ckpt by
+// ckpt_cap, carry by NORM_FIELDS + 1, pstore by 2 * small_block(d)^2; bc_table is shared.
 struct SmallTcc {
   const double* S;        // D x D pair indicator
   double ws, eps, m, weight;
@@ -299,7 +302,8 @@ struct SmallTcc {
 void launch_small_minimize(const Params* pr, State* st, double* W, double* m, double* v, const double* covs,
                            const double* minc, const double* mexc, const double* bc_table, CkptRec* ckpt,
                            int64_t ckpt_cap, double* carry, double* pstore, int64_t d, int64_t n_slots,
-                           hipStream_t stream, const SmallTcc* tcc = nullptr, bool w32 = false);
+                           hipStream_t stream, const SmallTcc* tcc = nullptr, bool w32 = false,
+                           const int32_t* index = nullptr, int64_t n_problems = 1);
 
 // --- trek.hip ---------------------------------------------------------------
 enum TrekSeq : int { TREK_EXP = 0, TREK_INV = 1, TREK_LOG = 2, TREK_BINOM = 3 };

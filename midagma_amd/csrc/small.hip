@@ -252,11 +252,30 @@ __device__ __noinline__ void small_control(const SmallCtlParams& pr_, State& S, 
 
 template <int DS, int NW, int TCC, bool W32 = false>
 __global__ __launch_bounds__(64 * NW) void small_minimize_kernel(
-    const Params* __restrict__ pr, State* __restrict__ stg, double* __restrict__ Wg, double* __restrict__ mg,
-    double* __restrict__ vg, const double* __restrict__ covs, const double* __restrict__ minc,
-    const double* __restrict__ mexc, const double* __restrict__ bc_table, CkptRec* __restrict__ ckpt,
-    int64_t ckpt_cap, double* __restrict__ carry, double* __restrict__ pstore, int64_t n_slots, SmallTcc tc) {
+    const Params* __restrict__ pr_, State* __restrict__ stg_, double* __restrict__ Wg_, double* __restrict__ mg_,
+    double* __restrict__ vg_, const double* __restrict__ covs_, const double* __restrict__ minc_,
+    const double* __restrict__ mexc_, const double* __restrict__ bc_table, CkptRec* __restrict__ ckpt_,
+    int64_t ckpt_cap, double* __restrict__ carry_, double* __restrict__ pstore_, int64_t n_slots, SmallTcc tc,
+    const int32_t* __restrict__ index) {
   constexpr int NT = 64 * NW, TPR = DS / 16, TPW = TPR * TPR / NW, E = 4 * TPW;
+  // A batch (batch.hip): workgroup blockIdx.x works on problem index[blockIdx.x] of per-problem
+  // arrays (Params, State, the D x D slabs, ckpt_cap records, the carry words, the two stored
+  // inverses); bc_table is the call's.  The workgroups share nothing and never wait on each
+  // other.  The single solver is the batch of one: no index, grid 1, problem 0.  The offsets are
+  // workgroup-uniform (scalar registers).
+  const int64_t prob = index ? index[blockIdx.x] : blockIdx.x;
+  const Params* __restrict__ const pr = pr_ + prob;
+  const int64_t slab = prob * (pr->D * pr->D);
+  State* __restrict__ const stg = stg_ + prob;
+  double* __restrict__ const Wg = Wg_ + slab;
+  double* __restrict__ const mg = mg_ + slab;
+  double* __restrict__ const vg = vg_ + slab;
+  const double* __restrict__ const covs = covs_ + slab;
+  const double* __restrict__ const minc = minc_ ? minc_ + slab : nullptr;
+  const double* __restrict__ const mexc = mexc_ ? mexc_ + slab : nullptr;
+  CkptRec* __restrict__ const ckpt = ckpt_ + prob * ckpt_cap;
+  double* __restrict__ const carry = carry_ + prob * (NORM_FIELDS + 1);
+  double* __restrict__ const pstore = pstore_ + prob * (2 * DS * DS);
   // TCC (0: off): tcc_blk.h's body on this workgroup.  4: NB x NB = NT threads of 4 x 4 blocks
   // (DS = 16: NB = 8, DS = 32: 16); 5: one wave of 5 x 5 blocks (NB = 8, 2d <= 40: d <= 20), the
   // other waves along without writes
@@ -926,9 +945,13 @@ int small_block(int64_t d) {
 void launch_small_minimize(const Params* pr, State* st, double* W, double* m, double* v, const double* covs,
                            const double* minc, const double* mexc, const double* bc_table, CkptRec* ckpt,
                            int64_t ckpt_cap, double* carry, double* pstore, int64_t d, int64_t n_slots,
-                           hipStream_t stream, const SmallTcc* tcc, bool w32) {
+                           hipStream_t stream, const SmallTcc* tcc, bool w32, const int32_t* index,
+                           int64_t n_problems) {
   const int ds = small_block(d);
   if (ds == 0) throw std::invalid_argument("small_minimize: d > 64");
+  if (n_problems < 1 || (!index && n_problems != 1))
+    throw std::invalid_argument("small_minimize: a batch needs its index list");
+  if (index && (tcc || w32)) throw std::invalid_argument("small_minimize: a batch is float64 without TCC");
   if (tcc && ds > 32) throw std::invalid_argument("small_minimize: the TCC regularizer needs d <= 32");
   if (tcc && w32) throw std::invalid_argument("small_minimize: float32 W with TCC runs on the graph path");
   // d <= 20 on DS = 32: the one-wave 5 x 5 body (d=20: 10.4k -> 11.7k steps/s; experiment knob
@@ -936,8 +959,9 @@ void launch_small_minimize(const Params* pr, State* st, double* W, double* m, do
   const bool bs5 = tcc && ds == 32 && d <= 20 && knob("MIDAGMA_EXP_TCC_BS5", 1) != 0;
   const SmallTcc tc = tcc ? *tcc : SmallTcc{};
 #define MIDAGMA_SMALL(DS_, NW_, TCC_, W32_)                                                                \
-  hipLaunchKernelGGL((small_minimize_kernel<DS_, NW_, TCC_, W32_>), dim3(1), dim3(64 * NW_), 0, stream, pr, st, W, \
-                     m, v, covs, minc, mexc, bc_table, ckpt, ckpt_cap, carry, pstore, n_slots, tc)
+  hipLaunchKernelGGL((small_minimize_kernel<DS_, NW_, TCC_, W32_>), dim3((unsigned)n_problems), dim3(64 * NW_), 0, \
+                     stream, pr, st, W, m, v, covs, minc, mexc, bc_table, ckpt, ckpt_cap, carry, pstore, n_slots, tc,   \
+                     index)
   // one wave per 16 x 16 tile
   if (ds == 16) {
     if (tcc)

@@ -35,6 +35,54 @@ namespace midagma {
 hipGraphExec_t group_capture(midagma_group* g, const midagma_solver* caller, int which, int reps, int passes);
 void group_clear_handback(midagma_group* g);
 
+// What a minimize call uploads before its first slot, shared by midagma_solver::begin and the
+// batch of small-d problems (batch.hip).
+// The Params of a float64 cov-mode l2 call without a trek regularizer; begin overrides the
+// fields its other modes set differently.
+inline Params cov_l2_params(int64_t d, int64_t D, double mu, double s, double lambda1, double tol, double b1,
+                            double b2, int64_t max_iter, int64_t checkpoint, int64_t ld_table, bool has_inc,
+                            bool has_exc) {
+  Params p{};
+  p.mu = mu;
+  p.s = s;
+  p.lambda1 = lambda1;
+  p.tol = tol;
+  p.beta1 = b1;
+  p.beta2 = b2;
+  p.c1 = 1 - b1;
+  p.c2 = 1 - b2;
+  p.mu_l1 = mu * lambda1;
+  p.d_log_s = (double)d * std::log(s);
+  p.max_iter = max_iter;
+  p.checkpoint = checkpoint;
+  p.d = d;
+  p.D = D;
+  p.ld_table = ld_table;
+  p.has_inc = has_inc;
+  p.has_exc = has_exc;
+  p.zscale = 1.0;  // Z already is ((-mu) cov) @ (I - W)
+  p.cscale = 0.0;
+  p.score_scale = 0.5 / (-mu);
+  return p;
+}
+// the State before a call's first slot
+inline State initial_state(double lr) {
+  State st{};
+  st.status = ST_RUNNING;
+  st.lr = lr;
+  st.obj_prev = 1e16;
+  return st;
+}
+// (1 - beta ** iter) for iter = 1..len, exactly as Python computes it (linear.py:160-161)
+inline std::vector<double> bc_table_values(double b1, double b2, int64_t len) {
+  std::vector<double> t(2 * len);
+  for (int64_t it = 1; it <= len; ++it) {
+    t[2 * (it - 1)] = 1 - ::pow(b1, (double)it);
+    t[2 * (it - 1) + 1] = 1 - ::pow(b2, (double)it);
+  }
+  return t;
+}
+
 }  // namespace midagma
 
 using namespace midagma;
@@ -899,11 +947,7 @@ struct midagma_solver {
   void ensure_bc_table(double b1, double b2, int64_t max_iter) {
     if (b1 == bc_b1 && b2 == bc_b2 && max_iter <= bc_len) return;
     const int64_t len = std::max<int64_t>(max_iter, 1);
-    std::vector<double> t(2 * len);
-    for (int64_t it = 1; it <= len; ++it) {  // (1 - beta ** iter) exactly as Python computes it (linear.py:160-161)
-      t[2 * (it - 1)] = 1 - ::pow(b1, (double)it);
-      t[2 * (it - 1) + 1] = 1 - ::pow(b2, (double)it);
-    }
+    const std::vector<double> t = bc_table_values(b1, b2, len);
     bc_table.alloc(2 * len);
     HIP_TRY(hipMemcpy(bc_table.p, t.data(), t.size() * sizeof(double), hipMemcpyHostToDevice));
     bc_b1 = b1;
@@ -929,34 +973,16 @@ struct midagma_solver {
     mu = mu_;
     ensure_bc_table(b1, b2, max_iter);
     ensure_ckpt(max_iter, checkpoint);
-    Params p{};
-    p.mu = mu_;
-    p.s = s;
-    p.lambda1 = lambda1;
-    p.tol = tol;
-    p.beta1 = b1;
-    p.beta2 = b2;
-    p.c1 = 1 - b1;
-    p.c2 = 1 - b2;
+    Params p = cov_l2_params(d, D, mu_, s, lambda1, tol, b1, b2, max_iter, checkpoint, bc_len, has_inc, has_exc);
     // (float32 W: mu * lambda1 * sign(W) is a float32 array, linear.py:248)
-    p.mu_l1 = w32 ? f32r(mu_ * lambda1) : mu_ * lambda1;
+    if (w32) p.mu_l1 = f32r(mu_ * lambda1);
     p.w32 = w32 ? 1 : 0;
-    p.d_log_s = (double)d * std::log(s);
-    p.max_iter = max_iter;
-    p.checkpoint = checkpoint;
-    p.d = d;
-    p.D = D;
-    p.ld_table = bc_len;
-    p.has_inc = has_inc;
-    p.has_exc = has_exc;
     p.logistic = loss == MIDAGMA_LOSS_LOGISTIC;
     p.trek_weight = trek_on ? tcfg.weight : 0.0;
     p.trek_mode = trek_on ? tcfg.mode : 0;
     const double n = (double)n_global;
     if (mode == MIDAGMA_MODE_COV) {
-      p.zscale = 1.0;  // Z already is ((-mu) cov) @ (I - W)
-      p.cscale = 0.0;
-      p.score_scale = 0.5 / (-mu_);
+      // cov_l2_params' scales: Z already is ((-mu) cov) @ (I - W)
     } else if (loss == MIDAGMA_LOSS_L2) {
       p.zscale = -mu_ / n;
       p.cscale = 0.0;
@@ -969,11 +995,7 @@ struct midagma_solver {
     }
     hp = p;
     HIP_TRY(hipMemcpyAsync(d_params.p, &hp, sizeof(Params), hipMemcpyHostToDevice, stream));
-    State st{};
-    st.status = ST_RUNNING;
-    st.lr = lr;
-    st.obj_prev = 1e16;
-    h_state.p[0] = st;
+    h_state.p[0] = initial_state(lr);
     HIP_TRY(hipMemcpyAsync(d_state.p, &h_state.p[0], sizeof(State), hipMemcpyHostToDevice, stream));
     if (mode == MIDAGMA_MODE_COV) {
       launch_scale(cov.p, -mu_, covs.p, D * D, stream);  // (-mu) * cov

@@ -17,7 +17,7 @@ import numpy as np
 from . import _lib
 from ._lib import check, dptr
 
-__all__ = ["HipSolver", "HipGroup", "HipIndep", "MinimizeResult", "CheckpointRecord", "run_allreduce_minimize",
+__all__ = ["HipSolver", "HipGroup", "HipIndep", "HipBatch", "MinimizeResult", "CheckpointRecord", "run_allreduce_minimize",
            "device_count", "colsum_dev", "center_dev", "gram", "row_range"]
 
 
@@ -759,6 +759,102 @@ class HipIndep:
         if return_perms:
             out.append(perms if perms is not None else pout)
         return tuple(out)
+
+
+class HipBatch:
+    """B independent small-d problems (d <= 64, l2, cov mode, float64) on one GPU, one persistent
+    workgroup each (`midagma_batch_*`, csrc/batch.hip).  The problems share d and the loop
+    settings; each has its own covariance, masks, mu, s, lr and lambda1.  Problem b's W, result
+    and checkpoint records are bit-identical to a `HipSolver` run of that problem alone."""
+
+    MAX_D, MAX_B = 64, 16384
+
+    def __init__(self, d: int, B: int, device: int = 0):
+        self.L = _lib.lib()
+        self.h = None
+        self.d, self.B, self.device = int(d), int(B), int(device)
+        self._has_cov = False
+        h = C.c_void_p()
+        self._check(self.L.midagma_batch_create(C.byref(h), self.d, self.B, self.device), None, "batch_create")
+        self.h = h
+
+    def _check(self, rc, handle, what):
+        if rc >= 0:
+            return rc
+        m = self.L.midagma_batch_last_error(handle)
+        msg = m.decode() if m else ""
+        if rc == _lib.E_ARG:
+            raise ValueError(f"{what}: {msg}")
+        raise _lib.HipSolverError(f"{what} failed ({rc}): {msg}")
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.L.midagma_batch_destroy(self.h)
+            self.h = None
+
+    def __del__(self):  # pragma: no cover
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _stack(self, a, what) -> np.ndarray:
+        a = _as_f64(a)
+        if a.shape != (self.B, self.d, self.d):
+            raise ValueError(f"{what} must be {(self.B, self.d, self.d)}, got {a.shape}")
+        return a
+
+    def _per_problem(self, x, what) -> np.ndarray:
+        a = np.ascontiguousarray(np.broadcast_to(np.asarray(x, dtype=np.float64), (self.B,)))
+        if a.shape != (self.B,):  # pragma: no cover (broadcast_to raised already)
+            raise ValueError(f"{what} must be a scalar or hold {self.B} values")
+        return a
+
+    def set_cov(self, cov):
+        """cov: B x d x d (copied); ValueError on inf / nan."""
+        cov = self._stack(cov, "cov")
+        self._check(self.L.midagma_batch_set_cov(self.h, dptr(cov)), self.h, "batch_set_cov")
+        self._has_cov = True
+
+    def set_masks(self, mask_inc, mask_exc):
+        """B x d x d each, or None to switch that mask off (linear.py:217-222, per problem)."""
+        mi = None if mask_inc is None else self._stack(mask_inc, "mask_inc")
+        me = None if mask_exc is None else self._stack(mask_exc, "mask_exc")
+        self._check(self.L.midagma_batch_set_masks(self.h, dptr(mi), dptr(me)), self.h, "batch_set_masks")
+
+    def minimize(self, W: np.ndarray, mu, s, lr, lambda1, max_iter: int, tol: float = 1e-6, beta_1: float = 0.99,
+                 beta_2: float = 0.999, checkpoint: int = 1000, active=None, want_checkpoints: bool = False):
+        """linear.py:165-333 for every active problem in one launch sequence.  W (B x d x d float64)
+        is updated in place; mu, s, lr, lambda1 are scalars or hold B values; active: B booleans
+        (None: all).  Returns B `MinimizeResult`s; an inactive problem's W is untouched and its
+        entry is None.  A singular problem is reported in its result's status, not raised."""
+        assert W.shape == (self.B, self.d, self.d) and W.dtype == np.float64 and W.flags.c_contiguous
+        if not self._has_cov:
+            raise _lib.HipSolverError("batch_minimize: set_cov before minimize")
+        mu, s, lr, lambda1 = (self._per_problem(x, n) for x, n in ((mu, "mu"), (s, "s"), (lr, "lr"),
+                                                                   (lambda1, "lambda1")))
+        act = None if active is None else np.ascontiguousarray(np.asarray(active, dtype=bool).astype(np.uint8))
+        if act is not None and act.shape != (self.B,):
+            raise ValueError(f"active must hold {self.B} values")
+        res = (_lib.MidagmaResult * self.B)()
+        rc = self.L.midagma_batch_minimize(self.h, dptr(W), dptr(mu), dptr(s), dptr(lr), dptr(lambda1), int(max_iter),
+                                           float(tol), float(beta_1), float(beta_2), int(checkpoint),
+                                           None if act is None else C.c_void_p(act.ctypes.data), res)
+        self._check(rc, self.h, "batch_minimize")
+        return [MinimizeResult.from_c(res[b], self.checkpoints(b) if want_checkpoints else ())
+                if act is None or act[b] else None for b in range(self.B)]
+
+    def checkpoints(self, b: int):
+        """Problem b's checkpoint records of the last minimize call (`CheckpointRecord`)."""
+        cap = 1 << 12
+        while True:
+            buf = (_lib.MidagmaCkpt * cap)()
+            n = self._check(self.L.midagma_batch_checkpoints(self.h, int(b), buf, cap), self.h, "batch_checkpoints")
+            if n < cap:
+                break
+            cap *= 16
+        return [CheckpointRecord(*(int(c.iter) if f == "iter" else float(getattr(c, f))
+                                   for f in CheckpointRecord._fields)) for c in buf[:n]]
 
 
 def run_allreduce_minimize(backend, W, mu, max_iter, s, lr, tol=1e-6, beta_1=0.99, beta_2=0.999,
