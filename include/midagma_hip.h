@@ -453,6 +453,31 @@ int midagma_batch_minimize(midagma_batch* h, double* W, const double* mu, const 
                            const double* lambda1, int64_t max_iter, double tol, double beta1, double beta2,
                            int64_t checkpoint, const uint8_t* active, midagma_result* res);
 int64_t midagma_batch_checkpoints(midagma_batch* h, int64_t b, midagma_ckpt* out, int64_t cap);
+
+/* Bootstrap covariances for a batch, formed on the device from one X (additive, ABI 11).
+ * Replicate b of `seed` draws n row indices with replacement:
+ *   o = Philox4x32-10(counter (j, b, 0, 0), key (seed & 0xffffffff, seed >> 32)),
+ *   r = (o0 << 32) | o1,  idx[j] = (r * n) >> 64  (the high 64 bits of the 128-bit product),
+ * and its covariance is that of the resample, Xb = X[idx]; Xb -= Xb.mean(0); Xb^T Xb / n, computed
+ * as (S - t t^T / n) / n over the rows of X weighted by how often each is drawn, X centred once by
+ * its global column mean.  The result for replicate b depends on (X, seed, b) alone and is exactly
+ * symmetric.
+ * boot_cov: cov of replicates first .. first+B-1 of (seed) from X (n x d, leading dimension ldx,
+ *   host or device memory per on_device) into the batch's B problems; afterwards the batch is as
+ *   after midagma_batch_set_cov.  X is not written.  Replicates are processed in chunks whose
+ *   scratch (n int32 counts and the Gram partials per replicate) stays within budget_bytes
+ *   (<= 0: 1 GiB; at least one replicate per chunk); results do not depend on the chunking.  A
+ *   device X must be complete before the call (the batch runs on its own stream).
+ *   MIDAGMA_E_ARG before any device work: a null handle or X, n < 1, n >= 2^31, ldx < d,
+ *   first < 0 or first + B > 2^32; MIDAGMA_E_ARG with set_cov's message: X holds inf/nan (the
+ *   batch's cov is then left as it was).
+ * boot_get_cov: the batch's current covariances, B x d x d, to the host (diagnostics and tests).
+ * boot_profile: device-event times in ms of the last boot_cov, summed over its chunks: [0] copy
+ *   and centring of X, [1] counts, [2] weighted Gram, [3] finish. */
+int midagma_boot_cov(midagma_batch* h, const void* X, int64_t n, int64_t ldx, int on_device, uint64_t seed,
+                     int64_t first, int64_t budget_bytes);
+int midagma_boot_get_cov(midagma_batch* h, double* out);
+int midagma_boot_profile(const midagma_batch* h, double* ms_out);
 #ifdef __cplusplus
 }
 #endif

@@ -8,7 +8,7 @@
 The compute path is hand-written HIP for gfx950 in `midagma_amd/csrc`, built
 in-tree into `libmidagma_hip.so` and bound with ctypes (`_lib.py`).
 """
-from .batch import DagmaLinearBatch  # noqa: F401
+from .batch import DagmaLinearBatch, bootstrap_indices  # noqa: F401
 from .linear import DagmaLinear  # noqa: F401
 from .simulate import count_accuracy, is_dag, make_dataset  # noqa: F401
 from .solver import HipBatch, HipIndep, HipSolver, MinimizeResult, device_count, run_allreduce_minimize  # noqa: F401

@@ -157,6 +157,10 @@ EXPORTED = {
     "midagma_batch_minimize": (_int, [_vp, _dp, _dp, _dp, _dp, _dp, _i64, _d, _d, _d, _i64, _vp,
                                       C.POINTER(MidagmaResult)]),
     "midagma_batch_checkpoints": (_i64, [_vp, _i64, C.POINTER(MidagmaCkpt), _i64]),
+    # additive to ABI 11: bootstrap covariances for a batch from one X (HipBatch.boot_cov, csrc/boot.hip)
+    "midagma_boot_cov": (_int, [_vp, _vp, _i64, _i64, _int, C.c_uint64, _i64, _i64]),
+    "midagma_boot_get_cov": (_int, [_vp, _dp]),
+    "midagma_boot_profile": (_int, [_vp, _dp]),
 }
 
 GROUP_EMULATE = 1
@@ -165,6 +169,7 @@ GROUP_EMULATE = 1
 DEBUG_HOOKS = {
     "midagma_debug_slot_matrices": (_int, [_vp, _dp, _dp]),
     "midagma_debug_live_bytes": (_i64, []),
+    "midagma_debug_batch_cov_slabs": (_int, [_vp, _dp]),
 }
 
 _lock = threading.Lock()

@@ -13,8 +13,16 @@ returns with the same arguments: the stages of the path-following loop (linear.p
 in lockstep over the problems, and within a stage the problems that have not yet succeeded are
 re-run, each with its own halved lr and enlarged s, until none is left.
 
+Bootstrap edge frequencies come from one X, host or device, without B gathered copies of it:
+
+    freq = DagmaLinearBatch().bootstrap(X, n_boot=1024, lambda1=0.03, seed=7)     # (d, d)
+
+The device draws replicate b's row indices (`bootstrap_indices(seed, b, n)` restates the rule on
+the host) and forms its covariance from counts over one pass of X (csrc/boot.hip), straight into
+problem b of the batch; the stage and retry loop is `fit`'s.
+
 Not in the batch: a trek regularizer, float32 W, d > 64, the logistic loss and data mode, several
-devices, a device X.
+devices, a device X in `fit` (`bootstrap` takes one), weighted or m-out-of-n bootstraps.
 """
 from __future__ import annotations
 
@@ -26,7 +34,40 @@ import numpy as np
 from . import _lib
 from .solver import HipBatch, HipSolver, is_device_tensor
 
-__all__ = ["DagmaLinearBatch"]
+__all__ = ["DagmaLinearBatch", "bootstrap_indices"]
+
+_M32 = np.uint64(0xFFFFFFFF)
+
+
+def _philox4x32_10(c0, c1, c2, c3, k0: int, k1: int):
+    """Philox4x32-10 (Salmon et al., SC'11) over arrays of counter words held in uint64; the four
+    output words.  csrc/philox.h is the device's."""
+    c0, c1, c2, c3 = (np.asarray(c, dtype=np.uint64) & _M32 for c in (c0, c1, c2, c3))
+    m0, m1 = np.uint64(0xD2511F53), np.uint64(0xCD9E8D57)
+    sh = np.uint64(32)
+    for r in range(10):
+        ka, kb = np.uint64((k0 + r * 0x9E3779B9) & 0xFFFFFFFF), np.uint64((k1 + r * 0xBB67AE85) & 0xFFFFFFFF)
+        p0, p1 = m0 * c0, m1 * c2  # 32 x 32 -> 64 bits, no overflow
+        c0, c1, c2, c3 = (p1 >> sh) ^ c1 ^ ka, p1 & _M32, (p0 >> sh) ^ c3 ^ kb, p0 & _M32
+    return c0, c1, c2, c3
+
+
+def bootstrap_indices(seed: int, b: int, n: int) -> np.ndarray:
+    """The n row indices (int64, in [0, n)) of bootstrap replicate `b` of `seed`, as the device draws
+    them (csrc/boot.hip): o = Philox4x32-10(counter (j, b, 0, 0), key (seed & 0xffffffff, seed >> 32)),
+    r = (o0 << 32) | o1, idx[j] = (r * n) >> 64.  `X[bootstrap_indices(seed, b, len(X))]` is the
+    resample that replicate b of `DagmaLinearBatch.bootstrap(X, ..., seed=seed)` fits."""
+    seed, b, n = int(seed) & (2**64 - 1), int(b), int(n)
+    if not 1 <= n < 2**31:
+        raise ValueError(f"bootstrap_indices needs 1 <= n < 2^31, got {n}")
+    if not 0 <= b < 2**32:
+        raise ValueError(f"bootstrap_indices needs 0 <= b < 2^32, got {b}")
+    j = np.arange(n, dtype=np.uint64)
+    zero = np.zeros(n, dtype=np.uint64)
+    o0, o1, _, _ = _philox4x32_10(j, zero + np.uint64(b), zero, zero, seed & 0xFFFFFFFF, seed >> 32)
+    # the high 64 bits of r * n with r = o0 2^32 + o1: (o0 n + ((o1 n) >> 32)) >> 32, all below 2^64
+    nn, sh = np.uint64(n), np.uint64(32)
+    return ((o0 * nn + ((o1 * nn) >> sh)) >> sh).astype(np.int64)
 
 
 def _edges(edges):
@@ -112,6 +153,133 @@ class DagmaLinearBatch:
             mask_exc[:, exc[0], exc[1]] = 0.
         return mask_inc, mask_exc
 
+    # ------------------------------------------------- the loop of fit and bootstrap
+    @staticmethod
+    def _s_list(s, T: int):
+        if isinstance(s, (list, tuple)):
+            return list(s) + max(0, T - len(s)) * [s[-1]]  # linear.py:431-434
+        if type(s) in (int, float):
+            return T * [s]
+        raise ValueError("s should be a list, int, or float.")
+
+    def _stages(self, batch, B, d, lam, T, s0, inc, exc, mu_init, mu_factor, warm_iter, max_iter, lr, checkpoint,
+                beta_1, beta_2):
+        """The path-following loop (linear.py:441-453) over a batch whose cov is set: the stages in
+        lockstep, within a stage every problem that has not yet succeeded re-run with its own
+        halved lr and enlarged s.  Leaves W_est (unthresholded) and minimize_log."""
+        self.W_est = np.zeros((B, d, d))
+        self.minimize_log = [[] for _ in range(B)]
+        s_of = [list(s0) for _ in range(B)]  # each problem enlarges its own s on a failure
+        mu = mu_init
+        for i in range(T):
+            self.vprint(f'\nIteration -- {i+1}:')
+            inner_iters = int(max_iter) if i == T - 1 else int(warm_iter)
+            lr_of = [lr] * B
+            todo = np.ones(B, dtype=bool)
+            batch.set_masks(*self._masks(mu, lam, inc, exc, B, d))
+            while todo.any():
+                t0 = time.time()
+                W_try = self.W_est.copy()
+                s_now = [s_of[b][i] for b in range(B)]
+                res = batch.minimize(W_try, mu, s_now, lr_of, lam, inner_iters, beta_1=beta_1, beta_2=beta_2,
+                                     checkpoint=checkpoint, active=todo)
+                seconds = time.time() - t0
+                singular = [b for b in np.flatnonzero(todo) if res[b].status == _lib.ST_SINGULAR]
+                if singular:
+                    raise np.linalg.LinAlgError(
+                        f"singular matrix: inverse of sI - W*W is not finite in problems {singular}")
+                for b in np.flatnonzero(todo):
+                    r = res[b]
+                    self.minimize_log[b].append(dict(mu=mu, s=s_now[b], lr=lr_of[b], max_iter=inner_iters,
+                                                     iters=r.iters, success=r.success, early_stop=r.early_stop,
+                                                     halvings=r.halvings, seconds=seconds))
+                    if r.success:
+                        self.W_est[b] = W_try[b]
+                        todo[b] = False
+                    else:  # this problem alone: a smaller lr and a larger s (linear.py:449-452)
+                        self.vprint(f'problem {b}: W went out of domain for s={s_now[b]} at iteration '
+                                    f'{r.iters + 1}; retrying with larger s')
+                        lr_of[b] *= 0.5
+                        s_of[b][i] += 0.1
+            mu *= mu_factor
+
+    def _finals(self, B, d):
+        """h and the score of every problem's W_est on self.cov[b], from one ordinary solver: the
+        kernels of the single fit."""
+        self.h_final, self.score_final = np.empty(B), np.empty(B)
+        solver = self._solver_factory(d, "l2", "cov", device=self.device)
+        try:
+            last = None
+            for b in range(B):
+                if self.cov[b] is not last:
+                    solver.set_cov(self.cov[b])
+                    last = self.cov[b]
+                self.h_final[b], _ = solver.h_value(self.W_est[b], 1.0, grad=True)
+                self.score_final[b], _ = solver.score_value(self.W_est[b])
+        finally:
+            solver.close()
+
+    # --------------------------------------------------------------- bootstrap
+    _FIT_DEFAULTS = dict(w_threshold=0.3, T=5, mu_init=1.0, mu_factor=0.1, s=[1.0, .9, .8, .7, .6], warm_iter=3e4,
+                         max_iter=6e4, lr=0.0003, checkpoint=1000, beta_1=0.99, beta_2=0.999, exclude_edges=None,
+                         include_edges=None)
+
+    def bootstrap(self, X, n_boot: int, lambda1: float = 0.03, seed: int = 0, **fit_kwargs) -> np.ndarray:
+        """Edge frequencies over `n_boot` bootstrap resamples of one X, the resampling and the
+        covariances on the device (`HipBatch.boot_cov`, csrc/boot.hip).
+
+        X: one (n, d) float64 host array or device tensor, d <= 64; it is not modified.  Replicate
+        b fits the rows `X[bootstrap_indices(seed, b, n)]`, so `DagmaLinear('l2').fit(X[idx].copy(),
+        lambda1, ...)` reproduces any one of them (up to the rounding of its covariance).  lambda1:
+        a scalar.  fit_kwargs: `fit`'s other arguments, with its defaults.
+
+        Leaves W_boot (n_boot, d, d; thresholded), edge_freq = (W_boot != 0).mean(0) (also
+        returned), boot_seed, and h_final, score_final, minimize_log and fit_timing as `fit`."""
+        t_start = time.perf_counter()
+        unknown = sorted(set(fit_kwargs) - set(self._FIT_DEFAULTS))
+        if unknown:
+            raise TypeError(f"bootstrap got unexpected arguments {unknown}")
+        kw = dict(self._FIT_DEFAULTS, **fit_kwargs)
+        if np.ndim(lambda1) != 0:
+            raise ValueError("bootstrap takes one scalar lambda1")
+        if isinstance(n_boot, bool) or int(n_boot) != n_boot or not 1 <= int(n_boot) <= HipBatch.MAX_B:
+            raise ValueError(f"bootstrap needs 1 <= n_boot <= {HipBatch.MAX_B}, got {n_boot}")
+        if is_device_tensor(X):
+            import torch
+            if X.dim() != 2 or X.dtype != torch.float64 or X.stride(1) != 1:
+                raise ValueError("X must be a 2-d float64 tensor (n x d) with unit column stride")
+        elif hasattr(X, "data_ptr") or not isinstance(X, np.ndarray) or X.dtype != np.float64 or X.ndim != 2:
+            raise ValueError("X must be one 2-d float64 host array or device tensor (n x d)")
+        elif X.strides[1] != 8:
+            X = np.ascontiguousarray(X)
+        n, d = int(X.shape[0]), int(X.shape[1])
+        if d < 1 or d > HipBatch.MAX_D:
+            raise ValueError(f"DagmaLinearBatch needs 1 <= d <= {HipBatch.MAX_D}, got d = {d}")
+        if n < 1 or n >= 2**31:
+            raise ValueError(f"bootstrap needs 1 <= n < 2^31 rows, got {n}")
+        B, T, lam = int(n_boot), int(kw["T"]), [float(lambda1)] * int(n_boot)
+        s0 = self._s_list(kw["s"], T)
+        inc, exc = _edges(kw["include_edges"]), _edges(kw["exclude_edges"])
+        self.B, self.d, self.lambda1, self.checkpoint, self.boot_seed = B, d, lam, kw["checkpoint"], int(seed)
+        batch = self._batch_factory(d, B, device=self.device)
+        try:
+            batch.boot_cov(X, int(seed))
+            t_prep = time.perf_counter()
+            self._stages(batch, B, d, lam, T, s0, inc, exc, kw["mu_init"], kw["mu_factor"], kw["warm_iter"],
+                         kw["max_iter"], kw["lr"], kw["checkpoint"], kw["beta_1"], kw["beta_2"])
+            covs = batch.get_cov()
+        finally:
+            batch.close()
+        t_loop = time.perf_counter()
+        self.cov = [covs[b] for b in range(B)]
+        self._finals(B, d)
+        self.fit_timing = dict(prep_s=t_prep - t_start, loop_s=t_loop - t_prep,
+                               final_s=time.perf_counter() - t_loop, cov_on="device")
+        self.W_est[np.abs(self.W_est) < kw["w_threshold"]] = 0
+        self.W_boot = self.W_est
+        self.edge_freq = (self.W_boot != 0).mean(axis=0)
+        return self.edge_freq
+
     # --------------------------------------------------------------------- fit
     def fit(self, Xs, lambda1: typing.Union[float, typing.Sequence[float]] = 0.03, w_threshold: float = 0.3,
             T: int = 5, mu_init: float = 1.0, mu_factor: float = 0.1,
@@ -135,12 +303,7 @@ class DagmaLinearBatch:
         t_start = time.perf_counter()
         xs, lam, d = self._problems(Xs, lambda1)
         B, T = len(xs), int(T)
-        if isinstance(s, (list, tuple)):
-            s0 = list(s) + max(0, T - len(s)) * [s[-1]]  # linear.py:431-434
-        elif type(s) in (int, float):
-            s0 = T * [s]
-        else:
-            raise ValueError("s should be a list, int, or float.")
+        s0 = self._s_list(s, T)
         inc, exc = _edges(include_edges), _edges(exclude_edges)
         self.B, self.d, self.lambda1, self.checkpoint = B, d, lam, checkpoint
         # centring and cov = X^T X / n on the host, once per distinct X (linear.py:411, 428)
@@ -154,57 +317,12 @@ class DagmaLinearBatch:
         try:
             batch.set_cov(np.stack(self.cov))
             t_prep = time.perf_counter()
-            self.W_est = np.zeros((B, d, d))
-            self.minimize_log = [[] for _ in range(B)]
-            s_of = [list(s0) for _ in range(B)]  # each problem enlarges its own s on a failure
-            mu = mu_init
-            for i in range(T):
-                self.vprint(f'\nIteration -- {i+1}:')
-                inner_iters = int(max_iter) if i == T - 1 else int(warm_iter)
-                lr_of = [lr] * B
-                todo = np.ones(B, dtype=bool)
-                batch.set_masks(*self._masks(mu, lam, inc, exc, B, d))
-                while todo.any():
-                    t0 = time.time()
-                    W_try = self.W_est.copy()
-                    s_now = [s_of[b][i] for b in range(B)]
-                    res = batch.minimize(W_try, mu, s_now, lr_of, lam, inner_iters, beta_1=beta_1, beta_2=beta_2,
-                                         checkpoint=checkpoint, active=todo)
-                    seconds = time.time() - t0
-                    singular = [b for b in np.flatnonzero(todo) if res[b].status == _lib.ST_SINGULAR]
-                    if singular:
-                        raise np.linalg.LinAlgError(
-                            f"singular matrix: inverse of sI - W*W is not finite in problems {singular}")
-                    for b in np.flatnonzero(todo):
-                        r = res[b]
-                        self.minimize_log[b].append(dict(mu=mu, s=s_now[b], lr=lr_of[b], max_iter=inner_iters,
-                                                         iters=r.iters, success=r.success, early_stop=r.early_stop,
-                                                         halvings=r.halvings, seconds=seconds))
-                        if r.success:
-                            self.W_est[b] = W_try[b]
-                            todo[b] = False
-                        else:  # this problem alone: a smaller lr and a larger s (linear.py:449-452)
-                            self.vprint(f'problem {b}: W went out of domain for s={s_now[b]} at iteration '
-                                        f'{r.iters + 1}; retrying with larger s')
-                            lr_of[b] *= 0.5
-                            s_of[b][i] += 0.1
-                mu *= mu_factor
+            self._stages(batch, B, d, lam, T, s0, inc, exc, mu_init, mu_factor, warm_iter, max_iter, lr, checkpoint,
+                         beta_1, beta_2)
         finally:
             batch.close()
         t_loop = time.perf_counter()
-        # h and the score of every problem's W from one ordinary solver: the kernels of the single fit
-        self.h_final, self.score_final = np.empty(B), np.empty(B)
-        solver = self._solver_factory(d, "l2", "cov", device=self.device)
-        try:
-            last = None
-            for b in range(B):
-                if self.cov[b] is not last:
-                    solver.set_cov(self.cov[b])
-                    last = self.cov[b]
-                self.h_final[b], _ = solver.h_value(self.W_est[b], 1.0, grad=True)
-                self.score_final[b], _ = solver.score_value(self.W_est[b])
-        finally:
-            solver.close()
+        self._finals(B, d)
         self.fit_timing = dict(prep_s=t_prep - t_start, loop_s=t_loop - t_prep,
                                final_s=time.perf_counter() - t_loop, cov_on="host")
         self.W_est[np.abs(self.W_est) < w_threshold] = 0

@@ -16,8 +16,7 @@
 #include <string>
 #include <vector>
 
-#include "../../include/midagma_hip.h"
-#include "solver_impl.h"
+#include "batch_impl.h"
 
 namespace {
 
@@ -36,7 +35,7 @@ __global__ void batch_pad_kernel(const double* __restrict__ src, double* __restr
 }
 __global__ void batch_unpad_kernel(const double* __restrict__ src, double* __restrict__ dst, int64_t d, int64_t D,
                                    const int32_t* __restrict__ index) {
-  const int64_t b = index[blockIdx.y];
+  const int64_t b = index ? index[blockIdx.y] : blockIdx.y;
   const int64_t e = (int64_t)blockIdx.x * NTHREADS + threadIdx.x;
   if (e >= d * d) return;
   dst[b * d * d + e] = src[b * D * D + (e / d) * D + e % d];
@@ -64,161 +63,129 @@ bool finite_block(const double* p, int64_t count) {
 
 }  // namespace
 
-struct midagma_batch {
-  int64_t d = 0, D = 0, B = 0;
-  int device = 0;
-  hipStream_t stream = nullptr;
-  std::string err;
-
-  DevBuf<> W, m, v, cov, covs, minc, mexc, carry, pstore, bc_table;
-  DevBuf<> stage;  // B x d x d: the compact host layout on the device
-  DevBuf<Params> d_params;
-  DevBuf<State> d_state;
-  DevBuf<CkptRec> d_ckpt;
-  DevBuf<int32_t> d_index;
-  PinBuf<Params> h_params;  // host mirrors of d_params, d_state; the index list of the next launch
-  PinBuf<State> h_state;
-  PinBuf<int32_t> h_index;
-  int64_t ckpt_cap = 0, bc_len = 0;
-  double bc_b1 = -1, bc_b2 = -1;
-  bool has_cov = false, has_inc = false, has_exc = false;
-  std::vector<uint8_t> last_active;  // the problems of the last minimize call (their checkpoints)
-
-  ~midagma_batch() {
-    if (stream) {
-      (void)hipStreamSynchronize(stream);
-      (void)hipStreamDestroy(stream);
-    }
+void midagma_batch::alloc() {
+  const size_t DD = (size_t)D * D, ds = (size_t)small_block(d);
+  for (DevBuf<>* b : {&W, &m, &v, &cov, &covs}) b->alloc((size_t)B * DD);
+  carry.alloc((size_t)B * (NORM_FIELDS + 1));
+  pstore.alloc((size_t)B * 2 * ds * ds);
+  stage.alloc((size_t)B * d * d);
+  d_params.alloc(B);
+  d_state.alloc(B);
+  d_index.alloc(B);
+  h_params.alloc(B);
+  h_state.alloc(B);
+  h_index.alloc(B);
+  for (int64_t b = 0; b < B; ++b) {
+    h_params.p[b] = Params{};
+    h_state.p[b] = State{};
   }
+  last_active.assign(B, 0);
+}
 
-  dim3 grid(int64_t elems, int64_t problems) const {
-    return dim3((unsigned)((elems + NTHREADS - 1) / NTHREADS), (unsigned)problems);
+void midagma_batch::upload_all(DevBuf<>& dst, const double* src) {
+  HIP_TRY(hipMemcpyAsync(stage.p, src, (size_t)B * d * d * sizeof(double), hipMemcpyHostToDevice, stream));
+  hipLaunchKernelGGL(batch_pad_kernel, grid(D * D, B), dim3(NTHREADS), 0, stream, stage.p, dst.p, d, D, nullptr);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipStreamSynchronize(stream));
+}
+
+void midagma_batch::download_all(const DevBuf<>& src, double* dst) {
+  hipLaunchKernelGGL(batch_unpad_kernel, grid(d * d, B), dim3(NTHREADS), 0, stream, src.p, stage.p, d, D, nullptr);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpyAsync(dst, stage.p, (size_t)B * d * d * sizeof(double), hipMemcpyDeviceToHost, stream));
+  HIP_TRY(hipStreamSynchronize(stream));
+}
+
+void midagma_batch::ensure_tables(double b1, double b2, int64_t max_iter, int64_t checkpoint) {
+  if (!(b1 == bc_b1 && b2 == bc_b2 && max_iter <= bc_len)) {  // midagma_solver::ensure_bc_table
+    const int64_t len = std::max<int64_t>(max_iter, 1);
+    const std::vector<double> t = bc_table_values(b1, b2, len);
+    bc_table.alloc(2 * len);
+    HIP_TRY(hipMemcpy(bc_table.p, t.data(), t.size() * sizeof(double), hipMemcpyHostToDevice));
+    bc_b1 = b1;
+    bc_b2 = b2;
+    bc_len = len;
   }
-
-  void alloc() {
-    const size_t DD = (size_t)D * D, ds = (size_t)small_block(d);
-    for (DevBuf<>* b : {&W, &m, &v, &cov, &covs}) b->alloc((size_t)B * DD);
-    carry.alloc((size_t)B * (NORM_FIELDS + 1));
-    pstore.alloc((size_t)B * 2 * ds * ds);
-    stage.alloc((size_t)B * d * d);
-    d_params.alloc(B);
-    d_state.alloc(B);
-    d_index.alloc(B);
-    h_params.alloc(B);
-    h_state.alloc(B);
-    h_index.alloc(B);
-    for (int64_t b = 0; b < B; ++b) {
-      h_params.p[b] = Params{};
-      h_state.p[b] = State{};
-    }
-    last_active.assign(B, 0);
+  const int64_t need = max_iter / checkpoint + 4;  // midagma_solver::ensure_ckpt
+  if (need > ckpt_cap) {
+    d_ckpt.alloc((size_t)B * need);
+    ckpt_cap = need;
   }
+}
 
-  // host B x d x d -> every problem's padded slab of dst
-  void upload_all(DevBuf<>& dst, const double* src) {
-    HIP_TRY(hipMemcpyAsync(stage.p, src, (size_t)B * d * d * sizeof(double), hipMemcpyHostToDevice, stream));
-    hipLaunchKernelGGL(batch_pad_kernel, grid(D * D, B), dim3(NTHREADS), 0, stream, stage.p, dst.p, d, D, nullptr);
-    HIP_TRY(hipGetLastError());
+void midagma_batch::minimize(double* Wh, const double* mu, const double* s_dom, const double* lr,
+                             const double* lambda1, int64_t max_iter, double tol, double b1, double b2,
+                             int64_t checkpoint, const uint8_t* active, midagma_result* res) {
+  ensure_tables(b1, b2, max_iter, checkpoint);
+  int64_t n_run = 0;
+  for (int64_t b = 0; b < B; ++b) {
+    last_active[b] = !active || active[b];
+    if (!last_active[b]) continue;
+    h_params.p[b] = cov_l2_params(d, D, mu[b], s_dom[b], lambda1[b], tol, b1, b2, max_iter, checkpoint, bc_len,
+                                  has_inc, has_exc);
+    h_state.p[b] = initial_state(lr[b]);
+    h_index.p[n_run++] = (int32_t)b;
+  }
+  if (n_run == 0) return;
+  const int64_t DD = D * D;
+  HIP_TRY(hipMemcpyAsync(d_params.p, h_params.p, B * sizeof(Params), hipMemcpyHostToDevice, stream));
+  HIP_TRY(hipMemcpyAsync(d_state.p, h_state.p, B * sizeof(State), hipMemcpyHostToDevice, stream));
+  HIP_TRY(hipMemcpyAsync(d_index.p, h_index.p, n_run * sizeof(int32_t), hipMemcpyHostToDevice, stream));
+  // (the stage keeps the caller's W of the inactive problems, which the download hands back)
+  HIP_TRY(hipMemcpyAsync(stage.p, Wh, (size_t)B * d * d * sizeof(double), hipMemcpyHostToDevice, stream));
+  hipLaunchKernelGGL(batch_pad_kernel, grid(DD, n_run), dim3(NTHREADS), 0, stream, stage.p, W.p, d, D, d_index.p);
+  hipLaunchKernelGGL(batch_begin_kernel, grid(DD, n_run), dim3(NTHREADS), 0, stream, d_params.p, cov.p, covs.p, m.p,
+                     v.p, carry.p, DD, d_index.p);
+  HIP_TRY(hipGetLastError());
+  const int64_t n_active = n_run;
+
+  // drive_small over the problems still running: one launch of up to kSmallBatch slots, one
+  // copy of every State, one sync
+  const int64_t cap = slot_cap(max_iter, checkpoint);
+  for (int64_t launched = 0; n_run > 0;) {
+    const int64_t slots = small_next_batch(-1, launched, cap, midagma_solver::kSmallBatch);
+    launch_small_minimize(d_params.p, d_state.p, W.p, m.p, v.p, covs.p, has_inc ? minc.p : nullptr,
+                          has_exc ? mexc.p : nullptr, bc_table.p, d_ckpt.p, ckpt_cap, carry.p, pstore.p, d, slots,
+                          stream, nullptr, false, d_index.p, n_run);
+    launched += slots;
+    HIP_TRY(hipMemcpyAsync(h_state.p, d_state.p, B * sizeof(State), hipMemcpyDeviceToHost, stream));
     HIP_TRY(hipStreamSynchronize(stream));
+    int64_t still = 0;
+    for (int64_t k = 0; k < n_run; ++k) {
+      const int32_t b = h_index.p[k];
+      if (h_state.p[b].status == ST_RUNNING) h_index.p[still++] = b;
+    }
+    n_run = still;
+    if (n_run > 0)
+      HIP_TRY(hipMemcpyAsync(d_index.p, h_index.p, n_run * sizeof(int32_t), hipMemcpyHostToDevice, stream));
   }
 
-  void ensure_tables(double b1, double b2, int64_t max_iter, int64_t checkpoint) {
-    if (!(b1 == bc_b1 && b2 == bc_b2 && max_iter <= bc_len)) {  // midagma_solver::ensure_bc_table
-      const int64_t len = std::max<int64_t>(max_iter, 1);
-      const std::vector<double> t = bc_table_values(b1, b2, len);
-      bc_table.alloc(2 * len);
-      HIP_TRY(hipMemcpy(bc_table.p, t.data(), t.size() * sizeof(double), hipMemcpyHostToDevice));
-      bc_b1 = b1;
-      bc_b2 = b2;
-      bc_len = len;
-    }
-    const int64_t need = max_iter / checkpoint + 4;  // midagma_solver::ensure_ckpt
-    if (need > ckpt_cap) {
-      d_ckpt.alloc((size_t)B * need);
-      ckpt_cap = need;
-    }
-  }
+  // hand back the active problems' W (the index list of the call again)
+  int64_t k = 0;
+  for (int64_t b = 0; b < B; ++b)
+    if (last_active[b]) h_index.p[k++] = (int32_t)b;
+  HIP_TRY(hipMemcpyAsync(d_index.p, h_index.p, n_active * sizeof(int32_t), hipMemcpyHostToDevice, stream));
+  hipLaunchKernelGGL(batch_unpad_kernel, grid(d * d, n_active), dim3(NTHREADS), 0, stream, W.p, stage.p, d, D,
+                     d_index.p);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpyAsync(Wh, stage.p, (size_t)B * d * d * sizeof(double), hipMemcpyDeviceToHost, stream));
+  HIP_TRY(hipStreamSynchronize(stream));
+  for (int64_t b = 0; b < B; ++b)
+    if (last_active[b]) midagma_solver::fill_result(h_state.p[b], &res[b]);
+}
 
-  void minimize(double* Wh, const double* mu, const double* s_dom, const double* lr, const double* lambda1,
-                int64_t max_iter, double tol, double b1, double b2, int64_t checkpoint, const uint8_t* active,
-                midagma_result* res) {
-    ensure_tables(b1, b2, max_iter, checkpoint);
-    int64_t n_run = 0;
-    for (int64_t b = 0; b < B; ++b) {
-      last_active[b] = !active || active[b];
-      if (!last_active[b]) continue;
-      h_params.p[b] = cov_l2_params(d, D, mu[b], s_dom[b], lambda1[b], tol, b1, b2, max_iter, checkpoint, bc_len,
-                                    has_inc, has_exc);
-      h_state.p[b] = initial_state(lr[b]);
-      h_index.p[n_run++] = (int32_t)b;
-    }
-    if (n_run == 0) return;
-    const int64_t DD = D * D;
-    HIP_TRY(hipMemcpyAsync(d_params.p, h_params.p, B * sizeof(Params), hipMemcpyHostToDevice, stream));
-    HIP_TRY(hipMemcpyAsync(d_state.p, h_state.p, B * sizeof(State), hipMemcpyHostToDevice, stream));
-    HIP_TRY(hipMemcpyAsync(d_index.p, h_index.p, n_run * sizeof(int32_t), hipMemcpyHostToDevice, stream));
-    // (the stage keeps the caller's W of the inactive problems, which the download hands back)
-    HIP_TRY(hipMemcpyAsync(stage.p, Wh, (size_t)B * d * d * sizeof(double), hipMemcpyHostToDevice, stream));
-    hipLaunchKernelGGL(batch_pad_kernel, grid(DD, n_run), dim3(NTHREADS), 0, stream, stage.p, W.p, d, D, d_index.p);
-    hipLaunchKernelGGL(batch_begin_kernel, grid(DD, n_run), dim3(NTHREADS), 0, stream, d_params.p, cov.p, covs.p, m.p,
-                       v.p, carry.p, DD, d_index.p);
-    HIP_TRY(hipGetLastError());
-    const int64_t n_active = n_run;
-
-    // drive_small over the problems still running: one launch of up to kSmallBatch slots, one
-    // copy of every State, one sync
-    const int64_t cap = slot_cap(max_iter, checkpoint);
-    for (int64_t launched = 0; n_run > 0;) {
-      const int64_t slots = small_next_batch(-1, launched, cap, midagma_solver::kSmallBatch);
-      launch_small_minimize(d_params.p, d_state.p, W.p, m.p, v.p, covs.p, has_inc ? minc.p : nullptr,
-                            has_exc ? mexc.p : nullptr, bc_table.p, d_ckpt.p, ckpt_cap, carry.p, pstore.p, d, slots,
-                            stream, nullptr, false, d_index.p, n_run);
-      launched += slots;
-      HIP_TRY(hipMemcpyAsync(h_state.p, d_state.p, B * sizeof(State), hipMemcpyDeviceToHost, stream));
-      HIP_TRY(hipStreamSynchronize(stream));
-      int64_t still = 0;
-      for (int64_t k = 0; k < n_run; ++k) {
-        const int32_t b = h_index.p[k];
-        if (h_state.p[b].status == ST_RUNNING) h_index.p[still++] = b;
-      }
-      n_run = still;
-      if (n_run > 0)
-        HIP_TRY(hipMemcpyAsync(d_index.p, h_index.p, n_run * sizeof(int32_t), hipMemcpyHostToDevice, stream));
-    }
-
-    // hand back the active problems' W (the index list of the call again)
-    int64_t k = 0;
-    for (int64_t b = 0; b < B; ++b)
-      if (last_active[b]) h_index.p[k++] = (int32_t)b;
-    HIP_TRY(hipMemcpyAsync(d_index.p, h_index.p, n_active * sizeof(int32_t), hipMemcpyHostToDevice, stream));
-    hipLaunchKernelGGL(batch_unpad_kernel, grid(d * d, n_active), dim3(NTHREADS), 0, stream, W.p, stage.p, d, D,
-                       d_index.p);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(Wh, stage.p, (size_t)B * d * d * sizeof(double), hipMemcpyDeviceToHost, stream));
-    HIP_TRY(hipStreamSynchronize(stream));
-    for (int64_t b = 0; b < B; ++b)
-      if (last_active[b]) midagma_solver::fill_result(h_state.p[b], &res[b]);
-  }
-};
-
-namespace {
-
-int bfail(midagma_batch* h, int code, const std::string& msg) {
+int midagma::batch_fail(midagma_batch* h, int code, const std::string& msg) {
   (h ? h->err : g_batch_err) = msg;
   return code;
 }
 
+namespace {
+
+int bfail(midagma_batch* h, int code, const std::string& msg) { return batch_fail(h, code, msg); }
+
 template <class F>
 int bguarded(midagma_batch* h, F&& f) {
-  try {
-    if (h) HIP_TRY(hipSetDevice(h->device));
-    f();
-    return MIDAGMA_OK;
-  } catch (...) {
-    std::string msg;
-    const int rc = classify(std::current_exception(), msg);
-    return bfail(h, rc, msg);
-  }
+  return batch_guarded(h, std::forward<F>(f));
 }
 
 }  // namespace

@@ -1,0 +1,78 @@
+// The batch of small-d problems behind the midagma_batch_* and midagma_boot_* entries: the handle
+// that batch.hip (create, set_cov, masks, minimize) and boot.hip (the bootstrap covariances written
+// into the handle's cov slabs) share, and the error plumbing of their entry points.
+#pragma once
+
+#include <hip/hip_runtime.h>
+
+#include <exception>
+#include <string>
+#include <vector>
+
+#include "../../include/midagma_hip.h"
+#include "solver_impl.h"
+
+struct midagma_batch {
+  int64_t d = 0, D = 0, B = 0;
+  int device = 0;
+  hipStream_t stream = nullptr;
+  std::string err;
+
+  DevBuf<> W, m, v, cov, covs, minc, mexc, carry, pstore, bc_table;
+  DevBuf<> stage;  // B x d x d: the compact host layout on the device
+  DevBuf<Params> d_params;
+  DevBuf<State> d_state;
+  DevBuf<CkptRec> d_ckpt;
+  DevBuf<int32_t> d_index;
+  PinBuf<Params> h_params;  // host mirrors of d_params, d_state; the index list of the next launch
+  PinBuf<State> h_state;
+  PinBuf<int32_t> h_index;
+  int64_t ckpt_cap = 0, bc_len = 0;
+  double bc_b1 = -1, bc_b2 = -1;
+  bool has_cov = false, has_inc = false, has_exc = false;
+  std::vector<uint8_t> last_active;  // the problems of the last minimize call (their checkpoints)
+  double boot_ms[4] = {0, 0, 0, 0};  // the last boot_cov: centring, counts, Gram, finish (device events)
+
+  ~midagma_batch() {
+    if (stream) {
+      (void)hipStreamSynchronize(stream);
+      (void)hipStreamDestroy(stream);
+    }
+  }
+
+  dim3 grid(int64_t elems, int64_t problems) const {
+    return dim3((unsigned)((elems + NTHREADS - 1) / NTHREADS), (unsigned)problems);
+  }
+
+  // batch.hip
+  void alloc();
+  void upload_all(DevBuf<>& dst, const double* src);  // host B x d x d -> every problem's padded slab of dst
+  void download_all(const DevBuf<>& src, double* dst);  // every problem's padded slab of src -> host B x d x d
+  void ensure_tables(double b1, double b2, int64_t max_iter, int64_t checkpoint);
+  void minimize(double* Wh, const double* mu, const double* s_dom, const double* lr, const double* lambda1,
+                int64_t max_iter, double tol, double b1, double b2, int64_t checkpoint, const uint8_t* active,
+                midagma_result* res);
+};
+
+namespace midagma {
+
+constexpr const char* kBatchNonFinite = "array must not contain infs or NaNs";
+
+// the message of a failed entry: on the handle, or thread-local for a call without one
+// (midagma_batch_last_error reads either)
+int batch_fail(midagma_batch* h, int code, const std::string& msg);
+
+template <class F>
+int batch_guarded(midagma_batch* h, F&& f) {
+  try {
+    if (h) HIP_TRY(hipSetDevice(h->device));
+    f();
+    return MIDAGMA_OK;
+  } catch (...) {
+    std::string msg;
+    const int rc = classify(std::current_exception(), msg);
+    return batch_fail(h, rc, msg);
+  }
+}
+
+}  // namespace midagma

@@ -816,6 +816,43 @@ class HipBatch:
         self._check(self.L.midagma_batch_set_cov(self.h, dptr(cov)), self.h, "batch_set_cov")
         self._has_cov = True
 
+    def boot_cov(self, X, seed: int, first: int = 0, budget_bytes: int | None = None):
+        """Problem b's cov <- the covariance of bootstrap replicate `first + b` of `seed` of X
+        (`midagma_amd.batch.bootstrap_indices`), formed on the device from one X (csrc/boot.hip).
+        X: (n, d) float64, a host array or a device tensor (its row stride is kept); it is not
+        written.  budget_bytes: the scratch of one chunk of replicates (None: 1 GiB).  ValueError
+        on inf / nan."""
+        n, d, ld = _rows(X)
+        if d != self.d:
+            raise ValueError(f"X must have {self.d} columns, got {d}")
+        on_dev = is_device_tensor(X)
+        if on_dev:
+            import torch
+            if X.device.index is not None and X.device.index != self.device:
+                raise ValueError(f"X lies on device {X.device.index}, the batch on {self.device}")
+            torch.cuda.current_stream(X.device).synchronize()  # (the batch runs on its own stream)
+            src = C.c_void_p(X.data_ptr())
+        elif hasattr(X, "data_ptr"):
+            raise ValueError("X must be a host array or a device tensor")
+        else:
+            src = X.ctypes.data_as(C.c_void_p)
+        rc = self.L.midagma_boot_cov(self.h, src, n, ld, 1 if on_dev else 0, C.c_uint64(int(seed) & (2**64 - 1)),
+                                     int(first), 0 if budget_bytes is None else int(budget_bytes))
+        self._check(rc, self.h, "boot_cov")
+        self._has_cov = True
+
+    def get_cov(self) -> np.ndarray:
+        """The problems' current covariances, (B, d, d)."""
+        out = np.empty((self.B, self.d, self.d))
+        self._check(self.L.midagma_boot_get_cov(self.h, dptr(out)), self.h, "boot_get_cov")
+        return out
+
+    def boot_profile(self) -> dict:
+        """Device-event times (ms) of the last `boot_cov`, summed over its chunks."""
+        ms = np.zeros(4)
+        self._check(self.L.midagma_boot_profile(self.h, dptr(ms)), self.h, "boot_profile")
+        return dict(zip(("center_ms", "counts_ms", "gram_ms", "finish_ms"), ms.tolist()))
+
     def set_masks(self, mask_inc, mask_exc):
         """B x d x d each, or None to switch that mask off (linear.py:217-222, per problem)."""
         mi = None if mask_inc is None else self._stack(mask_inc, "mask_inc")
