@@ -201,7 +201,15 @@ int midagma_sync(midagma_solver* s);
  * slot (GJ path), [4] data-mode X(I-W) GEMM, [5] data-mode X^T Y GEMM, [6] cov-mode fast
  * blocked inverse, [7] whole fast slot ([6], [7]: 0 if not available, -1 if the fast path
  * handed back).  ms_out holds 8 doubles.  Advances the state by up to 3 reps + 1 slots. */
+/* ([5] is the X^T Y GEMM with the combine of its split-K slices, in either form below.) */
 int midagma_profile_parts(midagma_solver* s, int reps, double* ms_out);
+/* The form of the data-mode X^T Y GEMM chosen by the last midagma_set_data: 1 the classical
+ * split-K GEMM, 2 one level of Strassen (seven half-size products instead of eight; D % 256 == 0,
+ * long row shards, and device memory for the five operand sums of X, 1.25 x the size of X: 10 GB
+ * at d = 1000, n = 1e6; when memory is short the classical form is kept).  0: no data set.  The two
+ * forms agree to rounding, not bit for bit; each is deterministic and identical across ranks with
+ * equal shards.  Purely additive: MIDAGMA_ABI_VERSION stays 11. */
+int midagma_xty_form(const midagma_solver* s);
 int midagma_step_finish(midagma_solver* s);
 int midagma_poll(midagma_solver* s, midagma_result* res); /* synchronizes */
 int midagma_end(midagma_solver* s, double* W, midagma_result* res);

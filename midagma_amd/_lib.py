@@ -84,6 +84,7 @@ EXPORTED = {
     "midagma_run_slots": (_int, [_vp, _i64]),
     "midagma_sync": (_int, [_vp]),
     "midagma_profile_parts": (_int, [_vp, _int, _dp]),
+    "midagma_xty_form": (_int, [_vp]),
     "midagma_step_finish": (_int, [_vp]),
     "midagma_poll": (_int, [_vp, C.POINTER(MidagmaResult)]),
     "midagma_end": (_int, [_vp, _dp, C.POINTER(MidagmaResult)]),

@@ -118,7 +118,7 @@ __device__ __forceinline__ int xcd_remap(int w, int nwg) {
 //   * B row kk of the next tile is reloaded into the same registers right after k-step kk's
 //     MFMAs are issued (no loop-carried register copies, which made hipcc drain the loads).
 // AMODE 1: A stored [k][m] (lda), AMODE 0: A stored [m][k].  BMODE B_IMINUS forms I - B in
-// registers.  Split-K: K slice z = t / (tiles_m tiles_n) of kslice, written to C + z slice_stride.
+// registers, B_PAIR B + sgn B2 (the Strassen form of X^T Y below).  Split-K: K slice z = t / (tiles_m tiles_n) of kslice, written to C + z slice_stride.
 // Measured at n = 1e6, d = 1000 (MI355X): X(I-W) from
 // X^T 29.1 ms (B = I - W pre-formed, 91.7% of FP64 peak), X^T Y split 16 28.7 ms (92.8%).
 constexpr int P_S = 132;
@@ -179,7 +179,8 @@ __device__ __forceinline__ void gemm_pipe_tile(int t, int64_t K, int64_t kslice,
                                                const double* __restrict__ B, int64_t ldb, double* __restrict__ C,
                                                int64_t ldc, int64_t slice_stride, double* __restrict__ loss_part,
                                                int64_t m_valid, int64_t n_valid, const State* __restrict__ st,
-                                               double* __restrict__ smem) {
+                                               double* __restrict__ smem, const double* __restrict__ B2 = nullptr,
+                                               double sgn = 0.0) {
   const int per_slice = tiles_m * tiles_n;
   const int z = t / per_slice, rem = t % per_slice;
   int bm, bn;
@@ -242,9 +243,14 @@ __device__ __forceinline__ void gemm_pipe_tile(int t, int64_t K, int64_t kslice,
   const int64_t a_kstride = AMODE ? lda : 1;
   const double* Bw = B + (int64_t)(4 * kq) * ldb + nw + 2 * r;
   const int fo = 4 * kq * P_S + r;  // fragment of block i at k-step kk: fo + kk P_S + 16 i
+  // B_PAIR: op(B) = B + sgn B2 (sgn = +-1, or 0 with B2 = B), the second operand loaded beside
+  // the first (same rows and columns, same ldb) and folded in before the MFMAs
+  constexpr int kBLoads = BMODE == B_PAIR ? 2 : 1;
+  const double* Bw2 = BMODE == B_PAIR ? B2 + (int64_t)(4 * kq) * ldb + nw + 2 * r : nullptr;
 
   double2 ra0, ra1, ra2, ra3;
   double2 fb[4];
+  double2 fb2[4];  // (B_PAIR only)
   double fa0[8], fa1[8];
 #define GP_LOADA(KT)                                                                              \
   {                                                                                               \
@@ -254,7 +260,11 @@ __device__ __forceinline__ void gemm_pipe_tile(int t, int64_t K, int64_t kslice,
     ra2 = *reinterpret_cast<const double2*>(ap_ + offA[2]);                                       \
     ra3 = *reinterpret_cast<const double2*>(ap_ + offA[3]);                                       \
   }
-#define GP_LOADB1(KT, KK) fb[KK] = *reinterpret_cast<const double2*>(Bw + ((KT) + (KK)) * ldb);
+#define GP_LOADB1(KT, KK)                                                                         \
+  {                                                                                               \
+    fb[KK] = *reinterpret_cast<const double2*>(Bw + ((KT) + (KK)) * ldb);                         \
+    if (BMODE == B_PAIR) fb2[KK] = *reinterpret_cast<const double2*>(Bw2 + ((KT) + (KK)) * ldb);  \
+  }
 #define GP_STA1(AS, I, RA)                                                                        \
   if (AMODE) {                                                                                    \
     *reinterpret_cast<double2*>((AS) + ldsA[I]) = RA;                                             \
@@ -277,6 +287,10 @@ __device__ __forceinline__ void gemm_pipe_tile(int t, int64_t K, int64_t kslice,
       const int64_t kg_ = (KT) + 4 * kq + (KK), ng_ = nw + 2 * r;                                 \
       b0_ = (kg_ == ng_ ? 1.0 : 0.0) - b0_;                                                       \
       b1_ = (kg_ == ng_ + 1 ? 1.0 : 0.0) - b1_;                                                   \
+    }                                                                                             \
+    if (BMODE == B_PAIR) {                                                                        \
+      b0_ = b0_ + sgn * fb2[KK].x;                                                                \
+      b1_ = b1_ + sgn * fb2[KK].y;                                                                \
     }                                                                                             \
     if (EPI == EPI_SUB_PRE) {                                                                     \
       b0_ = -b0_;                                                                                 \
@@ -399,19 +413,19 @@ __device__ __forceinline__ void gemm_pipe_tile(int t, int64_t K, int64_t kslice,
     GP_FRAG(fa1, As0, 1)  // k-step 0
     GP_MMA(fa0, kt, 0)
     GP_LOADB1(k1, 0)
-    GP_SCHED(0, 1)
+    GP_SCHED(0, kBLoads)
     __builtin_amdgcn_sched_barrier(0);
     GP_STOREA(As1)  // k-step 1: stage the next tile, then load the one after it
     GP_FRAG(fa0, As0, 2)
     GP_MMA(fa1, kt, 1)
     GP_LOADB1(k1, 1)
     GP_LOADA(k2)
-    GP_SCHED(AMODE ? 4 : 8, 5)
+    GP_SCHED(AMODE ? 4 : 8, 4 + kBLoads)
     __builtin_amdgcn_sched_barrier(0);
     GP_FRAG(fa1, As0, 3)  // k-step 2
     GP_MMA(fa0, kt, 2)
     GP_LOADB1(k1, 2)
-    GP_SCHED(0, 1)
+    GP_SCHED(0, kBLoads)
     __builtin_amdgcn_sched_barrier(0);
     __builtin_amdgcn_s_setprio(0);
     __syncthreads();
@@ -419,7 +433,7 @@ __device__ __forceinline__ void gemm_pipe_tile(int t, int64_t K, int64_t kslice,
     GP_FRAG(fa0, As1, 0)  // k-step 3, reading the next tile's first fragments meanwhile
     GP_MMA(fa1, kt, 3)
     GP_LOADB1(k1, 3)
-    GP_SCHED(0, 1)
+    GP_SCHED(0, kBLoads)
     __builtin_amdgcn_sched_barrier(0);
     double* tmp = As0;
     As0 = As1;
@@ -814,6 +828,155 @@ void launch_gemm_summed(GemmSpec gs, double* slices, double* out, const State* s
   gs.C = gs.split > 1 ? slices : out;
   launch_gemm(gs, st, stream);
   if (gs.split > 1) launch_sum_slices(slices, gs.split, gs.slice_stride, gs.M * gs.ldc, out, st, stream);
+}
+
+// ---- X^T Y by one level of Strassen (data mode) -----------------------
+// Z = A B with A = X^T (D x n_pad) and B = Y (n_pad x D), rows and columns of Z cut at H = D / 2
+// and the samples at h = n_pad / 2 (whole K tiles: n_pad % 128 == 0; padded rows are zero):
+//   A11 = X[0:h, 0:H]  A12 = X[h:, 0:H]  A21 = X[0:h, H:]  A22 = X[h:, H:]   (stored [k][m])
+//   B11 = Y[0:h, 0:H]  B12 = Y[0:h, H:]  B21 = Y[h:, 0:H]  B22 = Y[h:, H:]
+//   M1 = (A11 + A22)(B11 + B22)   M2 = (A21 + A22) B11   M3 = A11 (B12 - B22)   M4 = A22 (B21 - B11)
+//   M5 = (A11 + A12) B22          M6 = (A21 - A11)(B11 + B12)                   M7 = (A12 - A22)(B21 + B22)
+//   Z11 = M1 + M4 - M5 + M7   Z12 = M3 + M5   Z21 = M2 + M4   Z22 = M1 - M2 + M3 + M6
+// Seven H x H x h products instead of eight.  The five A sums depend on X alone and are formed
+// once per set_data (launch_xty_strassen_sums: h x H each, [k][m], one after the other); the B
+// pairs are formed in registers by the tile body's B_PAIR mode.  One launch runs the seven
+// products: workgroup w takes tile xcd_remap(w) of the (split-K slices) x 7 x (H / 128)^2 tiles,
+// K slice first, then product, then the product's tiles in the order of the classical launch
+// (measured at D = 1024, n = 1e6: 26.2 ms, against 27.3 ms product-major, where an XCD's resident
+// workgroups shared no B operand across products).  Product p's
+// slices go to parts + p nsplit H^2; strassen_combine_kernel sums each product's slices in slice
+// order and then the four signed quadrant sums in the order written above.  No workgroup waits
+// for another.
+struct StrassenProd {
+  const double* A;
+  int64_t lda;
+  const double* B1;
+  const double* B2;
+  double sgn;
+  double* C;
+};
+struct StrassenArgs {
+  StrassenProd p[7];
+  int64_t K, kslice, ldb, ldc, slice_stride;
+  int tm, nsplit;
+  const State* st;
+};
+
+__global__ __launch_bounds__(NTHREADS, 2) void xty_strassen_kernel(StrassenArgs a) {
+  if (a.st && a.st->status != ST_RUNNING) return;
+  extern __shared__ __attribute__((aligned(16))) double smem[];
+  // grid order: K slice, then product (table order), then the product's tiles, so the products
+  // of one K slice, which share their B operands, run side by side on one XCD
+  const int t = xcd_remap(blockIdx.x, gridDim.x);
+  const int per = a.tm * a.tm, z = t / (7 * per), r = t - z * 7 * per, p = r / per;
+  const StrassenProd& q = a.p[p];
+  gemm_pipe_tile<1, B_PAIR, EPI_STORE>(z * per + (r - p * per), a.K, a.kslice, a.tm, a.tm, q.A, q.lda, q.B1, a.ldb, q.C,
+                                       a.ldc, a.slice_stride, nullptr, 0, 0, a.st, smem, q.B2, q.sgn);
+}
+
+// S[0..5) = A11 + A22, A21 + A22, A11 + A12, A21 - A11, A12 - A22 (h x H each, consecutive)
+__global__ __launch_bounds__(NTHREADS) void strassen_sums_kernel(const double* __restrict__ X, int64_t D, int64_t h,
+                                                                 double* __restrict__ S) {
+  const int64_t H = D / 2, count = h * H;
+  for (int64_t e = (int64_t)blockIdx.x * NTHREADS + threadIdx.x; e < count; e += (int64_t)gridDim.x * NTHREADS) {
+    const int64_t k = e / H, m = e - k * H;
+    const double a11 = X[k * D + m], a21 = X[k * D + H + m];
+    const double a12 = X[(h + k) * D + m], a22 = X[(h + k) * D + H + m];
+    S[e] = a11 + a22;
+    S[count + e] = a21 + a22;
+    S[2 * count + e] = a11 + a12;
+    S[3 * count + e] = a21 - a11;
+    S[4 * count + e] = a12 - a22;
+  }
+}
+
+__global__ __launch_bounds__(NTHREADS) void strassen_combine_kernel(const double* __restrict__ parts, int nsplit,
+                                                                    int64_t H, double* __restrict__ out, int64_t ldo,
+                                                                    const State* __restrict__ st) {
+  if (st && st->status != ST_RUNNING) return;
+  const int64_t HH = H * H;
+  for (int64_t e = (int64_t)blockIdx.x * NTHREADS + threadIdx.x; e < HH; e += (int64_t)gridDim.x * NTHREADS) {
+    double m[7];
+#pragma unroll
+    for (int p = 0; p < 7; ++p) {
+      const double* pp = parts + (int64_t)p * nsplit * HH + e;
+      double acc = pp[0];
+      for (int z = 1; z < nsplit; ++z) acc += pp[z * HH];
+      m[p] = acc;
+    }
+    const int64_t i = e / H, j = e - i * H;
+    out[i * ldo + j] = ((m[0] + m[3]) - m[4]) + m[6];
+    out[i * ldo + H + j] = m[2] + m[4];
+    out[(H + i) * ldo + j] = m[1] + m[3];
+    out[(H + i) * ldo + H + j] = ((m[0] - m[1]) + m[2]) + m[5];
+  }
+}
+
+bool xty_strassen_shape(int64_t D, int64_t n_pad) {
+  return D >= 256 && D % 256 == 0 && n_pad >= 128 && n_pad % 128 == 0 && !knob_set("MIDAGMA_EXP_GEMM64");
+}
+
+static int64_t gcd64(int64_t a, int64_t b) { return b ? gcd64(b, a % b) : a; }
+
+XtyStrassenPlan xty_strassen_plan(int64_t D, int64_t n_pad, int split) {
+  if (!xty_strassen_shape(D, n_pad)) throw std::invalid_argument("xty_strassen_plan: shape");
+  const int64_t tiles = (D / 256) * (D / 256);
+  // the rule: 7 tiles nsplit workgroups a whole number of rounds of the 512 resident ones
+  // (256 CUs x 2; 7 is odd, so tiles nsplit % 512 == 0), D = 1024: 7 x 16 x 32 = 7 x 512
+  if (split < 1) split = (int)(512 / gcd64(512, tiles));
+  const SplitK sk = split_k(n_pad / 2, 16, split);
+  return {sk.nsplit, sk.kslice};
+}
+
+int64_t xty_strassen_sum_count(int64_t D, int64_t n_pad) { return 5 * (n_pad / 2) * (D / 2); }
+int64_t xty_strassen_part_count(int64_t D, int nsplit) { return 7 * (int64_t)nsplit * (D / 2) * (D / 2); }
+
+void launch_xty_strassen_sums(const double* X, int64_t D, int64_t n_pad, double* S, hipStream_t stream) {
+  if (!xty_strassen_shape(D, n_pad)) throw std::invalid_argument("launch_xty_strassen_sums: shape");
+  const int64_t count = (n_pad / 2) * (D / 2);
+  const int64_t blocks = std::min<int64_t>((count + NTHREADS - 1) / NTHREADS, 65536);
+  hipLaunchKernelGGL(strassen_sums_kernel, dim3((unsigned)blocks), dim3(NTHREADS), 0, stream, X, D, n_pad / 2, S);
+  HIP_TRY(hipGetLastError());
+}
+
+void launch_xty_strassen(const double* X, const double* S, const double* Y, int64_t D, int64_t n_pad, int split,
+                         double* parts, double* out, const State* st, hipStream_t stream) {
+  const XtyStrassenPlan pl = xty_strassen_plan(D, n_pad, split);
+  const int64_t H = D / 2, h = n_pad / 2, cnt = h * H;
+  const double *A11 = X, *A22 = X + h * D + H;
+  const double *B11 = Y, *B12 = Y + H, *B21 = Y + h * D, *B22 = Y + h * D + H;
+  StrassenArgs a{};
+  const StrassenProd prods[7] = {
+      {S, H, B11, B22, 1.0, nullptr},            // M1
+      {S + cnt, H, B11, B11, 0.0, nullptr},      // M2
+      {A11, D, B12, B22, -1.0, nullptr},         // M3
+      {A22, D, B21, B11, -1.0, nullptr},         // M4
+      {S + 2 * cnt, H, B22, B22, 0.0, nullptr},  // M5
+      {S + 3 * cnt, H, B11, B12, 1.0, nullptr},  // M6
+      {S + 4 * cnt, H, B21, B22, 1.0, nullptr},  // M7
+  };
+  // table order: M1 M2 M4 M6 (all read B11), then M3 M5 M7 (all read B22)
+  const int order[7] = {0, 1, 3, 5, 2, 4, 6};
+  for (int i = 0; i < 7; ++i) {
+    const int p = order[i];
+    a.p[i] = prods[p];
+    a.p[i].C = parts + (int64_t)p * pl.nsplit * H * H;
+  }
+  a.K = h;
+  a.kslice = pl.kslice;
+  a.ldb = D;
+  a.ldc = H;
+  a.slice_stride = H * H;
+  a.tm = (int)(H / 128);
+  a.nsplit = pl.nsplit;
+  a.st = st;
+  hipLaunchKernelGGL(xty_strassen_kernel, dim3((unsigned)(7 * a.tm * a.tm * pl.nsplit)), dim3(NTHREADS), kGemmPipeLds, stream, a);
+  HIP_TRY(hipGetLastError());
+  const int64_t blocks = std::min<int64_t>((H * H + NTHREADS - 1) / NTHREADS, 4096);
+  hipLaunchKernelGGL(strassen_combine_kernel, dim3((unsigned)blocks), dim3(NTHREADS), 0, stream, parts, pl.nsplit, H,
+                     out, D, st);
+  HIP_TRY(hipGetLastError());
 }
 
 // The EPI_SUB_MID / EPI_SUB_CROSS_MID tile bodies fold C0 over exactly 16 K-tiles of one K slice

@@ -97,7 +97,7 @@ void launch_gj_step(double* A, int64_t lda, int64_t D, const GJWork& w, const St
 //   the two K halves run in series (EPI_SIGMOID_SPLIT): C must hold the output, the first halves'
 //   partial at C + slice_stride (slice_stride >= M ldc) and one int flag per tile at
 //   C + 2 slice_stride, the flags zero before the first launch (each launch leaves them zero).
-enum GemmB : int { B_PLAIN = 0, B_IMINUS = 1 };
+enum GemmB : int { B_PLAIN = 0, B_IMINUS = 1, B_PAIR = 2 /* launch_xty_strassen only: B + sgn B2 */ };
 enum GemmEpi : int { EPI_STORE = 0, EPI_SIGMOID = 1, EPI_SUB_BAND = 2 /* launch_trail128 only */,
                      EPI_SUB_CROSS = 3 /* launch_trail128_split only */,
                      EPI_SUB_PRE = 4 /* EPI_SUB_BAND with C0 preloaded into the accumulators */,
@@ -519,6 +519,27 @@ void launch_gemm(const GemmSpec& gs, const State* st, hipStream_t stream);
 // The same with the split-K slices summed: split == 1 writes `out` itself, otherwise the slices go
 // to `slices` (gs.slice_stride apart) and launch_sum_slices adds them into `out` (gs.C unused).
 void launch_gemm_summed(GemmSpec gs, double* slices, double* out, const State* st, hipStream_t stream);
+// The data-mode X^T Y (D x D, K = n_pad) by one level of Strassen: seven (D/2) x (D/2) x (n_pad/2)
+// products in one launch and a combine that writes `out` (ld D) as launch_gemm_summed does.
+// shape: D % 256 == 0 and n_pad % 128 == 0.  plan: the split-K of every product (split < 1: the
+// rule, a whole number of resident rounds; else at most `split` slices, split_k's rounding).
+// sums: the five X-side operand sums (xty_strassen_sum_count doubles), formed once per X; parts:
+// xty_strassen_part_count(D, plan.nsplit) doubles.  Gated on st (nullable); deterministic.
+struct XtyStrassenPlan {
+  int nsplit;
+  int64_t kslice;
+};
+// the size rule's shortest product K slice (set_data): measured at D = 1024 (DESIGN.md section
+// 8), GEMM plus combine against the classical form's: 1.13x at slices of 256 rows, 1.005x at 512,
+// 0.96x at 1024, 0.93x at 2048, 0.91x from 8192 on
+constexpr int64_t kXtyStrassenMinSlice = 1024;
+bool xty_strassen_shape(int64_t D, int64_t n_pad);
+XtyStrassenPlan xty_strassen_plan(int64_t D, int64_t n_pad, int split);
+int64_t xty_strassen_sum_count(int64_t D, int64_t n_pad);
+int64_t xty_strassen_part_count(int64_t D, int nsplit);
+void launch_xty_strassen_sums(const double* X, int64_t D, int64_t n_pad, double* S, hipStream_t stream);
+void launch_xty_strassen(const double* X, const double* S, const double* Y, int64_t D, int64_t n_pad, int split,
+                         double* parts, double* out, const State* st, hipStream_t stream);
 // Trailing update of the blocked inverse's outer step g on 128 x 128 tiles:
 // Aout[i, j] = Ain[i, j] - Ain[i, G] Aout[G, j] for i, j outside G = [g B2, (g+1) B2);
 // with `check`, ORs the domain flags of the outputs into st->flags.

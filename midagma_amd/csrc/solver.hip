@@ -241,6 +241,40 @@ int midagma_set_data(midagma_solver* s, const double* X, int64_t n_local, int64_
     s->split = std::min(split, 32);
     if (knob_set("MIDAGMA_EXP_DATA_SPLIT")) s->split = (int)knob("MIDAGMA_EXP_DATA_SPLIT", s->split);
     if (s->split > 1) s->Zparts.alloc((size_t)s->split * D * D);
+    // X^T Y by one level of Strassen (gemm.hip): when the shape allows it (D % 256 == 0), every
+    // product's K slice is long enough to amortise its tile's prologue and epilogue
+    // (kXtyStrassenMinSlice), and the device has room for the five operand sums of X (1.25 x the
+    // size of X; the same free-memory rule as X^T).  Everything else keeps the classical GEMM.
+    s->xty_form = 1;
+    bool strassen = s->xty_form_force != 1 && xty_strassen_shape(D, s->n_pad) && !knob_set("MIDAGMA_EXP_DATA_SPLIT");
+    XtyStrassenPlan plan{};
+    if (strassen) {
+      plan = xty_strassen_plan(D, s->n_pad, s->xty_split_force);
+      if (s->xty_form_force != 2 && plan.kslice < kXtyStrassenMinSlice) strassen = false;
+    }
+    if (strassen) {
+      const size_t nsum = (size_t)xty_strassen_sum_count(D, s->n_pad);
+      HIP_TRY(hipMemGetInfo(&mem_free, &mem_total));
+      strassen = mem_free > nsum * sizeof(double) + (size_t(2) << 30);
+      if (strassen) {
+        try {
+          s->Xsums.alloc(nsum);
+          s->Sparts.alloc((size_t)xty_strassen_part_count(D, plan.nsplit));
+        } catch (const HipError& e) {
+          if (e.code != hipErrorOutOfMemory) throw;
+          (void)hipGetLastError();
+          strassen = false;
+        }
+      }
+    }
+    if (strassen) {
+      launch_xty_strassen_sums(s->X.p, D, s->n_pad, s->Xsums.p, s->stream);
+      s->xty_form = 2;
+      s->xty_split = s->xty_split_force;
+    } else {
+      s->Xsums.release();
+      s->Sparts.release();
+    }
     s->loss_part_count = (s->n_pad / 64) * (D / 64);
     // small shards run the cov-mode slot structure: the warm-started fast blocked inverse in
     // sequence with the GEMMs (hand-backs and checkpoint slots on the pivoted path).  Forked beside
@@ -589,6 +623,21 @@ extern "C" int midagma_debug_sig_split(midagma_solver* s, int mode) {
   if (!s || mode < -1 || mode > 2) return -1;
   if (mode >= 0) s->sig_split_force = mode;
   return s->sig_split;
+}
+
+// The form of the data-mode X^T Y GEMM the current data uses: 1 classical, 2 one level of
+// Strassen (0: no data).
+int midagma_xty_form(const midagma_solver* s) { return s && s->has_data ? s->xty_form : 0; }
+
+// Test hook (not in the public header): choose that form for the next set_data (mode 0: the size
+// rule, 1: always classical, 2: Strassen wherever the shape allows it; -1: no change) and the
+// split-K of the Strassen products (split 0: the rule's, > 0: at most that many slices; -1: no
+// change).  Returns the form the current data uses (1 or 2).
+extern "C" int midagma_debug_xty_form(midagma_solver* s, int mode, int split) {
+  if (!s || mode < -1 || mode > 2 || split < -1) return -1;
+  if (mode >= 0) s->xty_form_force = mode;
+  if (split >= 0) s->xty_split_force = split;
+  return s->xty_form;
 }
 
 // Test hooks (not in the public header) for the hand-back path of the blocked inverse:

@@ -155,6 +155,14 @@ struct midagma_solver {
   const double* xw_a() const { return use_xt ? XT.p : X.p; }
   int64_t xw_lda() const { return use_xt ? n_pad : D; }
   int split = 1;
+  // X^T Y by one level of Strassen (gemm.hip, launch_xty_strassen): the five X-side operand sums,
+  // formed by set_data for as long as this X is set, and the seven products' split-K slices.
+  // xty_form: what the current data uses (1 classical, 2 Strassen).  midagma_debug_xty_form:
+  // xty_form_force 0 the size rule, 1 always classical, 2 Strassen wherever the shape allows;
+  // xty_split_force > 0: that split-K for the products instead of the rule's, for the next
+  // set_data; xty_split: the one the current data's slices (Sparts) were sized for
+  DevBuf<> Xsums, Sparts;
+  int xty_form = 1, xty_form_force = 0, xty_split_force = 0, xty_split = 0;
   int sig_split = 1;  // the logistic sigmoid GEMM's serial split-K (launch_gemm; 2: Y holds the partial too)
   int sig_split_force = 0;
   DevBuf<> cupart_ctr;  // experiments: launch_gemm_cupart's tile counter
@@ -503,7 +511,8 @@ struct midagma_solver {
     gs.n_valid = d;
     return gs;
   }
-  // data mode: Z_k = X_k^T Y in `split` K slices (launch_gemm_summed: Zparts -> zbuf)
+  // data mode: Z_k = X_k^T Y in `split` K slices (launch_gemm_summed: Zparts -> zbuf); the
+  // classical form (enqueue_xty: the Strassen form takes its place when set_data chose it)
   GemmSpec xty_spec() const {
     return GemmSpec{D, D, n_pad, X.p, D, true, Y.p, D, B_PLAIN, Zparts.p, D, split, D * D};
   }
@@ -543,7 +552,12 @@ struct midagma_solver {
   void enqueue_xw(const double* Wp, const State* st, const double* iw) {
     launch_gemm(loss == MIDAGMA_LOSS_L2 ? xw_spec(Wp, iw) : sigmoid_spec(Wp), st, stream);
   }
-  void enqueue_xty(const State* st) { launch_gemm_summed(xty_spec(), Zparts.p, zbuf, st, stream); }
+  void enqueue_xty(const State* st) {
+    if (xty_form == 2)
+      launch_xty_strassen(X.p, Xsums.p, Y.p, D, n_pad, xty_split, Sparts.p, zbuf, st, stream);
+    else
+      launch_gemm_summed(xty_spec(), Zparts.p, zbuf, st, stream);
+  }
 
   // fast (blocked cov slots): the domain flags come from the inverse's last outer step and the
   // score slices are summed inside fused_update; fast slots never carry a checkpoint

@@ -230,6 +230,25 @@ class HipSolver:
             raise ValueError(f"debug_sig_split: bad mode {mode!r}")
         return int(cur)
 
+    @property
+    def xty_form(self) -> int:
+        """The form of the data-mode X^T Y GEMM the current data uses: 1 the classical split-K
+        GEMM, 2 one level of Strassen (0: no data set)."""
+        return int(self.L.midagma_xty_form(self.h))
+
+    def debug_xty_form(self, mode: int | None = None, split: int | None = None) -> int:
+        """Test hook (not part of the public header): the X^T Y GEMM's form for the next set_data
+        (None: leave it; 0: the size rule, 1: always classical, 2: Strassen wherever the shape
+        allows) and the split-K of the Strassen products (None: leave it; 0: the rule's; > 0: at
+        most that many slices).  Returns the form the current data uses (1 or 2)."""
+        fn = self.L.midagma_debug_xty_form
+        fn.restype, fn.argtypes = C.c_int, [C.c_void_p, C.c_int, C.c_int]
+        cur = fn(self.h, -1, -1)
+        if (mode is not None or split is not None) and \
+                fn(self.h, -1 if mode is None else int(mode), -1 if split is None else int(split)) < 0:
+            raise ValueError(f"debug_xty_form: bad mode {mode!r} or split {split!r}")
+        return int(cur)
+
     def debug_spoil_warm(self):
         """Test hook: zero the blocked inverse's stored warm starts, so the next fast slot hands
         back (ST_NEED_GJ) from inside its forked inverse."""
