@@ -430,13 +430,13 @@ int midagma_indep_run(midagma_indep* h, int kind, const int64_t* pairs, int64_t 
                       uint64_t seed, int64_t budget_bytes, double* stat, int64_t* ge, double* null_out,
                       int32_t* perms_out);
 
-/* A batch of B independent small-d problems (1 <= d <= 64, l2, cov mode, float64 W, no trek
- * regularizer) that share d, the device and the loop settings and each have their own covariance,
+/* A batch of B independent small-d problems (1 <= d <= 64, l2, cov mode, float64 W; the PST trek
+ * regularizer at d <= 32 through midagma_btrek_set below, no TCC) that share d, the device and the loop settings and each have their own covariance,
  * lambda1, mu, s and lr: one launch of the small-d persistent loop runs them with one workgroup per
  * problem, so bootstrap resamples, a lambda1 grid or a table over seeds fill the device instead of
  * one compute unit.  Purely additive: MIDAGMA_ABI_VERSION stays 11.
  * Problem b's W, result and checkpoint records are bit-identical to what a cov-mode l2
- * midagma_solver gives for that problem alone with the same arguments.
+ * midagma_solver gives for that problem alone with the same arguments (without a regularizer).
  * Every entry checks its arguments before it touches a device (MIDAGMA_E_ARG); the message comes
  * from midagma_batch_last_error(handle) (or (NULL) for errors raised without a handle).  A handle
  * owns one stream and its device and pinned buffers; one host thread drives it at a time.
@@ -461,6 +461,20 @@ int midagma_batch_minimize(midagma_batch* h, double* W, const double* mu, const 
                            const double* lambda1, int64_t max_iter, double tol, double beta1, double beta2,
                            int64_t checkpoint, const uint8_t* active, midagma_result* res);
 int64_t midagma_batch_checkpoints(midagma_batch* h, int64_t b, midagma_ckpt* out, int64_t cap);
+
+/* The PST trek regularizer in a batch (additive, ABI 11; d <= 32): its value and gradient are
+ * computed inside each problem's workgroup (csrc/pst_blk.h), so a problem's result does not depend
+ * on the rest of the batch; it agrees with midagma_set_trek's launch chain on a midagma_solver to
+ * rounding, not bit for bit.  Errors as the batch entries' (midagma_batch_last_error).
+ * set: seq 0 exp | 1 inv, agg and mode as midagma_set_trek; weight holds B values (one per
+ *   problem), pairs m (i, j) int64 shared by the problems (repeats count, (i, j) and (j, i)
+ *   differ, (i, i) is allowed).  mode 0 or m = 0 switches the regularizer off again.
+ *   MIDAGMA_E_ARG: d > 32, seq log or binom, a pair index outside [0, d), a non-finite weight.
+ * value: trek_value_grad of B given matrices (W is B x d x d host), no Adam step: value holds B
+ *   values, grad (nullable) B x d x d; zeros without a regularizer. */
+int midagma_btrek_set(midagma_batch* h, int seq, int agg, int mode, const double* weight, double eps_inv,
+                      const int64_t* pairs, int64_t m);
+int midagma_btrek_value(midagma_batch* h, const double* W, double* value, double* grad);
 
 /* Bootstrap covariances for a batch, formed on the device from one X (additive, ABI 11).
  * Replicate b of `seed` draws n row indices with replacement:

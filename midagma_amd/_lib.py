@@ -158,6 +158,9 @@ EXPORTED = {
     "midagma_batch_minimize": (_int, [_vp, _dp, _dp, _dp, _dp, _dp, _i64, _d, _d, _d, _i64, _vp,
                                       C.POINTER(MidagmaResult)]),
     "midagma_batch_checkpoints": (_i64, [_vp, _i64, C.POINTER(MidagmaCkpt), _i64]),
+    # additive to ABI 11: the PST trek regularizer in a batch (HipBatch.set_trek / trek_value, csrc/pst_blk.h)
+    "midagma_btrek_set": (_int, [_vp, _int, _int, _int, _dp, _d, C.POINTER(_i64), _i64]),
+    "midagma_btrek_value": (_int, [_vp, _dp, _dp, _dp]),
     # additive to ABI 11: bootstrap covariances for a batch from one X (HipBatch.boot_cov, csrc/boot.hip)
     "midagma_boot_cov": (_int, [_vp, _vp, _i64, _i64, _int, C.c_uint64, _i64, _i64]),
     "midagma_boot_get_cov": (_int, [_vp, _dp]),

@@ -13,6 +13,17 @@ returns with the same arguments: the stages of the path-following loop (linear.p
 in lockstep over the problems, and within a stage the problems that have not yet succeeded are
 re-run, each with its own halved lr and enlarged s, until none is left.
 
+The PST trek regularizer (seq exp or inv, d <= 32) runs inside each problem's workgroup
+(csrc/pst_blk.h), with one pair set and a weight per problem, so the knob every PST user turns is a
+grid like any other:
+
+    m = DagmaLinearBatch(trek_reg=PSTRegularizer(I=I, seq="exp", mode="opt", weight=0.1))
+    W = m.fit(X, lambda1=0.03, trek_weight=[0.01, 0.1, 1.0])       # a weight grid on one X
+
+With a regularizer a problem's result does not depend on the rest of the batch, and it matches
+`DagmaLinear(trek_reg=...).fit` (which runs the launch chain of csrc/trek.hip) to rounding along
+the trajectory, not bit for bit.
+
 Bootstrap edge frequencies come from one X, host or device, without B gathered copies of it:
 
     freq = DagmaLinearBatch().bootstrap(X, n_boot=1024, lambda1=0.03, seed=7)     # (d, d)
@@ -21,8 +32,9 @@ The device draws replicate b's row indices (`bootstrap_indices(seed, b, n)` rest
 the host) and forms its covariance from counts over one pass of X (csrc/boot.hip), straight into
 problem b of the batch; the stage and retry loop is `fit`'s.
 
-Not in the batch: a trek regularizer, float32 W, d > 64, the logistic loss and data mode, several
-devices, a device X in `fit` (`bootstrap` takes one), weighted or m-out-of-n bootstraps.
+Not in the batch: the TCC trek regularizer, PST with seq log or binom or at d > 32, a pair set per
+problem, float32 W, d > 64, the logistic loss and data mode, several devices, a device X in `fit`
+(`bootstrap` takes one), weighted or m-out-of-n bootstraps.
 """
 from __future__ import annotations
 
@@ -88,8 +100,7 @@ class DagmaLinearBatch:
             raise ValueError("DagmaLinearBatch runs the l2 loss (cov mode) only")
         if np.dtype(dtype).type is not np.float64:
             raise ValueError("DagmaLinearBatch runs a float64 W only")
-        if trek_reg is not None and trek_reg.enabled():
-            raise ValueError("DagmaLinearBatch runs no trek regularizer")
+        self._trek = self._read_trek(trek_reg)
         self.loss_type = loss_type
         self.dtype = np.float64
         self.vprint = print if verbose else (lambda *a, **k: None)
@@ -99,8 +110,56 @@ class DagmaLinearBatch:
         self._solver_factory = solver_factory or HipSolver
         self.minimize_log: list = []
 
+    # -------------------------------------------------------- trek regularizer
+    @staticmethod
+    def _read_trek(tr):
+        """The PST settings of an enabled regularizer, read as `DagmaLinear._install_trek` reads them
+        (None: no regularizer); everything the batch does not run raises."""
+        if tr is None or not tr.enabled():
+            return None
+        if str(tr.name).lower().strip() != "pst":
+            raise ValueError(f"DagmaLinearBatch runs the PST trek regularizer only, not {tr.name!r}")
+        pairs = tr.cfg.get("I")
+        if pairs is None or len(pairs) == 0:
+            return None  # (an empty pair set is no regularizer, as in the reference)
+        kw = dict(tr.cfg.get("kwargs") or {})
+        seq = str(tr.cfg.get("seq", "exp")).lower().strip()
+        if seq not in ("exp", "inv"):
+            raise ValueError(f"DagmaLinearBatch runs PST with seq 'exp' or 'inv', not {seq!r}")
+        if kw.get("K_log") is not None:
+            raise ValueError("DagmaLinearBatch runs no log series (K_log)")
+        return dict(pairs=np.ascontiguousarray(np.asarray(pairs, dtype=np.int64).reshape(-1, 2)), seq=seq,
+                    agg=kw.get("agg", "mean"), mode=tr.mode, weight=float(tr.weight),
+                    eps_inv=kw.get("eps_inv", 1e-8))
+
+    def _trek_weights(self, trek_weight, B: int, d: int):
+        """The B weights of the regularizer (None without one); no device work."""
+        if self._trek is None:
+            if trek_weight is not None:
+                raise ValueError("trek_weight needs a trek regularizer")
+            return None
+        if d > HipBatch.MAX_D_TREK:
+            raise ValueError(f"DagmaLinearBatch runs a trek regularizer at d <= {HipBatch.MAX_D_TREK}, got d = {d}")
+        if trek_weight is None:
+            return [self._trek["weight"]] * B
+        if np.ndim(trek_weight) == 0:
+            return [float(trek_weight)] * B
+        w = [float(x) for x in trek_weight]
+        if len(w) != B:
+            raise ValueError(f"trek_weight holds {len(w)} values for {B} problems")
+        return w
+
+    def _install_trek(self, batch, weights):
+        if self._trek is not None:
+            t = self._trek
+            batch.set_trek(t["pairs"], t["seq"], agg=t["agg"], mode=t["mode"], weight=weights, eps_inv=t["eps_inv"])
+
+    def _trek_final(self, batch, B):
+        """The PST value at every unthresholded W_est (zeros without a regularizer)."""
+        self.trek_final = np.zeros(B) if self._trek is None else np.asarray(batch.trek_value(self.W_est, grad=False)[0])
+
     # ------------------------------------------------------------------ inputs
-    def _problems(self, Xs, lambda1):
+    def _problems(self, Xs, lambda1, trek_weight=None):
         """(list of B host X, B lambda1 values), checked; no device work."""
         def host2d(X):
             if is_device_tensor(X) or hasattr(X, "data_ptr"):
@@ -110,12 +169,16 @@ class DagmaLinearBatch:
             return X
 
         lam_seq = None if np.ndim(lambda1) == 0 else [float(x) for x in lambda1]
+        tw_len = None if trek_weight is None or np.ndim(trek_weight) == 0 else len(trek_weight)
+        if lam_seq is not None and tw_len is not None and tw_len != len(lam_seq):
+            raise ValueError(f"lambda1 holds {len(lam_seq)} values and trek_weight {tw_len}")
         if is_device_tensor(Xs) or hasattr(Xs, "data_ptr"):
             raise ValueError("DagmaLinearBatch takes host arrays, not device tensors")
         if isinstance(Xs, np.ndarray) and Xs.ndim == 2:
-            # one X: a lambda1 grid (X centred once, cov formed once, shared by the problems)
+            # one X: a lambda1 and / or trek_weight grid (X centred once, cov formed once, shared by
+            # the problems)
             X = host2d(Xs)
-            xs = [X] * (1 if lam_seq is None else len(lam_seq))
+            xs = [X] * (len(lam_seq) if lam_seq is not None else (tw_len if tw_len is not None else 1))
         elif isinstance(Xs, np.ndarray):
             if Xs.ndim != 3 or Xs.dtype != np.float64:
                 raise ValueError("Xs must be a sequence of (n_b, d) float64 arrays, a (B, n, d) array or one (n, d) X")
@@ -224,17 +287,20 @@ class DagmaLinearBatch:
                          max_iter=6e4, lr=0.0003, checkpoint=1000, beta_1=0.99, beta_2=0.999, exclude_edges=None,
                          include_edges=None)
 
-    def bootstrap(self, X, n_boot: int, lambda1: float = 0.03, seed: int = 0, **fit_kwargs) -> np.ndarray:
+    def bootstrap(self, X, n_boot: int, lambda1: float = 0.03, seed: int = 0, trek_weight=None,
+                  **fit_kwargs) -> np.ndarray:
         """Edge frequencies over `n_boot` bootstrap resamples of one X, the resampling and the
         covariances on the device (`HipBatch.boot_cov`, csrc/boot.hip).
 
         X: one (n, d) float64 host array or device tensor, d <= 64; it is not modified.  Replicate
         b fits the rows `X[bootstrap_indices(seed, b, n)]`, so `DagmaLinear('l2').fit(X[idx].copy(),
         lambda1, ...)` reproduces any one of them (up to the rounding of its covariance).  lambda1:
-        a scalar.  fit_kwargs: `fit`'s other arguments, with its defaults.
+        a scalar.  trek_weight: a scalar that replaces the trek regularizer's weight (None: its own).
+        fit_kwargs: `fit`'s other arguments, with its defaults.
 
         Leaves W_boot (n_boot, d, d; thresholded), edge_freq = (W_boot != 0).mean(0) (also
-        returned), boot_seed, and h_final, score_final, minimize_log and fit_timing as `fit`."""
+        returned), boot_seed, and h_final, score_final, trek_final, minimize_log and fit_timing as
+        `fit`."""
         t_start = time.perf_counter()
         unknown = sorted(set(fit_kwargs) - set(self._FIT_DEFAULTS))
         if unknown:
@@ -242,6 +308,8 @@ class DagmaLinearBatch:
         kw = dict(self._FIT_DEFAULTS, **fit_kwargs)
         if np.ndim(lambda1) != 0:
             raise ValueError("bootstrap takes one scalar lambda1")
+        if trek_weight is not None and np.ndim(trek_weight) != 0:
+            raise ValueError("bootstrap takes one scalar trek_weight")
         if isinstance(n_boot, bool) or int(n_boot) != n_boot or not 1 <= int(n_boot) <= HipBatch.MAX_B:
             raise ValueError(f"bootstrap needs 1 <= n_boot <= {HipBatch.MAX_B}, got {n_boot}")
         if is_device_tensor(X):
@@ -258,16 +326,19 @@ class DagmaLinearBatch:
         if n < 1 or n >= 2**31:
             raise ValueError(f"bootstrap needs 1 <= n < 2^31 rows, got {n}")
         B, T, lam = int(n_boot), int(kw["T"]), [float(lambda1)] * int(n_boot)
+        tw = self._trek_weights(trek_weight, B, d)
         s0 = self._s_list(kw["s"], T)
         inc, exc = _edges(kw["include_edges"]), _edges(kw["exclude_edges"])
         self.B, self.d, self.lambda1, self.checkpoint, self.boot_seed = B, d, lam, kw["checkpoint"], int(seed)
         batch = self._batch_factory(d, B, device=self.device)
         try:
             batch.boot_cov(X, int(seed))
+            self._install_trek(batch, tw)
             t_prep = time.perf_counter()
             self._stages(batch, B, d, lam, T, s0, inc, exc, kw["mu_init"], kw["mu_factor"], kw["warm_iter"],
                          kw["max_iter"], kw["lr"], kw["checkpoint"], kw["beta_1"], kw["beta_2"])
             covs = batch.get_cov()
+            self._trek_final(batch, B)
         finally:
             batch.close()
         t_loop = time.perf_counter()
@@ -287,22 +358,28 @@ class DagmaLinearBatch:
             warm_iter: int = 3e4, max_iter: int = 6e4, lr: float = 0.0003, checkpoint: int = 1000,
             beta_1: float = 0.99, beta_2: float = 0.999,
             exclude_edges: typing.Optional[typing.Tuple[typing.Tuple[int, int], ...]] = None,
-            include_edges: typing.Optional[typing.Tuple[typing.Tuple[int, int], ...]] = None) -> np.ndarray:
+            include_edges: typing.Optional[typing.Tuple[typing.Tuple[int, int], ...]] = None,
+            trek_weight: typing.Union[None, float, typing.Sequence[float]] = None) -> np.ndarray:
         """Runs DAGMA (linear.py:335-462) on every problem and returns the thresholded weighted
         adjacencies, (B, d, d).
 
         Xs: a sequence of B host float64 arrays (n_b, d) with a common d (the n_b may differ), a
         (B, n, d) array, or one (n, d) X with `lambda1` a length-B sequence (a lambda1 grid).
-        lambda1: a scalar or a length-B sequence.  The other arguments are `DagmaLinear.fit`'s and
-        shared by the problems.  Every distinct X is centred in place, once, as the reference
-        centres its X; the caller's `s` list is not changed.
+        lambda1: a scalar or a length-B sequence.  trek_weight: a scalar or a length-B sequence that
+        replaces the trek regularizer's weight per problem (None: its own); one X with a
+        `trek_weight` sequence is a weight grid, and with both sequences given their lengths must
+        agree.  The other arguments are `DagmaLinear.fit`'s and shared by the problems.  Every
+        distinct X is centred in place, once, as the reference centres its X; the caller's `s` list
+        is not changed.
 
-        Leaves W_est (B, d, d), h_final (B,), score_final (B,), minimize_log (B lists with
+        Leaves W_est (B, d, d), h_final (B,), score_final (B,), trek_final (B,; the PST value at the
+        unthresholded W_est, zeros without a regularizer), minimize_log (B lists with
         `DagmaLinear.minimize_log`'s fields) and fit_timing.  Raises np.linalg.LinAlgError naming
         the problems whose s I - W o W became singular."""
         t_start = time.perf_counter()
-        xs, lam, d = self._problems(Xs, lambda1)
+        xs, lam, d = self._problems(Xs, lambda1, trek_weight)
         B, T = len(xs), int(T)
+        tw = self._trek_weights(trek_weight, B, d)
         s0 = self._s_list(s, T)
         inc, exc = _edges(include_edges), _edges(exclude_edges)
         self.B, self.d, self.lambda1, self.checkpoint = B, d, lam, checkpoint
@@ -316,9 +393,11 @@ class DagmaLinearBatch:
         batch = self._batch_factory(d, B, device=self.device)
         try:
             batch.set_cov(np.stack(self.cov))
+            self._install_trek(batch, tw)
             t_prep = time.perf_counter()
             self._stages(batch, B, d, lam, T, s0, inc, exc, mu_init, mu_factor, warm_iter, max_iter, lr, checkpoint,
                          beta_1, beta_2)
+            self._trek_final(batch, B)
         finally:
             batch.close()
         t_loop = time.perf_counter()

@@ -1,9 +1,12 @@
-// A batch of B independent small-d problems (d <= 64, l2, cov mode, float64, no trek regularizer)
-// behind the midagma_batch_* entries of the C ABI: the small-d persistent loop (small.hip) with
-// one workgroup per problem.  Problem b's result is bit-identical to what a midagma_solver gives
-// for that problem alone: the same kernel instantiation runs it, on Params / State / (-mu) cov /
-// W / m / v filled as midagma_solver::begin fills them (solver_impl.h's shared helpers), and the
-// kernel's results do not depend on how the host splits slots over launches.
+// A batch of B independent small-d problems (d <= 64, l2, cov mode, float64; at d <= 32 with the
+// PST trek regularizer) behind the midagma_batch_* and midagma_btrek_* entries of the C ABI: the
+// small-d persistent loop (small.hip) with one workgroup per problem.  Without a regularizer,
+// problem b's result is bit-identical to what a midagma_solver gives for that problem alone: the
+// same kernel instantiation runs it, on Params / State / (-mu) cov / W / m / v filled as
+// midagma_solver::begin fills them (solver_impl.h's shared helpers), and the kernel's results do
+// not depend on how the host splits slots over launches.  With PST (pst_blk.h's body in the
+// slots; the single solver runs trek.hip's launch chain) a problem's result does not depend on
+// the rest of the batch, and agrees with the single solver's to rounding.
 //
 // Device layout: every per-problem array of the single solver with a leading problem index
 // (D x D slabs with D = 64, as the single solver pads d <= 64).  The host relaunches only the
@@ -123,6 +126,10 @@ void midagma_batch::minimize(double* Wh, const double* mu, const double* s_dom, 
     if (!last_active[b]) continue;
     h_params.p[b] = cov_l2_params(d, D, mu[b], s_dom[b], lambda1[b], tol, b1, b2, max_iter, checkpoint, bc_len,
                                   has_inc, has_exc);
+    if (trek.mode) {
+      h_params.p[b].trek_weight = trek_weight[b];
+      h_params.p[b].trek_mode = trek.mode;
+    }
     h_state.p[b] = initial_state(lr[b]);
     h_index.p[n_run++] = (int32_t)b;
   }
@@ -146,7 +153,7 @@ void midagma_batch::minimize(double* Wh, const double* mu, const double* s_dom, 
     const int64_t slots = small_next_batch(-1, launched, cap, midagma_solver::kSmallBatch);
     launch_small_minimize(d_params.p, d_state.p, W.p, m.p, v.p, covs.p, has_inc ? minc.p : nullptr,
                           has_exc ? mexc.p : nullptr, bc_table.p, d_ckpt.p, ckpt_cap, carry.p, pstore.p, d, slots,
-                          stream, nullptr, false, d_index.p, n_run);
+                          stream, nullptr, false, d_index.p, n_run, trek.mode ? &trek : nullptr);
     launched += slots;
     HIP_TRY(hipMemcpyAsync(h_state.p, d_state.p, B * sizeof(State), hipMemcpyDeviceToHost, stream));
     HIP_TRY(hipStreamSynchronize(stream));
@@ -172,6 +179,35 @@ void midagma_batch::minimize(double* Wh, const double* mu, const double* s_dom, 
   HIP_TRY(hipStreamSynchronize(stream));
   for (int64_t b = 0; b < B; ++b)
     if (last_active[b]) midagma_solver::fill_result(h_state.p[b], &res[b]);
+}
+
+void midagma_batch::set_trek(int seq, int agg, int mode, const double* weight, double eps_inv, const int64_t* pairs,
+                             int64_t m) {
+  trek = SmallPst{};
+  if (mode == 0 || m == 0) return;
+  std::vector<double> N((size_t)d * d, 0.0);
+  for (int64_t p = 0; p < m; ++p) N[(size_t)(pairs[2 * p] * d + pairs[2 * p + 1])] += 1.0;
+  trek_N.alloc((size_t)d * d);
+  trek_val.alloc((size_t)B);
+  HIP_TRY(hipMemcpy(trek_N.p, N.data(), N.size() * sizeof(double), hipMemcpyHostToDevice));
+  trek_weight.assign(weight, weight + B);
+  trek.N = trek_N.p;
+  trek.m = (double)m;
+  trek.eps_inv = eps_inv;
+  trek.seq = seq;
+  trek.agg = agg;
+  trek.mode = mode;
+}
+
+// (W and m serve as the call's scratch slabs: minimize uploads W and zeroes m at its start)
+void midagma_batch::trek_value(const double* Wh, double* value, double* grad) {
+  upload_all(W, Wh);
+  launch_small_pst_eval(W.p, d, D, B, trek, trek_val.p, grad ? m.p : nullptr, stream);
+  HIP_TRY(hipMemcpyAsync(value, trek_val.p, (size_t)B * sizeof(double), hipMemcpyDeviceToHost, stream));
+  if (grad)
+    download_all(m, grad);
+  else
+    HIP_TRY(hipStreamSynchronize(stream));
 }
 
 int midagma::batch_fail(midagma_batch* h, int code, const std::string& msg) {
@@ -282,4 +318,36 @@ extern "C" int64_t midagma_batch_checkpoints(midagma_batch* h, int64_t b, midagm
       HIP_TRY(hipMemcpy(out, h->d_ckpt.p + b * h->ckpt_cap, n * sizeof(CkptRec), hipMemcpyDeviceToHost));
   });
   return rc == MIDAGMA_OK ? n : rc;
+}
+
+extern "C" int midagma_btrek_set(midagma_batch* h, int seq, int agg, int mode, const double* weight, double eps_inv,
+                                 const int64_t* pairs, int64_t m) {
+  if (!h) return bfail(h, MIDAGMA_E_ARG, "btrek_set: null handle");
+  if (mode < 0 || mode > 2 || m < 0) return bfail(h, MIDAGMA_E_ARG, "btrek_set: bad mode or pair count");
+  if (mode != 0 && m > 0) {
+    if (!weight || !pairs) return bfail(h, MIDAGMA_E_ARG, "btrek_set: null argument");
+    if (h->d > 32) return bfail(h, MIDAGMA_E_ARG, "btrek_set: the PST regularizer in a batch needs d <= 32");
+    if (seq != midagma::TREK_EXP && seq != midagma::TREK_INV)
+      return bfail(h, MIDAGMA_E_ARG, "btrek_set: a batch runs seq exp and inv (not log or binom)");
+    if (agg < midagma::TREK_MEAN || agg > midagma::TREK_LSE) return bfail(h, MIDAGMA_E_ARG, "btrek_set: unknown agg");
+    for (int64_t p = 0; p < 2 * m; ++p)
+      if (pairs[p] < 0 || pairs[p] >= h->d) return bfail(h, MIDAGMA_E_ARG, "btrek_set: pair index outside [0, d)");
+    if (!finite_block(weight, h->B) || !std::isfinite(eps_inv))
+      return bfail(h, MIDAGMA_E_ARG, "btrek_set: weight and eps_inv must be finite");
+  }
+  return bguarded(h, [&] { h->set_trek(seq, agg, mode, weight, eps_inv, pairs, m); });
+}
+
+extern "C" int midagma_btrek_value(midagma_batch* h, const double* W, double* value, double* grad) {
+  if (!h) return bfail(h, MIDAGMA_E_ARG, "btrek_value: null handle");
+  if (!W || !value) return bfail(h, MIDAGMA_E_ARG, "btrek_value: null argument");
+  if (!finite_block(W, h->B * h->d * h->d))
+    return bfail(h, MIDAGMA_E_ARG, "btrek_value: array must not contain infs or NaNs");
+  if (!h->trek.mode) {  // no regularizer: notreks gives (0, 0) for an empty pair set
+    for (int64_t b = 0; b < h->B; ++b) value[b] = 0.0;
+    if (grad)
+      for (int64_t e = 0; e < h->B * h->d * h->d; ++e) grad[e] = 0.0;
+    return MIDAGMA_OK;
+  }
+  return bguarded(h, [&] { h->trek_value(W, value, grad); });
 }

@@ -30,6 +30,11 @@ struct midagma_batch {
   int64_t ckpt_cap = 0, bc_len = 0;
   double bc_b1 = -1, bc_b2 = -1;
   bool has_cov = false, has_inc = false, has_exc = false;
+  // the PST trek regularizer of the problems (midagma_btrek_set): one pair list, as its d x d
+  // multiplicity matrix on the device, and a weight per problem
+  DevBuf<> trek_N, trek_val;
+  midagma::SmallPst trek{};  // (mode 0: off)
+  std::vector<double> trek_weight;
   std::vector<uint8_t> last_active;  // the problems of the last minimize call (their checkpoints)
   double boot_ms[4] = {0, 0, 0, 0};  // the last boot_cov: centring, counts, Gram, finish (device events)
 
@@ -52,6 +57,8 @@ struct midagma_batch {
   void minimize(double* Wh, const double* mu, const double* s_dom, const double* lr, const double* lambda1,
                 int64_t max_iter, double tol, double b1, double b2, int64_t checkpoint, const uint8_t* active,
                 midagma_result* res);
+  void set_trek(int seq, int agg, int mode, const double* weight, double eps_inv, const int64_t* pairs, int64_t m);
+  void trek_value(const double* Wh, double* value, double* grad);
 };
 
 namespace midagma {

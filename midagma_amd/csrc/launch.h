@@ -287,6 +287,8 @@ int small_block(int64_t d);
 // tcc (nullable; d <= 32): the TCC trek regularizer inside every slot ('opt') or every
 // checkpoint slot ('log'), tcc_blk.h's body on the workgroup, its state words read at entry and
 // written back at exit (the graph-replayed slots' TccWork words, so the two paths interleave).
+// pst (nullable; d <= 32, float64, no tcc): the PST trek regularizer inside the slots in the same
+// way, pst_blk.h's body; its weight and mode are the problem's Params.trek_weight / trek_mode.
 // index (nullable; float64, no tcc): a batch (batch.hip).  n_problems workgroups, workgroup g on
 // problem index[g] of per-problem arrays: pr and st by 1, the matrices by pr->D * pr->D, ckpt by
 // ckpt_cap, carry by NORM_FIELDS + 1, pstore by 2 * small_block(d)^2; bc_table is shared.
@@ -299,11 +301,22 @@ struct SmallTcc {
   double* uprev;
   int fix = 1;            // TccWork::fix
 };
+struct SmallPst {
+  const double* N = nullptr;  // d x d (leading dimension d): how often the pair list holds (i, j)
+  double m = 0.0;             // pairs, with their repeats
+  double eps_inv = 0.0;
+  int seq = 0, agg = 0;       // TrekSeq (exp or inv), TrekAgg
+  int mode = 0;               // 1 'log', 2 'opt'
+};
 void launch_small_minimize(const Params* pr, State* st, double* W, double* m, double* v, const double* covs,
                            const double* minc, const double* mexc, const double* bc_table, CkptRec* ckpt,
                            int64_t ckpt_cap, double* carry, double* pstore, int64_t d, int64_t n_slots,
                            hipStream_t stream, const SmallTcc* tcc = nullptr, bool w32 = false,
-                           const int32_t* index = nullptr, int64_t n_problems = 1);
+                           const int32_t* index = nullptr, int64_t n_problems = 1, const SmallPst* pst = nullptr);
+// The PST penalty of n_problems matrices (D x D slabs of W, d <= 32), one workgroup each, no Adam
+// step: value[b] and, with grad (D x D slabs, nullable), d value / d W on the d x d block.
+void launch_small_pst_eval(const double* W, int64_t d, int64_t D, int64_t n_problems, const SmallPst& ps,
+                           double* value, double* grad, hipStream_t stream);
 
 // --- trek.hip ---------------------------------------------------------------
 enum TrekSeq : int { TREK_EXP = 0, TREK_INV = 1, TREK_LOG = 2, TREK_BINOM = 3 };

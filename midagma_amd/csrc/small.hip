@@ -1,5 +1,5 @@
-// Small-d cov-mode inner loop in ONE persistent workgroup (d <= 64, l2; the TCC trek regularizer
-// at d <= 32, tcc_blk.h; no PST).
+// Small-d cov-mode inner loop in ONE persistent workgroup (d <= 64, l2; at d <= 32 the TCC trek
+// regularizer, tcc_blk.h, or the PST one, pst_blk.h).
 //
 // At d = 20 a graph-replayed slot is 8 dependent launches of a 64 x 64 padded problem, each
 // 4-6 us (profiles/r01_rocprof_cov_small_kernel_stats.csv): the GPU ran the reference's loop
@@ -31,6 +31,7 @@
 #include "np_sum.h"
 #include "mfma64.h"
 #include "tcc_blk.h"
+#include "pst_blk.h"
 
 namespace midagma {
 
@@ -250,13 +251,13 @@ __device__ __noinline__ void small_control(const SmallCtlParams& pr_, State& S, 
     ctl.bc2 = S.bc2;
 }
 
-template <int DS, int NW, int TCC, bool W32 = false>
+template <int DS, int NW, int TCC, bool W32 = false, bool PST = false>
 __global__ __launch_bounds__(64 * NW) void small_minimize_kernel(
     const Params* __restrict__ pr_, State* __restrict__ stg_, double* __restrict__ Wg_, double* __restrict__ mg_,
     double* __restrict__ vg_, const double* __restrict__ covs_, const double* __restrict__ minc_,
     const double* __restrict__ mexc_, const double* __restrict__ bc_table, CkptRec* __restrict__ ckpt_,
     int64_t ckpt_cap, double* __restrict__ carry_, double* __restrict__ pstore_, int64_t n_slots, SmallTcc tc,
-    const int32_t* __restrict__ index) {
+    const int32_t* __restrict__ index, SmallPst ps) {
   constexpr int NT = 64 * NW, TPR = DS / 16, TPW = TPR * TPR / NW, E = 4 * TPW;
   // A batch (batch.hip): workgroup blockIdx.x works on problem index[blockIdx.x] of per-problem
   // arrays (Params, State, the D x D slabs, ckpt_cap records, the carry words, the two stored
@@ -284,6 +285,8 @@ __global__ __launch_bounds__(64 * NW) void small_minimize_kernel(
   static_assert(TCC == 0 || (TCC == 4 && TNB * TNB == NT && DS <= 32) || (TCC == 5 && DS == 32 && NT >= 64),
                 "TCC in the small loop: d <= 32");
   static_assert(TPW * NW == TPR * TPR, "whole tiles per wave");
+  // PST: pst_blk.h's body on this workgroup's ownership (one tile per wave), float64, never with TCC
+  static_assert(!PST || (TCC == 0 && !W32 && DS <= 32 && TPW == 1), "PST in the small loop: d <= 32, float64");
   constexpr int SW = DS + 2;                         // W, cov images: 16 rows x 4 cols per read
   constexpr int SI = ((DS + 15) / 32) * 32 + 16;     // I - W image: B operand rows, = 16 mod 32
   // DS = 64: the images are single-buffered (an extra barrier before each rewrite), R / Q serve
@@ -317,6 +320,8 @@ __global__ __launch_bounds__(64 * NW) void small_minimize_kernel(
   // TCC: the body's LDS and the regularizer's state words (scal, v, u), loaded at entry
   __shared__ std::conditional_t<TCC != 0, tccb::TccLds<TNB, TBS>, char> TL;
   __shared__ double tsc[TCC ? 10 : 1], tvp[TCC ? TBS * TNB : 1], tup[TCC ? TBS * TNB : 1];
+  // PST: the body's LDS (the pair multiplicities, loaded at entry; the value of the last run)
+  __shared__ std::conditional_t<PST, pstb::PstLds<DS, NW>, char> PL;
 
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
   const int q = lane >> 4, c = lane & 15;
@@ -375,6 +380,13 @@ __global__ __launch_bounds__(64 * NW) void small_minimize_kernel(
       tup[e] = tc.uprev[e];
     }
   }
+  if constexpr (PST) {
+    for (int e = tid; e < DS * DS; e += NT) {
+      const int r = e / DS, k = e % DS;
+      PL.nimg[e] = (r < di && k < di) ? ps.N[r * di + k] : 0.0;
+    }
+    if (tid == 0) PL.val = 0.0;
+  }
   __syncthreads();
   if (!ctl.run) return;
   constexpr bool w32 = W32;  // dtype=np.float32 (common.h f32r; a template argument: the float64
@@ -405,6 +417,11 @@ __global__ __launch_bounds__(64 * NW) void small_minimize_kernel(
   // the launch (linear.py:217-222)
   const double c_zscale = pr->zscale, c_mu_l1 = pr->mu_l1, c_beta1 = pr->beta1, c_c1 = pr->c1,
                c_beta2 = pr->beta2, c_c2 = pr->c2;
+  [[maybe_unused]] const double c_trek_w = PST ? pr->trek_weight : 0.0;
+  // the regularizer's value, where the controller reads it
+  const double* trek_val = nullptr;
+  if constexpr (TCC) trek_val = tsc;
+  if constexpr (PST) trek_val = &PL.val;
   double incv[E], excv[E];
 #pragma unroll
   for (int e = 0; e < E; ++e) {
@@ -435,6 +452,18 @@ __global__ __launch_bounds__(64 * NW) void small_minimize_kernel(
                                 [&](int i, int j) { return tc.S[(int64_t)i * D + j]; }, tc.ws, di, tc.mode, tc.eps,
                                 tc.m, tc.weight, tsc, tvp, tup, nullptr, D, TL, tc.fix != 0);
         tcc_ran = true;
+      }
+    }
+    // the PST regularizer of this slot's W (trek_gate_kernel's rule, as above): the value for the
+    // controller, this lane's elements of d value / d W for the element loop
+    [[maybe_unused]] double pg[PST ? E : 1];
+    if constexpr (PST) {
+      if (ps.mode == 2 || (RC ? r_ckpt : S.ckpt_pending)) {
+        const pstb::PstBufs pbufs{PAbuf, PRbuf, PBbuf, rowb[0], colb[0]};
+        pstb::pst_blk_body<DS, NW>(ps, di, wv, Wimg, pbufs, PL, ps.mode == 2, pg);
+      } else {
+#pragma unroll
+        for (int e = 0; e < E; ++e) pg[e] = 0.0;
       }
     }
     // 1 - beta^it for it = iter + 1 from the host table (read early: latency under the inverse)
@@ -692,7 +721,7 @@ __global__ __launch_bounds__(64 * NW) void small_minimize_kernel(
         }
       }
       if (tid == 0)
-        small_control<NW>(cp, S, ctl, red, nred, flw, ckpt, ckpt_cap, bc1n, bc2n, TCC ? tsc : nullptr, next_ck);
+        small_control<NW>(cp, S, ctl, red, nred, flw, ckpt, ckpt_cap, bc1n, bc2n, trek_val, next_ck);
       __syncthreads();
       act = ctl.act;
       norms = ctl.norms != 0;
@@ -767,6 +796,12 @@ __global__ __launch_bounds__(64 * NW) void small_minimize_kernel(
         if constexpr (TCC) {  // Gobj + weight * trek_grad (linear.py:257-258), step.hip's order
           if (tc.mode == 2 && tcc_ran) {
             gtr[e] = tccb::tcc_grad_elem<TNB, TBS>(TL, di, rows[e], cols[e], wo, tc.m, tc.weight);
+            g = g + gtr[e];
+          }
+        }
+        if constexpr (PST) {  // trek_grad_kernel's weight * grad, then step.hip's Gobj + Gtrek
+          if (ps.mode == 2) {
+            gtr[e] = c_trek_w * pg[e];
             g = g + gtr[e];
           }
         }
@@ -921,6 +956,47 @@ __global__ __launch_bounds__(64 * NW) void small_minimize_kernel(
   }
 }
 
+// The PST penalty of B given matrices, no Adam step: workgroup b runs pst_blk.h's body on problem
+// b's D x D slab of W; value[b], and with grad (D x D slabs) d value / d W on d x d.
+template <int DS, int NW>
+__global__ __launch_bounds__(64 * NW) void small_pst_eval_kernel(const double* __restrict__ W_, int64_t d, int64_t D,
+                                                                  SmallPst ps, double* __restrict__ value,
+                                                                  double* __restrict__ grad_) {
+  constexpr int NT = 64 * NW, TPR = DS / 16, SW = DS + 2, SI = ((DS + 15) / 32) * 32 + 16;
+  __shared__ double Wimg[DS * SW];
+  __shared__ double PAbuf[2 * DS * SW], PRbuf[2 * DS * SW], PBbuf[2 * DS * SI];
+  __shared__ double rowb[2][DS], colb[2][DS];
+  __shared__ pstb::PstLds<DS, NW> PL;
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  const int q = lane >> 4, c = lane & 15, di = (int)d;
+  const double* __restrict__ const W = W_ + (int64_t)blockIdx.x * D * D;
+  const int col = 16 * (w % TPR) + c;
+  double wv[4], g[4];
+#pragma unroll
+  for (int t = 0; t < 4; ++t) {
+    const int row = 16 * (w / TPR) + q + 4 * t;
+    wv[t] = (row < di && col < di) ? W[(int64_t)row * D + col] : 0.0;
+    Wimg[row * SW + col] = wv[t];
+  }
+  for (int e = tid; e < DS * DS; e += NT) {
+    const int r = e / DS, k = e % DS;
+    PL.nimg[e] = (r < di && k < di) ? ps.N[r * di + k] : 0.0;
+  }
+  __syncthreads();
+  const pstb::PstBufs pbufs{PAbuf, PRbuf, PBbuf, rowb[0], colb[0]};
+  pstb::pst_blk_body<DS, NW>(ps, di, wv, Wimg, pbufs, PL, grad_ != nullptr, g);
+  __syncthreads();
+  if (tid == 0) value[blockIdx.x] = PL.val;
+  if (grad_) {
+    double* __restrict__ const G = grad_ + (int64_t)blockIdx.x * D * D;
+#pragma unroll
+    for (int t = 0; t < 4; ++t) {
+      const int row = 16 * (w / TPR) + q + 4 * t;
+      if (row < di && col < di) G[(int64_t)row * D + col] = g[t];
+    }
+  }
+}
+
 }  // namespace
 
 #ifdef MIDAGMA_KSTAMPS
@@ -946,7 +1022,7 @@ void launch_small_minimize(const Params* pr, State* st, double* W, double* m, do
                            const double* minc, const double* mexc, const double* bc_table, CkptRec* ckpt,
                            int64_t ckpt_cap, double* carry, double* pstore, int64_t d, int64_t n_slots,
                            hipStream_t stream, const SmallTcc* tcc, bool w32, const int32_t* index,
-                           int64_t n_problems) {
+                           int64_t n_problems, const SmallPst* pst) {
   const int ds = small_block(d);
   if (ds == 0) throw std::invalid_argument("small_minimize: d > 64");
   if (n_problems < 1 || (!index && n_problems != 1))
@@ -954,16 +1030,26 @@ void launch_small_minimize(const Params* pr, State* st, double* W, double* m, do
   if (index && (tcc || w32)) throw std::invalid_argument("small_minimize: a batch is float64 without TCC");
   if (tcc && ds > 32) throw std::invalid_argument("small_minimize: the TCC regularizer needs d <= 32");
   if (tcc && w32) throw std::invalid_argument("small_minimize: float32 W with TCC runs on the graph path");
+  if (pst && (tcc || w32 || ds > 32 || !pst->N || !(pst->m > 0.0) || (pst->mode != 1 && pst->mode != 2) ||
+              (pst->seq != TREK_EXP && pst->seq != TREK_INV) || pst->agg < TREK_MEAN || pst->agg > TREK_LSE))
+    throw std::invalid_argument("small_minimize: PST needs d <= 32, a float64 W, no TCC, seq exp or inv and pairs");
   // d <= 20 on DS = 32: the one-wave 5 x 5 body (d=20: 10.4k -> 11.7k steps/s; experiment knob
   // MIDAGMA_EXP_TCC_BS5=0: NB = 16, 4 x 4)
   const bool bs5 = tcc && ds == 32 && d <= 20 && knob("MIDAGMA_EXP_TCC_BS5", 1) != 0;
   const SmallTcc tc = tcc ? *tcc : SmallTcc{};
-#define MIDAGMA_SMALL(DS_, NW_, TCC_, W32_)                                                                \
-  hipLaunchKernelGGL((small_minimize_kernel<DS_, NW_, TCC_, W32_>), dim3((unsigned)n_problems), dim3(64 * NW_), 0, \
-                     stream, pr, st, W, m, v, covs, minc, mexc, bc_table, ckpt, ckpt_cap, carry, pstore, n_slots, tc,   \
-                     index)
+  const SmallPst ps = pst ? *pst : SmallPst{};
+#define MIDAGMA_SMALL_(DS_, NW_, TCC_, W32_, PST_)                                                                \
+  hipLaunchKernelGGL((small_minimize_kernel<DS_, NW_, TCC_, W32_, PST_>), dim3((unsigned)n_problems),             \
+                     dim3(64 * NW_), 0, stream, pr, st, W, m, v, covs, minc, mexc, bc_table, ckpt, ckpt_cap, carry, \
+                     pstore, n_slots, tc, index, ps)
+#define MIDAGMA_SMALL(DS_, NW_, TCC_, W32_) MIDAGMA_SMALL_(DS_, NW_, TCC_, W32_, false)
   // one wave per 16 x 16 tile
-  if (ds == 16) {
+  if (pst) {
+    if (ds == 16)
+      MIDAGMA_SMALL_(16, 1, 0, false, true);
+    else
+      MIDAGMA_SMALL_(32, 4, 0, false, true);
+  } else if (ds == 16) {
     if (tcc)
       MIDAGMA_SMALL(16, 1, 4, false);
     else if (w32)
@@ -985,6 +1071,22 @@ void launch_small_minimize(const Params* pr, State* st, double* W, double* m, do
     MIDAGMA_SMALL(64, 16, 0, false);
   }
 #undef MIDAGMA_SMALL
+#undef MIDAGMA_SMALL_
+  HIP_TRY(hipGetLastError());
+}
+
+void launch_small_pst_eval(const double* W, int64_t d, int64_t D, int64_t n_problems, const SmallPst& ps,
+                           double* value, double* grad, hipStream_t stream) {
+  const int ds = small_block(d);
+  if (ds == 0 || ds > 32 || n_problems < 1 || !ps.N || !(ps.m > 0.0) || (ps.seq != TREK_EXP && ps.seq != TREK_INV) ||
+      ps.agg < TREK_MEAN || ps.agg > TREK_LSE)
+    throw std::invalid_argument("small_pst_eval: PST needs d <= 32, seq exp or inv and pairs");
+  if (ds == 16)
+    hipLaunchKernelGGL((small_pst_eval_kernel<16, 1>), dim3((unsigned)n_problems), dim3(64), 0, stream, W, d, D, ps,
+                       value, grad);
+  else
+    hipLaunchKernelGGL((small_pst_eval_kernel<32, 4>), dim3((unsigned)n_problems), dim3(256), 0, stream, W, d, D, ps,
+                       value, grad);
   HIP_TRY(hipGetLastError());
 }
 

@@ -784,9 +784,14 @@ class HipBatch:
     """B independent small-d problems (d <= 64, l2, cov mode, float64) on one GPU, one persistent
     workgroup each (`midagma_batch_*`, csrc/batch.hip).  The problems share d and the loop
     settings; each has its own covariance, masks, mu, s, lr and lambda1.  Problem b's W, result
-    and checkpoint records are bit-identical to a `HipSolver` run of that problem alone."""
+    and checkpoint records are bit-identical to a `HipSolver` run of that problem alone.
 
-    MAX_D, MAX_B = 64, 16384
+    With `set_trek` (d <= 32) the PST trek regularizer runs inside each problem's workgroup
+    (csrc/pst_blk.h): one pair list, a weight per problem.  A problem's result then does not
+    depend on the rest of the batch, and agrees with `HipSolver.set_trek`'s launch chain to
+    rounding, not bit for bit."""
+
+    MAX_D, MAX_B, MAX_D_TREK = 64, 16384, 32
 
     def __init__(self, d: int, B: int, device: int = 0):
         self.L = _lib.lib()
@@ -877,6 +882,30 @@ class HipBatch:
         mi = None if mask_inc is None else self._stack(mask_inc, "mask_inc")
         me = None if mask_exc is None else self._stack(mask_exc, "mask_exc")
         self._check(self.L.midagma_batch_set_masks(self.h, dptr(mi), dptr(me)), self.h, "batch_set_masks")
+
+    def set_trek(self, pairs, seq: str = "exp", *, agg: str = "mean", mode: str = "opt", weight=0.0,
+                 eps_inv: float = 1e-8):
+        """The PST trek regularizer (notreks.pst) inside every problem's loop: one pair list, `weight`
+        a scalar or B values.  seq 'exp' or 'inv', d <= 32; mode 'off' or no pairs disables it."""
+        P = np.ascontiguousarray(np.asarray(pairs, dtype=np.int64).reshape(-1, 2)) if pairs is not None \
+            else np.zeros((0, 2), dtype=np.int64)
+        seq, agg, mode = seq.lower().strip(), agg.lower().strip(), mode.lower().strip()
+        if seq not in HipSolver.TREK_SEQ or agg not in HipSolver.TREK_AGG or mode not in HipSolver.TREK_MODE:
+            raise ValueError(f"unsupported PST configuration seq={seq!r} agg={agg!r} mode={mode!r}")
+        w = self._per_problem(weight, "weight")
+        rc = self.L.midagma_btrek_set(self.h, HipSolver.TREK_SEQ[seq], HipSolver.TREK_AGG[agg],
+                                      HipSolver.TREK_MODE[mode], dptr(w), float(eps_inv),
+                                      P.ctypes.data_as(C.POINTER(C.c_int64)), int(P.shape[0]))
+        self._check(rc, self.h, "btrek_set")
+
+    def trek_value(self, W: np.ndarray, grad: bool = True):
+        """notreks.trek_value_grad of B matrices (B x d x d) for the configured regularizer, no Adam
+        step: ((B,) values, (B, d, d) gradients or None); zeros without a regularizer."""
+        W = self._stack(W, "W")
+        v = np.empty(self.B)
+        G = np.empty((self.B, self.d, self.d)) if grad else None
+        self._check(self.L.midagma_btrek_value(self.h, dptr(W), dptr(v), dptr(G)), self.h, "btrek_value")
+        return v, G
 
     def minimize(self, W: np.ndarray, mu, s, lr, lambda1, max_iter: int, tol: float = 1e-6, beta_1: float = 0.99,
                  beta_2: float = 0.999, checkpoint: int = 1000, active=None, want_checkpoints: bool = False):
