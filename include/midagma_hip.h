@@ -500,6 +500,33 @@ int midagma_boot_cov(midagma_batch* h, const void* X, int64_t n, int64_t ldx, in
                      int64_t first, int64_t budget_bytes);
 int midagma_boot_get_cov(midagma_batch* h, double* out);
 int midagma_boot_profile(const midagma_batch* h, double* ms_out);
+
+/* Pearson and Spearman on the device (notreks/mi_tests.py: pearson_stat_pvalue / spearman_stat_pvalue
+ * over all pairs at once; the analytic p-values stay host work), csrc/corr.hip.  Purely additive:
+ * MIDAGMA_ABI_VERSION stays 11.  X_dev is n x d row-major device memory of the current device with
+ * row stride ldx and is never written; the work is enqueued on `stream` (a hipStream_t, NULL: the
+ * null stream) behind X's producer, and each entry returns after its result is written.  Every
+ * entry checks its arguments before it touches a device: MIDAGMA_E_ARG for a null pointer,
+ * n outside [2, 2^31), d outside [1, 65535], ldx < d or an output leading dimension < d (message:
+ * midagma_last_error(NULL)).  MIDAGMA_E_ARG too when X holds inf or nan (found on the device; the
+ * output is then unspecified).
+ * colrank: R[r, c] (ldr) = the 1-based average rank of X[r, c] within column c
+ *   (scipy.stats.rankdata(method="average"); -0.0 ties with +0.0), an exact half-integer.  A
+ *   stable LSD radix sort of (64-bit key, row) per column, the columns in chunks whose scratch
+ *   stays within budget_bytes (<= 0: 2 GiB; at least one column); the ranks do not depend on it.
+ * corr: Rho (d x d, ldrho) = the Pearson correlation matrix of X's columns: G_ij / sqrt(G_ii G_jj)
+ *   clamped to [-1, 1] for the Gram G of the columns minus their means (midagma_gram's FP64 MFMA
+ *   GEMM over a centred staging copy in row chunks within budget_bytes, <= 0: 2 GiB, chunk sums in a
+ *   fixed order), 1 on the diagonal.  const_col[c] = 1 when column c's max equals its min (scipy's
+ *   constant-input rule, on the raw values), else 0; such a column's row and column of Rho are NaN.
+ *   Spearman's rho is corr of colrank's R.
+ * corr_workspace: the bytes of device scratch the larger of the two entries allocates for these
+ *   arguments; 0 for n or d out of range. */
+int midagma_colrank(const double* X_dev, int64_t n, int64_t d, int64_t ldx, double* R_dev, int64_t ldr,
+                    int64_t budget_bytes, void* stream);
+int midagma_corr(const double* X_dev, int64_t n, int64_t d, int64_t ldx, double* Rho_dev, int64_t ldrho,
+                 int32_t* const_col_dev, int64_t budget_bytes, void* stream);
+int64_t midagma_corr_workspace(int64_t n, int64_t d, int64_t budget_bytes);
 #ifdef __cplusplus
 }
 #endif

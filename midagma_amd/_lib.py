@@ -165,6 +165,10 @@ EXPORTED = {
     "midagma_boot_cov": (_int, [_vp, _vp, _i64, _i64, _int, C.c_uint64, _i64, _i64]),
     "midagma_boot_get_cov": (_int, [_vp, _dp]),
     "midagma_boot_profile": (_int, [_vp, _dp]),
+    # additive to ABI 11: column ranks and correlations on the device (solver.column_ranks / correlation, csrc/corr.hip)
+    "midagma_colrank": (_int, [_vp, _i64, _i64, _i64, _vp, _i64, _i64, _vp]),
+    "midagma_corr": (_int, [_vp, _i64, _i64, _i64, _vp, _i64, _vp, _i64, _vp]),
+    "midagma_corr_workspace": (_i64, [_i64, _i64, _i64]),
 }
 
 GROUP_EMULATE = 1

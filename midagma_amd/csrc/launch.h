@@ -624,6 +624,12 @@ struct GramPlan {
 };
 GramPlan gram_plan(int64_t n, int64_t d, int64_t chunk_rows);
 
+// --- solver.hip (for the entries of other files that have no handle: corr.hip) ---
+// records msg as midagma_last_error(NULL)'s message of this thread and returns code
+int fail_global(int code, const std::string& msg);
+// the GEMM and Gauss-Jordan kernels' function attributes, once per process
+void setup_attributes();
+
 // --- comm.hip (the in-library RCCL communicator of a data-mode solver) -------
 // 128-byte ncclUniqueId into out (returns its size); a communicator of nranks (opaque);
 // in-place all-reduce of n doubles (sum, or max) on stream (graph-capturable)

@@ -61,6 +61,15 @@ void setup_attributes_once() {
   });
 }
 
+}  // namespace
+
+namespace midagma {
+int fail_global(int code, const std::string& msg) { return fail(nullptr, code, msg); }
+void setup_attributes() { setup_attributes_once(); }
+}  // namespace midagma
+
+namespace {
+
 // A minimize that ended ST_SINGULAR: the reference's sla.inv raised at that step.  scipy
 // raises ValueError when sI - W*W has a non-finite entry (check_finite: W itself went
 // non-finite, e.g. from non-finite data) and LinAlgError when the finite matrix is singular.

@@ -3,8 +3,18 @@
 
 Names, signatures, defaults and pair order are the reference's.  'hsic' and 'dcor' run their
 permutation tests in csrc/indep.hip through `midagma_amd.solver.HipIndep`; there is no CPU path for
-them (no device: `HipSolverError`).  'pearson' and 'spearman' are analytic and stay on the host
-(scipy), as in the reference.
+them (no device: `HipSolverError`).  'pearson' and 'spearman' are analytic: inside
+`test_pairwise_independence` and `get_I_from_full_pairwise_tests` they run on the host, scipy once
+per pair, exactly as in the reference (bit for bit, and O(pairs) rankings: small problems only).
+
+For all pairs at once there are two functions the reference does not have,
+`correlation_tests(X, test="pearson" | "spearman")` and `get_I_from_correlation_tests(X, ...)`:
+the column ranks (a batched radix sort) and the correlation matrix (centring and the FP64 MFMA
+Gram) are computed on the GPU by csrc/corr.hip from a host or device-resident X, and scipy's
+analytic p-values are evaluated on the host for the whole d x d matrix in one vectorised call.
+They agree with the per-pair path to rounding in the correlation ("Ranks and
+correlations") and return the same I wherever no p-value is within that rounding of alpha_eff.
+There is no CPU path for them either.
 
 One keyword is added, ``perms``:
   * ``"numpy"`` (default): the host draws ``rng = np.random.default_rng(seed)`` once and calls
@@ -40,7 +50,8 @@ import numpy as np
 from .solver import HipIndep, is_device_tensor
 
 __all__ = ["IndepTestResult", "hsic_stat", "dcor_stat", "permutation_null", "test_pairwise_independence",
-           "get_I_from_full_pairwise_tests", "summarize_I", "median_sigma2"]
+           "get_I_from_full_pairwise_tests", "summarize_I", "median_sigma2", "correlation_tests",
+           "get_I_from_correlation_tests"]
 
 TestName = Literal["hsic", "dcor", "pearson", "spearman"]
 
@@ -298,6 +309,95 @@ def get_I_from_full_pairwise_tests(X: np.ndarray, *, alpha: float = 0.05, test: 
     alpha_eff = (alpha / m) if (bonferroni and m > 0) else alpha
     I = [(r.i, r.j) for r in results if r.pvalue > alpha_eff]
     return np.asarray(I, dtype=int)
+
+
+def _pearson_pvalues(r: np.ndarray, n: int) -> np.ndarray:
+    """scipy.stats.pearsonr's two-sided p-value at r, elementwise: r is Beta(n/2 - 1, n/2 - 1) on
+    [-1, 1] under independence (the distribution object scipy uses; n = 2: p = 1 as in scipy)."""
+    from scipy import stats
+    r = np.asarray(r, dtype=np.float64)
+    if n == 2:
+        return np.where(np.isnan(r), np.nan, 1.0)
+    ab = n / 2 - 1
+    return 2 * stats.beta(ab, ab, loc=-1, scale=2).sf(np.abs(r))
+
+
+def _spearman_pvalues(r: np.ndarray, n: int) -> np.ndarray:
+    """scipy.stats.spearmanr's two-sided p-value at r, elementwise: t = r sqrt(dof / ((r + 1)(1 - r)))
+    is Student-t with dof = n - 2 under independence."""
+    from scipy import stats
+    r = np.asarray(r, dtype=np.float64)
+    dof = n - 2
+    with np.errstate(divide="ignore", invalid="ignore"):
+        t = r * np.sqrt((dof / ((r + 1.0) * (1.0 - r))).clip(0))
+        return 2 * stats.t.sf(np.abs(t), dof)
+
+
+def _stat_pvalue_from_rho(rho: np.ndarray, const: np.ndarray, n: int, test: str):
+    """(stat, pvalue), d x d each, from a correlation matrix and its constant-column marks, by
+    the reference's rules: stat = |rho|; the diagonal is (1, 0); a pair with a constant column is
+    (nan, nan) for 'pearson' (scipy's result, passed on) and (0, 1) for 'spearman' (the
+    reference's replacement of scipy's nan)."""
+    rho = np.asarray(rho, dtype=np.float64)
+    const = np.asarray(const, dtype=bool)
+    d = rho.shape[0]
+    # the distribution functions are the cost at large d (scipy's beta.sf: 5 us a value), so they
+    # run on the entries above the diagonal only and (j, i) takes (i, j)'s values
+    iu = np.triu_indices(d, 1)
+    r = rho[iu]
+    stat, p = np.empty((d, d)), np.empty((d, d))
+    stat[iu] = np.abs(r)
+    p[iu] = _pearson_pvalues(r, n) if test == "pearson" else _spearman_pvalues(r, n)
+    stat.T[iu], p.T[iu] = stat[iu], p[iu]
+    np.fill_diagonal(stat, 1.0)
+    np.fill_diagonal(p, 0.0)
+    bad = const[:, None] | const[None, :]
+    if test == "pearson":
+        stat[bad], p[bad] = np.nan, np.nan
+    else:
+        bad |= ~np.isfinite(stat) | ~np.isfinite(p)
+        stat[bad], p[bad] = 0.0, 1.0
+    return stat, p
+
+
+def correlation_tests(X, *, test: str = "pearson", device: int = 0, budget_bytes: int = 0):
+    """(stat, pvalue), two d x d host arrays: the 'pearson' or 'spearman' test of every ordered
+    pair of X's columns at once, with the correlations (and, for 'spearman', the column ranks)
+    computed on the GPU (csrc/corr.hip) and scipy's analytic p-values vectorised on the host.
+    Entry (i, j) is what `test_pairwise_independence(X, [(i, j)], test=test)` returns, to rounding
+    in the correlation; the diagonal is (1, 0) by rule, and (j, i) holds (i, j)'s values (i < j).
+    X: a host float64 array (uploaded to
+    `device`) or a float64 CUDA tensor, read in place and never written (`device` is ignored).
+    ValueError when X holds inf or nan; no GPU: `HipSolverError` (there is no CPU path)."""
+    from .solver import _device_matrix, correlation
+    if test not in ("pearson", "spearman"):
+        raise ValueError("test must be 'pearson' or 'spearman'")
+    Xd = _device_matrix(X, "correlation_tests", device)
+    n = int(Xd.shape[0])
+    rho, const = correlation(Xd, ranks=(test == "spearman"), budget_bytes=budget_bytes)
+    return _stat_pvalue_from_rho(rho.cpu().numpy(), const, n, test)
+
+
+def get_I_from_correlation_tests(X, *, alpha: float = 0.05, test: str = "pearson", bonferroni: bool = True,
+                                 undirected: bool = True, exclude_diagonal: bool = True,
+                                 device: int = 0) -> np.ndarray:
+    """`get_I_from_full_pairwise_tests` for the analytic tests, with every pair tested at once by
+    `correlation_tests`: I = {(i, j): p > alpha_eff} in the reference's pair order, alpha_eff =
+    alpha / #pairs under Bonferroni; the same dtype and shape, the empty case included."""
+    _, p = correlation_tests(X, test=test, device=device)
+    d = p.shape[0]
+    if undirected:
+        i, j = np.triu_indices(d, 1)
+    else:
+        i, j = np.divmod(np.arange(d * d), d)
+        if exclude_diagonal:
+            i, j = i[i != j], j[i != j]
+    m = len(i)
+    alpha_eff = (alpha / m) if (bonferroni and m > 0) else alpha
+    keep = p[i, j] > alpha_eff  # (nan compares False: a pearson pair with a constant column never enters I)
+    if not keep.any():
+        return np.asarray([], dtype=int)
+    return np.stack([i[keep], j[keep]], axis=1).astype(int)
 
 
 def summarize_I(I: np.ndarray, d: int, max_show: int = 10) -> None:

@@ -18,7 +18,7 @@ from . import _lib
 from ._lib import check, dptr
 
 __all__ = ["HipSolver", "HipGroup", "HipIndep", "HipBatch", "MinimizeResult", "CheckpointRecord", "run_allreduce_minimize",
-           "device_count", "colsum_dev", "center_dev", "gram", "row_range"]
+           "device_count", "colsum_dev", "center_dev", "gram", "row_range", "column_ranks", "correlation"]
 
 
 CheckpointRecord = namedtuple("CheckpointRecord", [f for f, _ in _lib.MidagmaCkpt._fields_])
@@ -113,6 +113,75 @@ def gram(X, device: int | None = None):
         check(_lib.lib().midagma_gram(src, n, d, ld, 1 if on_dev else 0, C.c_void_p(G.data_ptr()), d,
                                       _cur_stream(dev)), None, "gram")
     return G
+
+
+def _device_matrix(X, what: str, device=None):
+    """X as a 2-d float64 CUDA tensor with unit column stride: a device tensor as it is (checked),
+    a host float64 array uploaded with torch (to `device`; None: torch's current device).  No GPU:
+    HipSolverError (there is no CPU path)."""
+    import torch
+    if is_device_tensor(X):
+        if X.dtype != torch.float64:
+            raise ValueError(f"{what}: a device X must be a float64 tensor")
+        if X.dim() != 2:
+            raise ValueError(f"{what}: X must be 2-d (n samples x d variables)")
+        if X.stride(1) != 1 or X.stride(0) < X.shape[1]:
+            X = X.contiguous()
+    else:
+        if hasattr(X, "data_ptr"):  # a host torch tensor
+            X = X.detach().numpy()
+        X = np.asarray(X)
+        if X.dtype != np.float64:
+            raise ValueError(f"{what}: X must be float64, got {X.dtype}")
+        if X.ndim != 2:
+            raise ValueError(f"{what}: X must be 2-d (n samples x d variables)")
+    if int(X.shape[0]) < 2 or int(X.shape[1]) < 1:
+        raise ValueError(f"{what}: need at least 2 samples and 1 variable")
+    if is_device_tensor(X):
+        return X
+    if not np.isfinite(X).all():
+        raise ValueError(f"{what}: X holds inf or nan")
+    _lib.lib()
+    if not torch.cuda.is_available():
+        raise _lib.HipSolverError(f"{what}: no GPU (there is no CPU path)")
+    dev = torch.device("cuda", torch.cuda.current_device() if device is None else int(device))
+    return torch.from_numpy(np.ascontiguousarray(X)).to(dev)
+
+
+def column_ranks(X, budget_bytes: int = 0):
+    """The 1-based average-tie ranks of every column of X (`scipy.stats.rankdata(method="average")`
+    per column, bit for bit) as an n x d float64 device tensor, by csrc/corr.hip's batched radix
+    sort.  X: a float64 CUDA tensor with unit column stride (any row stride), read in place on
+    torch's current stream and never written, or a host float64 array (uploaded with torch).
+    budget_bytes: the sort's scratch per chunk of columns (0: the library's default); the ranks do
+    not depend on it.  ValueError when X holds inf or nan."""
+    import torch
+    X = _device_matrix(X, "column_ranks")
+    n, d, ld = _rows(X)
+    R = torch.empty((n, d), dtype=torch.float64, device=X.device)
+    with torch.cuda.device(X.device):
+        check(_lib.lib().midagma_colrank(C.c_void_p(X.data_ptr()), n, d, ld, C.c_void_p(R.data_ptr()), d,
+                                         int(budget_bytes), _cur_stream(X.device)), None, "column_ranks")
+    return R
+
+
+def correlation(X, *, ranks: bool = False, budget_bytes: int = 0):
+    """(Rho, const): the d x d Pearson correlation matrix of X's columns (float64 device tensor;
+    1 on the diagonal, NaN in the rows and columns of constant columns) and a d-element bool array
+    that marks the constant columns (max == min).  ranks=True: Spearman's rho, the same on
+    `column_ranks(X)`.  X and budget_bytes as in `column_ranks`."""
+    import torch
+    X = _device_matrix(X, "correlation")
+    if ranks:
+        X = column_ranks(X, budget_bytes)
+    n, d, ld = _rows(X)
+    Rho = torch.empty((d, d), dtype=torch.float64, device=X.device)
+    const = torch.empty(d, dtype=torch.int32, device=X.device)
+    with torch.cuda.device(X.device):
+        check(_lib.lib().midagma_corr(C.c_void_p(X.data_ptr()), n, d, ld, C.c_void_p(Rho.data_ptr()), d,
+                                      C.c_void_p(const.data_ptr()), int(budget_bytes), _cur_stream(X.device)),
+              None, "correlation")
+    return Rho, const.cpu().numpy().astype(bool)
 
 
 class HipSolver:
