@@ -527,6 +527,62 @@ int midagma_colrank(const double* X_dev, int64_t n, int64_t d, int64_t ldx, doub
 int midagma_corr(const double* X_dev, int64_t n, int64_t d, int64_t ldx, double* Rho_dev, int64_t ldrho,
                  int32_t* const_col_dev, int64_t budget_bytes, void* stream);
 int64_t midagma_corr_workspace(int64_t n, int64_t d, int64_t budget_bytes);
+
+/* colargsort (additive, ABI 11; csrc/corr.hip): order[c n + i] (int32, column-major d x n) = the
+ * row at position i of the stable argsort of column c of X (-0.0 equal to +0.0): the row payload
+ * colrank's radix sort carries, with its passes, key map, chunking (budget_bytes as colrank) and
+ * determinism.  Arguments, errors and the stream rule as colrank's. */
+int midagma_colargsort(const double* X_dev, int64_t n, int64_t d, int64_t ldx, int32_t* order_dev,
+                       int64_t budget_bytes, void* stream);
+
+/* dCor permutation tests of pairs of columns without an n x n sum (additive, ABI 11; csrc/dcor.hip):
+ * the dCor statistic of midagma_indep_run and its bias-corrected form, exact in O(n m) work an
+ * evaluation for a block edge m near sqrt(n) (a sort, block sums and K x K cell tables, K =
+ * ceil(n / m)), for 2 <= n < 2^31.  Not the midagma_indep_ prefix: that handle keeps the transposed X
+ * of an O(n^2) kernel, caps n at 16384 and packs a < 2^14 into its permutation keys; this one
+ * keeps per-column sorts and row sums, has another permutation rule and no HSIC, and none of the
+ * indep entries applies to it.  Errors: midagma_dcor_last_error(handle) (or (NULL)).  One host
+ * thread drives a handle at a time.
+ * create: no device call; the device is opened by the first set_data*.
+ * set_data: host X (n x d row-major), copied.  set_data_dev: device X of the handle's device, row
+ *   stride ld, never written, read on hip_stream behind its producer; the entry synchronises
+ *   hip_stream before it returns (midagma_indep_set_data_dev's ordering rule), so the caller
+ *   synchronises nothing.  Both run the per-column pre-pass (stable argsort through colargsort
+ *   within budget_bytes, centred values, row sums, a.., dvar^2 in both forms, the zero-range mark
+ *   max == min on the raw values).  MIDAGMA_E_ARG before any device call: a null pointer, n outside
+ *   [2, 2^31), d outside [1, 65535], ld < d; MIDAGMA_E_ARG too for inf / nan in X (found on the
+ *   device); the handle then holds no data.
+ * run: for each of the m pairs (int64 m x 2) stat[q], ge[q] = #{p < P : value_p >= value_0} and
+ *   null_out (nullable, m x P) as midagma_indep_run's dcor: unbiased = 0 counts by dcov^2 and returns
+ *   sqrt(max(dcov^2, 0)) / sqrt(sqrt(dvar_x^2 dvar_y^2)) (0 when a variance is <= 0); unbiased = 1
+ *   counts by the U-centred dcov^2_U and returns R_U = dcov^2_U / sqrt(dvar_U,x dvar_U,y) (0 when a
+ *   variance is <= 0; needs n >= 4).  A pair with a zero-range column gives 0, ge = P.
+ *   perms: m x P x n int32 host array, every row a permutation of [0, n) (checked on the host), or
+ *   NULL for device permutations: pi for (pair q of the call, permutation p) is the stable argsort
+ *   over a of the 64-bit word (o0 << 32) | o1, o = Philox4x32-10(counter (q, p, a, 0), key (seed low
+ *   word, seed high word)).  block: the block edge m, 0 for the rule (the power of two in
+ *   [64, 1024] with m^2 >= n, else 1024; midagma_dcor_block) or a value in [4, 1024] (tests); the
+ *   result depends on it by rounding only.  Evaluations ((pair, permutation), the identity
+ *   included) run in chunks whose scratch (cell tables, permutations and inverses, the sort's
+ *   buffers, partials) stays within budget_bytes (<= 0: 2 GiB; at least one evaluation; at most
+ *   16383); results do not depend on it.  MIDAGMA_E_ARG before any device call: null pointers,
+ *   P outside [0, 65535], a pair index outside [0, d), a block that is neither 0 nor in [4, 1024],
+ *   no data.
+ * perms (tests, diagnostics): the P device permutations of pair q of a call with this seed
+ *   (perms_out P x n) and their inverses (inverse_out, nullable). */
+typedef struct midagma_dcor midagma_dcor;
+int midagma_dcor_create(midagma_dcor** out, int device);
+void midagma_dcor_destroy(midagma_dcor* h);
+const char* midagma_dcor_last_error(const midagma_dcor* h);
+int midagma_dcor_set_data(midagma_dcor* h, const double* X, int64_t n, int64_t d, int64_t budget_bytes);
+int midagma_dcor_set_data_dev(midagma_dcor* h, const double* X_dev, int64_t n, int64_t d, int64_t ld,
+                              int64_t budget_bytes, void* hip_stream);
+int midagma_dcor_run(midagma_dcor* h, const int64_t* pairs, int64_t m, int64_t P, const int32_t* perms,
+                     uint64_t seed, int unbiased, int block, int64_t budget_bytes, double* stat, int64_t* ge,
+                     double* null_out);
+int midagma_dcor_perms(midagma_dcor* h, int64_t q, int64_t P, uint64_t seed, int32_t* perms_out,
+                       int32_t* inverse_out);
+int midagma_dcor_block(int64_t n);
 #ifdef __cplusplus
 }
 #endif

@@ -169,6 +169,16 @@ EXPORTED = {
     "midagma_colrank": (_int, [_vp, _i64, _i64, _i64, _vp, _i64, _i64, _vp]),
     "midagma_corr": (_int, [_vp, _i64, _i64, _i64, _vp, _i64, _vp, _i64, _vp]),
     "midagma_corr_workspace": (_i64, [_i64, _i64, _i64]),
+    # additive to ABI 11: the columns' stable argsort and dCor tests without the n^2 sum (solver.HipDcor, csrc/dcor.hip)
+    "midagma_colargsort": (_int, [_vp, _i64, _i64, _i64, _vp, _i64, _vp]),
+    "midagma_dcor_create": (_int, [C.POINTER(_vp), _int]),
+    "midagma_dcor_destroy": (None, [_vp]),
+    "midagma_dcor_last_error": (C.c_char_p, [_vp]),
+    "midagma_dcor_set_data": (_int, [_vp, _dp, _i64, _i64, _i64]),
+    "midagma_dcor_set_data_dev": (_int, [_vp, _vp, _i64, _i64, _i64, _i64, _vp]),
+    "midagma_dcor_run": (_int, [_vp, _vp, _i64, _i64, _vp, C.c_uint64, _int, _int, _i64, _dp, _vp, _dp]),
+    "midagma_dcor_perms": (_int, [_vp, _i64, _i64, C.c_uint64, _vp, _vp]),
+    "midagma_dcor_block": (_int, [_i64]),
 }
 
 GROUP_EMULATE = 1

@@ -1,5 +1,5 @@
-// Pearson and Spearman on the device: average-tie column ranks of a row-major X (midagma_colrank)
-// and the Pearson correlation matrix of its columns (midagma_corr).  Spearman is midagma_corr on
+// Pearson and Spearman on the device: average-tie column ranks of a row-major X (midagma_colrank),
+// the columns' stable argsort (midagma_colargsort) and the Pearson correlation matrix of its columns (midagma_corr).  Spearman is midagma_corr on
 // the ranks.  The analytic p-values are host work (midagma_amd/mi_tests.py).
 //
 // Ranks: a chunk of columns at a time (the chunk's scratch fits the byte budget).  The chunk is
@@ -14,7 +14,9 @@
 // side from them.  Tie runs come from head / tail flags of the sorted keys within a wave and, for
 // a run that crosses the wave's 64 positions, one binary search on the sorted column, so the cost
 // does not depend on the run length.  The ranks are scattered into the column's free key buffer
-// (a column-major image) and go to R by tiles through LDS.
+// (a column-major image) and go to R by tiles through LDS.  midagma_colargsort returns the sorted row
+// payloads instead (the stable argsort of every column); the eight passes are launch_segsort of
+// colsort.h, which dcor.hip also runs on the keys of its permutations.
 //
 // Correlations: one pass gives every column's sum, min and max (constant iff max == min on the raw
 // values); X minus the column means is staged in zero-padded row chunks and goes through the FP64
@@ -26,6 +28,7 @@
 #include <limits>
 #include <string>
 
+#include "colsort.h"
 #include "devmem.h"
 
 namespace {
@@ -267,6 +270,19 @@ corr_ranks_out_kernel(const uint64_t* __restrict__ K0, const uint64_t* __restric
   }
 }
 
+// the sorted payloads of segment c -> order[c n + i] and, with inverse, inverse[c n + payload] = i
+__global__ void __launch_bounds__(NTHREADS)
+corr_payload_out_kernel(const uint32_t* __restrict__ I0, const uint32_t* __restrict__ I1, int64_t n,
+                        const unsigned long long* __restrict__ key_or, const unsigned long long* __restrict__ key_and,
+                        int32_t* __restrict__ order, int32_t* __restrict__ inverse) {
+  const int64_t c = blockIdx.y, i = (int64_t)blockIdx.x * NTHREADS + threadIdx.x;
+  if (i >= n) return;
+  const int side = side_before(live_passes(key_or[c], key_and[c]), PASSES);
+  const uint32_t row = ((side ? I1 : I0) + c * n)[i];
+  order[c * n + i] = (int32_t)row;
+  if (inverse && row < (uint64_t)n) inverse[c * n + row] = (int32_t)i;
+}
+
 // --- correlations ------------------------------------------------------------------------------
 constexpr int CS_COLS = 64;
 
@@ -405,6 +421,76 @@ const char* bad_args(const void* X, int64_t n, int64_t d, int64_t ldx, const voi
 
 }  // namespace
 
+namespace midagma {
+
+int64_t segsort_hist_per_segment(int64_t n) { return RADIX * ((n + SEG - 1) / SEG); }
+
+void launch_segsort(const SegSort& s, int64_t n, int64_t nseg, hipStream_t st) {
+  const int64_t S = (n + SEG - 1) / SEG;
+  const dim3 segs((unsigned)((S + WAVES - 1) / WAVES), (unsigned)nseg);
+  for (int pass = 0; pass < PASSES; ++pass) {
+    hipLaunchKernelGGL(corr_hist_kernel, segs, dim3(NTHREADS), 0, st, s.K0, s.K1, n, S, pass, s.key_or, s.key_and,
+                       s.hist);
+    hipLaunchKernelGGL(corr_scan_kernel, dim3((unsigned)nseg), dim3(RADIX), 0, st, S, pass, s.key_or, s.key_and,
+                       s.hist);
+    hipLaunchKernelGGL(corr_scatter_kernel, segs, dim3(NTHREADS), 0, st, s.K0, s.K1, s.I0, s.I1, n, S, pass, s.key_or,
+                       s.key_and, s.hist);
+    HIP_TRY(hipGetLastError());
+  }
+}
+
+void launch_segsort_payload(const SegSort& s, int64_t n, int64_t nseg, int32_t* order, int32_t* inverse,
+                            hipStream_t st) {
+  hipLaunchKernelGGL(corr_payload_out_kernel, dim3((unsigned)((n + NTHREADS - 1) / NTHREADS), (unsigned)nseg),
+                     dim3(NTHREADS), 0, st, s.I0, s.I1, n, s.key_or, s.key_and, order, inverse);
+  HIP_TRY(hipGetLastError());
+}
+
+// midagma_colrank's chunk loop up to the sorted columns, then the payloads instead of the ranks
+void colargsort_run(const double* X_dev, int64_t n, int64_t d, int64_t ldx, int32_t* order_dev, int64_t budget_bytes,
+                    hipStream_t st) {
+  const RankPlan p = rank_plan(n, d, budget_bytes);
+  DevBuf<uint64_t> keys;
+  DevBuf<uint32_t> idx, hist;
+  DevBuf<unsigned long long> oa;
+  DevBuf<int> fl;
+  keys.alloc((size_t)p.key_count);
+  idx.alloc((size_t)p.idx_count);
+  hist.alloc((size_t)p.hist_count);
+  oa.alloc((size_t)(2 * p.cols));
+  fl.alloc(1);
+  HIP_TRY(hipMemsetAsync(fl.p, 0, sizeof(int), st));
+  const int64_t half = p.cols * n;
+  const SegSort s{keys.p, keys.p + half, idx.p, idx.p + half, oa.p, oa.p + p.cols, hist.p};
+  for (int64_t c0 = 0; c0 < d; c0 += p.cols) {
+    const int64_t nc = std::min(p.cols, d - c0);
+    HIP_TRY(hipMemsetAsync(s.key_or, 0, (size_t)nc * 8, st));
+    HIP_TRY(hipMemsetAsync(s.key_and, 0xff, (size_t)nc * 8, st));
+    const dim3 tiles((unsigned)((n + RT - 1) / RT), (unsigned)((nc + RT - 1) / RT));
+    hipLaunchKernelGGL(corr_keys_kernel, tiles, dim3(NTHREADS), 0, st, X_dev, n, ldx, c0, nc, s.K0, s.I0, s.key_or,
+                       s.key_and, fl.p);
+    HIP_TRY(hipGetLastError());
+    launch_segsort(s, n, nc, st);
+    launch_segsort_payload(s, n, nc, order_dev + c0 * n, nullptr, st);
+  }
+  int bad = 0;
+  HIP_TRY(hipMemcpyAsync(&bad, fl.p, sizeof(int), hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));  // (the scratch is freed on return)
+  if (bad) throw std::invalid_argument(std::string("colargsort: ") + kNonFiniteX);
+}
+
+}  // namespace midagma
+
+extern "C" int midagma_colargsort(const double* X_dev, int64_t n, int64_t d, int64_t ldx, int32_t* order_dev,
+                                  int64_t budget_bytes, void* stream) {
+  if (const char* why = bad_args(X_dev, n, d, ldx, order_dev, d))
+    return fail_global(MIDAGMA_E_ARG, std::string("colargsort: ") + why);
+  return corr_guarded([&] {
+    colargsort_run(X_dev, n, d, ldx, order_dev, budget_bytes, reinterpret_cast<hipStream_t>(stream));
+    return MIDAGMA_OK;
+  });
+}
+
 extern "C" int64_t midagma_corr_workspace(int64_t n, int64_t d, int64_t budget_bytes) {
   if (!shape_ok(n, d)) return 0;
   return std::max(rank_plan(n, d, budget_bytes).bytes, corr_plan(n, d, budget_bytes).bytes);
@@ -439,14 +525,7 @@ extern "C" int midagma_colrank(const double* X_dev, int64_t n, int64_t d, int64_
       hipLaunchKernelGGL(corr_keys_kernel, tiles, dim3(NTHREADS), 0, st, X_dev, n, ldx, c0, nc, K0, I0, kor, kand,
                          fl.p);
       HIP_TRY(hipGetLastError());
-      const dim3 segs((unsigned)((p.S + WAVES - 1) / WAVES), (unsigned)nc);
-      for (int pass = 0; pass < PASSES; ++pass) {
-        hipLaunchKernelGGL(corr_hist_kernel, segs, dim3(NTHREADS), 0, st, K0, K1, n, p.S, pass, kor, kand, hist.p);
-        hipLaunchKernelGGL(corr_scan_kernel, dim3((unsigned)nc), dim3(RADIX), 0, st, p.S, pass, kor, kand, hist.p);
-        hipLaunchKernelGGL(corr_scatter_kernel, segs, dim3(NTHREADS), 0, st, K0, K1, I0, I1, n, p.S, pass, kor, kand,
-                           hist.p);
-        HIP_TRY(hipGetLastError());
-      }
+      launch_segsort(SegSort{K0, K1, I0, I1, kor, kand, hist.p}, n, nc, st);
       hipLaunchKernelGGL(corr_tie_kernel, dim3((unsigned)((n + NTHREADS - 1) / NTHREADS), (unsigned)nc),
                          dim3(NTHREADS), 0, st, K0, K1, I0, I1, n, kor, kand);
       hipLaunchKernelGGL(corr_ranks_out_kernel, tiles, dim3(NTHREADS), 0, st, K0, K1, n, c0, nc, kor, kand, R_dev,

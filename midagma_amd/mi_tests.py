@@ -16,6 +16,13 @@ They agree with the per-pair path to rounding in the correlation ("Ra
 correlations") and return the same I wherever no p-value is within that rounding of alpha_eff.
 There is no CPU path for them either.
 
+The 'dcor' test of those functions sums n^2 terms an evaluation and stops at n = 16384.  Beside it,
+for any n < 2^31, stand three more functions the reference does not have: `dcor_null`, `dcor_tests`
+and `get_I_from_dcor_tests` (csrc/dcor.hip through `midagma_amd.solver.HipDcor`): the same
+statistic, exact, from a sort, block sums and cell tables in O(n sqrt(n)) work an evaluation, with
+the permutation p-value or the analytic chi-square p-value of the bias-corrected statistic
+("dCor without the n^2 sum").  They change nothing of the functions above.
+
 One keyword is added, ``perms``:
   * ``"numpy"`` (default): the host draws ``rng = np.random.default_rng(seed)`` once and calls
     ``rng.permutation(n)`` num_perm times per pair, in pair order -- the reference's stream, so the
@@ -47,11 +54,11 @@ from typing import Iterable, List, Literal, Optional, Tuple
 
 import numpy as np
 
-from .solver import HipIndep, is_device_tensor
+from .solver import HipDcor, HipIndep, is_device_tensor
 
 __all__ = ["IndepTestResult", "hsic_stat", "dcor_stat", "permutation_null", "test_pairwise_independence",
            "get_I_from_full_pairwise_tests", "summarize_I", "median_sigma2", "correlation_tests",
-           "get_I_from_correlation_tests"]
+           "get_I_from_correlation_tests", "dcor_null", "dcor_tests", "get_I_from_dcor_tests"]
 
 TestName = Literal["hsic", "dcor", "pearson", "spearman"]
 
@@ -398,6 +405,152 @@ def get_I_from_correlation_tests(X, *, alpha: float = 0.05, test: str = "pearson
     if not keep.any():
         return np.asarray([], dtype=int)
     return np.stack([i[keep], j[keep]], axis=1).astype(int)
+
+
+def _I_from_pvalues(p: np.ndarray, alpha: float, bonferroni: bool, undirected: bool,
+                    exclude_diagonal: bool) -> np.ndarray:
+    d = p.shape[0]
+    if undirected:
+        i, j = np.triu_indices(d, 1)
+    else:
+        i, j = np.divmod(np.arange(d * d), d)
+        if exclude_diagonal:
+            i, j = i[i != j], j[i != j]
+    m = len(i)
+    alpha_eff = (alpha / m) if (bonferroni and m > 0) else alpha
+    keep = p[i, j] > alpha_eff
+    if not keep.any():
+        return np.asarray([], dtype=int)
+    return np.stack([i[keep], j[keep]], axis=1).astype(int)
+
+
+def _as_dcor_data(X):
+    """`_as_data` without the cap on n (the engine checks a device X for inf and nan itself)."""
+    if is_device_tensor(X):
+        HipDcor._check_tensor(X)
+        return X
+    X = np.array(X, dtype=np.float64, order="C", copy=True)
+    if X.ndim != 2:
+        raise ValueError("X must be a 2-d array (n samples x d variables)")
+    if X.shape[0] < 2:
+        raise ValueError("need at least 2 samples")
+    if not np.isfinite(X).all():
+        raise ValueError("X holds inf or nan")
+    return X
+
+
+def _dcor_null(eng: HipDcor, pairs: np.ndarray, P: int, seed: int, perms, unbiased: bool, budget_bytes: int,
+               return_null: bool, block: int):
+    n, m = eng.n, len(pairs)
+    kw = dict(unbiased=unbiased, block=block, budget_bytes=budget_bytes, return_null=True)
+    if isinstance(perms, str) and perms == "device":
+        stat, ge, null = eng.run(pairs, P, None, seed, **kw)
+    elif isinstance(perms, str):
+        rng = np.random.default_rng(seed)
+        stat, ge, null = np.zeros(m), np.zeros(m, dtype=np.int64), np.zeros((m, P))
+        chunk = max(1, _HOST_CHUNK_BYTES // max(1, 4 * P * n))
+        for q0 in range(0, m, chunk):
+            q1 = min(m, q0 + chunk)
+            pm = _numpy_perms(rng, q1 - q0, P, n)
+            stat[q0:q1], ge[q0:q1], null[q0:q1] = eng.run(pairs[q0:q1], P, pm, 0, **kw)
+    else:
+        stat, ge, null = eng.run(pairs, P, perms, 0, **kw)
+    return stat, ge, (null if return_null else None)
+
+
+def dcor_null(X, pairs, *, num_perm: int = 200, seed: int = 0, perms="numpy", unbiased: bool = False,
+              device: int = 0, budget_bytes: int = 0, return_null: bool = True, block: int = 0):
+    """`permutation_null(test="dcor")` without the n^2 sum and without its cap on n (csrc/dcor.hip:
+    a sort, block sums and cell tables, exact in O(n sqrt(n)) work an evaluation): (stat, ge, null)
+    with the same conventions, to rounding the same values.
+    perms: ``"numpy"`` draws one ``default_rng(seed)`` exactly as `permutation_null` does (pair
+    order, num_perm permutations each); ``"device"`` makes them on the GPU by this path's own rule
+    (the stable argsort of 64 Philox bits per row, DESIGN.md, so not `permutation_null`'s device
+    stream); an int32 array (m, num_perm, n) is taken as given (every row must be a permutation).
+    unbiased: the bias-corrected R_U = dcov^2_U / sqrt(dvar_U,x dvar_U,y) (U-centring; needs n >= 4),
+    counted by dcov^2_U.  budget_bytes: the device scratch per chunk of evaluations (0: 2 GiB);
+    block: the block edge (0: the rule; tests); results do not depend on the budget."""
+    if isinstance(perms, str) and perms not in ("numpy", "device"):
+        raise ValueError("perms must be 'numpy', 'device' or an int32 array (m, num_perm, n)")
+    X = _as_dcor_data(X)
+    n, d = int(X.shape[0]), int(X.shape[1])
+    pairs = _as_pairs(pairs, d)
+    P = int(num_perm)
+    if P < 0:
+        raise ValueError("num_perm must be >= 0")
+    if unbiased and n < 4:
+        raise ValueError("the bias-corrected statistic needs n >= 4")
+    if not (block == 0 or 4 <= int(block) <= 1024):
+        raise ValueError("block must be 0 or in [4, 1024]")
+    if not isinstance(perms, str):
+        perms = np.ascontiguousarray(perms, dtype=np.int32)
+        if perms.shape != (len(pairs), P, n):
+            raise ValueError(f"perms must be {(len(pairs), P, n)}, got {perms.shape}")
+    eng = HipDcor(X, device, budget_bytes)
+    try:
+        return _dcor_null(eng, pairs, P, seed, perms, unbiased, budget_bytes, return_null, int(block))
+    finally:
+        eng.close()
+
+
+def dcor_tests(X, *, pvalue: str = "permutation", num_perm: int = 200, seed: int = 0, perms="device",
+               device: int = 0, budget_bytes: int = 0):
+    """(stat, p), two d x d host arrays: the dCor test of every pair i < j of X's columns, in the
+    reference's pair order, mirrored to (j, i); the diagonal is (1, 0) by rule and a pair with a
+    zero-range column is (0, 1).
+    pvalue="permutation": stat is the reference's dCor (`dcor_null`), p = (ge + 1) / (num_perm + 1).
+    pvalue="chi2": one evaluation a pair, no permutations: stat is the bias-corrected R_U and
+    p = chi2.sf(n R_U + 1, 1), the chi-square test of Shen, Panda and Vogelstein, "The chi-square test
+    of distance correlation" (valid and slightly conservative at alpha <= 0.05).  It is not in the
+    reference, which has only the permutation test.  n < 4 raises ValueError."""
+    if pvalue not in ("permutation", "chi2"):
+        raise ValueError("pvalue must be 'permutation' or 'chi2'")
+    if isinstance(perms, str) and perms not in ("numpy", "device"):
+        raise ValueError("perms must be 'numpy' or 'device'")
+    X = _as_dcor_data(X)
+    n, d = int(X.shape[0]), int(X.shape[1])
+    if pvalue == "chi2" and n < 4:
+        raise ValueError("the chi-square test needs n >= 4")
+    P = int(num_perm)
+    if P < 0:
+        raise ValueError("num_perm must be >= 0")
+    iu = np.triu_indices(d, 1)
+    pairs = np.stack(iu, axis=1).astype(np.int64)
+    stat, p = np.ones((d, d)), np.zeros((d, d))
+    if len(pairs):
+        eng = HipDcor(X, device, budget_bytes)
+        try:
+            if pvalue == "chi2":
+                from scipy import stats
+                s, ge, _ = _dcor_null(eng, pairs, 0, 0, "device", True, budget_bytes, False, 0)
+                zero = _zero_range(X)  # (their R_U is 0 by rule, and the rule's p is 1, not chi2.sf(1))
+                pv = np.where(zero[iu[0]] | zero[iu[1]], 1.0, stats.chi2.sf(n * s + 1.0, 1))
+            else:
+                s, ge, _ = _dcor_null(eng, pairs, P, seed, perms, False, budget_bytes, False, 0)
+                pv = (ge + 1.0) / (P + 1.0)
+        finally:
+            eng.close()
+        stat[iu], p[iu] = s, pv
+        stat.T[iu], p.T[iu] = s, pv
+    return stat, p
+
+
+def _zero_range(X) -> np.ndarray:
+    """max == min per column, on the raw values."""
+    if is_device_tensor(X):
+        return (X.max(dim=0).values == X.min(dim=0).values).cpu().numpy()
+    return X.max(axis=0) == X.min(axis=0)
+
+
+def get_I_from_dcor_tests(X, *, alpha: float = 0.05, pvalue: str = "permutation", num_perm: int = 200,
+                          seed: int = 0, perms="device", bonferroni: bool = True, undirected: bool = True,
+                          exclude_diagonal: bool = True, device: int = 0) -> np.ndarray:
+    """`get_I_from_full_pairwise_tests(test="dcor")` through `dcor_tests`: I = {(i, j): p > alpha_eff}
+    in the reference's pair order, built from p exactly as `get_I_from_correlation_tests` builds it
+    (alpha_eff = alpha / #pairs under Bonferroni; the same dtype and shape, the empty case included).
+    With perms="numpy" and undirected=True the p-values are `permutation_null`'s."""
+    _, p = dcor_tests(X, pvalue=pvalue, num_perm=num_perm, seed=seed, perms=perms, device=device)
+    return _I_from_pvalues(p, alpha, bonferroni, undirected, exclude_diagonal)
 
 
 def summarize_I(I: np.ndarray, d: int, max_show: int = 10) -> None:

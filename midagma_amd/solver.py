@@ -849,6 +849,141 @@ class HipIndep:
         return tuple(out)
 
 
+def column_argsort(X, budget_bytes: int = 0):
+    """order (d x n int32 device tensor): order[c, i] = the row at position i of the stable argsort
+    of column c of X (-0.0 equal to +0.0), the row payload of `column_ranks`' radix sort
+    (`midagma_colargsort`).  X and budget_bytes as in `column_ranks`."""
+    import torch
+    X = _device_matrix(X, "column_argsort")
+    n, d, ld = _rows(X)
+    order = torch.empty((d, n), dtype=torch.int32, device=X.device)
+    with torch.cuda.device(X.device):
+        check(_lib.lib().midagma_colargsort(C.c_void_p(X.data_ptr()), n, d, ld, C.c_void_p(order.data_ptr()),
+                                            int(budget_bytes), _cur_stream(X.device)), None, "column_argsort")
+    return order
+
+
+class HipDcor:
+    """dCor permutation tests of pairs of columns without the n^2 sum, on one GPU
+    (`midagma_dcor_*`, csrc/dcor.hip): the engine under `mi_tests.dcor_null` / `dcor_tests`, for
+    2 <= n < 2^31.  Holds the per-column sorts, centred values and row sums of X (24 bytes a value).
+
+    X is a host array (copied to `device`), or a 2-d float64 torch CUDA tensor: the engine then
+    lives on the tensor's device (`device` is ignored), reads X there on torch's current stream
+    without a host copy and never writes it.  No synchronise is needed around the call."""
+
+    def __init__(self, X, device: int = 0, budget_bytes: int = 0):
+        self.L = _lib.lib()
+        self.h = None
+        self.n = self.d = 0
+        on_device = is_device_tensor(X)
+        if on_device:
+            self._check_tensor(X)
+            device = X.device.index
+        else:
+            X = self._check_array(X)
+        h = C.c_void_p()
+        self._check(self.L.midagma_dcor_create(C.byref(h), int(device)), None, "dcor_create")
+        self.h = h
+        try:
+            self.set_data(X, budget_bytes)
+        except Exception:
+            self.close()
+            raise
+
+    @staticmethod
+    def _check_tensor(X):
+        import torch
+        if X.dtype != torch.float64 or X.dim() != 2:
+            raise ValueError("a device X must be a 2-d float64 tensor (n x d)")
+        if int(X.shape[0]) < 2 or int(X.shape[1]) < 1:
+            raise ValueError("need at least 2 samples and 1 variable")
+
+    @staticmethod
+    def _check_array(X) -> np.ndarray:
+        X = _as_f64(X)  # (the library copies it to the device and never writes it)
+        if X.ndim != 2:
+            raise ValueError("X must be n x d")
+        if X.shape[0] < 2 or X.shape[1] < 1:
+            raise ValueError("need at least 2 samples and 1 variable")
+        if not np.isfinite(X).all():
+            raise ValueError("X holds inf or nan")
+        return X
+
+    def set_data(self, X, budget_bytes: int = 0):
+        """Replace the engine's data and run the per-column pre-pass.  When the library rejects a
+        device X (inf or nan), the engine holds no data."""
+        self.n = self.d = 0
+        if is_device_tensor(X):
+            self._check_tensor(X)
+            if X.stride(1) != 1 or X.stride(0) < X.shape[1]:
+                X = X.contiguous()
+            n, d, ld = _rows(X)
+            rc = self.L.midagma_dcor_set_data_dev(self.h, C.c_void_p(X.data_ptr()), n, d, ld, int(budget_bytes),
+                                                  _cur_stream(X.device))
+            self._check(rc, self.h, "dcor_set_data_dev")
+        else:
+            X = self._check_array(X)
+            n, d = int(X.shape[0]), int(X.shape[1])
+            self._check(self.L.midagma_dcor_set_data(self.h, dptr(X), n, d, int(budget_bytes)), self.h,
+                        "dcor_set_data")
+        self.n, self.d = n, d
+
+    def _check(self, rc, handle, what):
+        if rc >= 0:
+            return rc
+        m = self.L.midagma_dcor_last_error(handle)
+        msg = m.decode() if m else ""
+        if rc == _lib.E_ARG:
+            raise ValueError(f"{what}: {msg}")
+        raise _lib.HipSolverError(f"{what} failed ({rc}): {msg}")
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.L.midagma_dcor_destroy(self.h)
+            self.h = None
+
+    def __del__(self):  # pragma: no cover
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def run(self, pairs, P: int, perms=None, seed: int = 0, *, unbiased: bool = False, block: int = 0,
+            budget_bytes: int = 0, return_null: bool = False):
+        """(stat, ge[, null]) per pair, as `HipIndep.run("dcor", ...)`; unbiased: the bias-corrected
+        R_U, counted by dcov^2_U.  perms: explicit m x P x n int32 permutations, or None for device
+        permutations from `seed` (csrc/dcor.hip's rule).  block: the block edge (0: the rule)."""
+        pairs = np.ascontiguousarray(pairs, dtype=np.int64).reshape(-1, 2)
+        m, P = int(pairs.shape[0]), int(P)
+        if perms is not None:
+            perms = np.ascontiguousarray(perms, dtype=np.int32)
+            if perms.shape != (m, P, self.n):
+                raise ValueError(f"perms must be {(m, P, self.n)}, got {perms.shape}")
+        stat = np.zeros(m)
+        ge = np.zeros(m, dtype=np.int64)
+        null = np.zeros((m, max(P, 0))) if return_null else None
+
+        def vp(a):
+            return None if a is None or a.size == 0 else C.c_void_p(a.ctypes.data)
+
+        rc = self.L.midagma_dcor_run(self.h, vp(pairs), m, P, vp(perms), C.c_uint64(int(seed) & (2**64 - 1)),
+                                     int(bool(unbiased)), int(block), int(budget_bytes), dptr(stat), vp(ge),
+                                     dptr(null) if (return_null and null.size) else None)
+        self._check(rc, self.h, "dcor_run")
+        return (stat, ge, null) if return_null else (stat, ge)
+
+    def device_perms(self, q: int, P: int, seed: int = 0, inverse: bool = False):
+        """The P device permutations (P x n int32) of pair q of a call with this seed, and with
+        `inverse` their inverses."""
+        out = np.zeros((int(P), self.n), dtype=np.int32)
+        inv = np.zeros((int(P), self.n), dtype=np.int32) if inverse else None
+        rc = self.L.midagma_dcor_perms(self.h, int(q), int(P), C.c_uint64(int(seed) & (2**64 - 1)),
+                                       C.c_void_p(out.ctypes.data), None if inv is None else C.c_void_p(inv.ctypes.data))
+        self._check(rc, self.h, "dcor_perms")
+        return (out, inv) if inverse else out
+
+
 class HipBatch:
     """B independent small-d problems (d <= 64, l2, cov mode, float64) on one GPU, one persistent
     workgroup each (`midagma_batch_*`, csrc/batch.hip).  The problems share d and the loop
