@@ -228,16 +228,17 @@ def last_error(handle=None) -> str:
     return msg.decode() if msg else ""
 
 
-def check(rc: int, handle=None, what: str = "", group: bool = False):
+def check(rc: int, handle=None, what: str = "", getter=None):
     """Raise for a negative return code: LinAlgError (singular), ValueError (bad argument,
-    non-finite input) or HipSolverError; `group`: the handle is a midagma_group."""
+    non-finite input) or HipSolverError.  `getter`: the `*_last_error` entry of the handle's
+    family (None: midagma_last_error, the solver's and the handle-less entries')."""
     if rc >= 0:
         return rc
-    if group:
-        m = lib().midagma_group_last_error(handle)
-        msg = m.decode() if m else ""
-    else:
+    if getter is None:
         msg = last_error(handle)
+    else:
+        m = getter(handle)
+        msg = m.decode() if m else ""
     if rc == E_SINGULAR:
         raise np.linalg.LinAlgError(msg or "singular matrix")
     if rc == E_ARG:

@@ -123,3 +123,65 @@ void launch_adam_gated(double* p, const double* g, double* m, double* v, int64_t
 }
 
 }  // namespace midagma
+
+using namespace midagma;
+
+// ---- the C entries: gated Adam steps for DagmaNonlinear on torch tensors ----
+extern "C" int midagma_adam_step(double* p, const double* g, double* m, double* v, int64_t n, double step_size,
+                                 double w1, double beta2, double c2, double bc2_sqrt, double eps, double wd,
+                                 const double* gate, void* stream) {
+  if (!p || !g || !m || !v || n < 0) return abi_fail(nullptr, MIDAGMA_E_ARG, "adam_step: bad arguments");
+  if (n == 0) return MIDAGMA_OK;
+  return abi_guarded(nullptr, [&] {
+    launch_adam_gated(p, g, m, v, n, AdamCoef{step_size, w1, beta2, c2, bc2_sqrt, eps, wd}, gate,
+                      reinterpret_cast<hipStream_t>(stream));
+    return MIDAGMA_OK;
+  });
+}
+
+extern "C" int midagma_adam_step_table(double* p, const double* g, double* m, double* v, int64_t n,
+                                       const double* table, const int64_t* counter, double w1, double beta2,
+                                       double c2, double eps, double wd, const double* gate, void* stream) {
+  if (!p || !g || !m || !v || !table || !counter || n < 0)
+    return abi_fail(nullptr, MIDAGMA_E_ARG, "adam_step_table: bad arguments");
+  if (n == 0) return MIDAGMA_OK;
+  return abi_guarded(nullptr, [&] {
+    launch_adam_gated_table(p, g, m, v, n, AdamCoef{0.0, w1, beta2, c2, 1.0, eps, wd}, table, counter, gate,
+                            reinterpret_cast<hipStream_t>(stream));
+    return MIDAGMA_OK;
+  });
+}
+
+extern "C" int midagma_adam_step_table_multi(int64_t k, double* const* p, const double* const* g, double* const* m,
+                                             double* const* v, const int64_t* n, const double* table,
+                                             const int64_t* counter, double w1, double beta2, double c2, double eps,
+                                             double wd, const double* gate, void* stream) {
+  if (k < 1 || k > ADAM_MULTI || !p || !g || !m || !v || !n || !table || !counter)
+    return abi_fail(nullptr, MIDAGMA_E_ARG, "adam_step_table_multi: bad arguments");
+  AdamSet set{};
+  set.k = (int)k;
+  set.off[0] = 0;
+  for (int64_t q = 0; q < k; ++q) {
+    if (!p[q] || !g[q] || !m[q] || !v[q] || n[q] < 0)
+      return abi_fail(nullptr, MIDAGMA_E_ARG, "adam_step_table_multi: bad tensor");
+    set.p[q] = p[q];
+    set.g[q] = g[q];
+    set.m[q] = m[q];
+    set.v[q] = v[q];
+    set.off[q + 1] = set.off[q] + n[q];
+  }
+  if (set.off[k] == 0) return MIDAGMA_OK;
+  return abi_guarded(nullptr, [&] {
+    launch_adam_gated_table_multi(set, AdamCoef{0.0, w1, beta2, c2, 1.0, eps, wd}, table, counter, gate,
+                                  reinterpret_cast<hipStream_t>(stream));
+    return MIDAGMA_OK;
+  });
+}
+
+extern "C" int midagma_counter_advance(int64_t* counter, void* stream) {
+  if (!counter) return abi_fail(nullptr, MIDAGMA_E_ARG, "counter_advance: null counter");
+  return abi_guarded(nullptr, [&] {
+    launch_counter_advance(counter, reinterpret_cast<hipStream_t>(stream));
+    return MIDAGMA_OK;
+  });
+}

@@ -23,7 +23,6 @@
 
 namespace {
 
-thread_local std::string g_batch_err;
 constexpr int64_t kMaxBatch = 16384;
 
 // The listed problems' d x d blocks between the compact host layout (B x d x d) and the padded
@@ -210,36 +209,16 @@ void midagma_batch::trek_value(const double* Wh, double* value, double* grad) {
     HIP_TRY(hipStreamSynchronize(stream));
 }
 
-int midagma::batch_fail(midagma_batch* h, int code, const std::string& msg) {
-  (h ? h->err : g_batch_err) = msg;
-  return code;
-}
-
-namespace {
-
-int bfail(midagma_batch* h, int code, const std::string& msg) { return batch_fail(h, code, msg); }
-
-template <class F>
-int bguarded(midagma_batch* h, F&& f) {
-  return batch_guarded(h, std::forward<F>(f));
-}
-
-}  // namespace
-
-extern "C" const char* midagma_batch_last_error(const midagma_batch* h) {
-  return (h ? h->err : g_batch_err).c_str();
-}
+extern "C" const char* midagma_batch_last_error(const midagma_batch* h) { return abi_last_error(h); }
 
 extern "C" int midagma_batch_create(midagma_batch** out, int64_t d, int64_t B, int device) {
   if (!out || d < 1 || d > 64 || B < 1 || B > kMaxBatch || device < 0)
-    return bfail(nullptr, MIDAGMA_E_ARG, "batch_create: need 1 <= d <= 64, 1 <= B <= 16384 and a device");
+    return abi_fail(no_handle<midagma_batch>, MIDAGMA_E_ARG,
+                    "batch_create: need 1 <= d <= 64, 1 <= B <= 16384 and a device");
   *out = nullptr;
   midagma_batch* h = nullptr;
-  const int rc = bguarded(nullptr, [&] {
-    int count = 0;
-    HIP_TRY(hipGetDeviceCount(&count));
-    if (device >= count) throw std::invalid_argument("batch_create: no such device");
-    HIP_TRY(hipSetDevice(device));
+  const int rc = abi_guarded(no_handle<midagma_batch>, [&] {
+    open_device(device, "batch_create: ");
     h = new midagma_batch;
     h->d = d;
     h->D = round_up64(d);
@@ -263,18 +242,18 @@ extern "C" void midagma_batch_destroy(midagma_batch* h) {
 }
 
 extern "C" int midagma_batch_set_cov(midagma_batch* h, const double* cov) {
-  if (!h || !cov) return bfail(h, MIDAGMA_E_ARG, "batch_set_cov: null argument");
+  if (!h || !cov) return abi_fail(h, MIDAGMA_E_ARG, "batch_set_cov: null argument");
   if (!finite_block(cov, h->B * h->d * h->d))
-    return bfail(h, MIDAGMA_E_ARG, "batch_set_cov: array must not contain infs or NaNs");
-  return bguarded(h, [&] {
+    return abi_fail(h, MIDAGMA_E_ARG, "batch_set_cov: array must not contain infs or NaNs");
+  return abi_guarded(h, [&] {
     h->upload_all(h->cov, cov);
     h->has_cov = true;
   });
 }
 
 extern "C" int midagma_batch_set_masks(midagma_batch* h, const double* mask_inc, const double* mask_exc) {
-  if (!h) return bfail(h, MIDAGMA_E_ARG, "batch_set_masks: null handle");
-  return bguarded(h, [&] {
+  if (!h) return abi_fail(h, MIDAGMA_E_ARG, "batch_set_masks: null handle");
+  return abi_guarded(h, [&] {
     const size_t n = (size_t)h->B * h->D * h->D;
     if (mask_inc) {
       h->minc.alloc(n);
@@ -293,25 +272,26 @@ extern "C" int midagma_batch_minimize(midagma_batch* h, double* W, const double*
                                       const double* lr, const double* lambda1, int64_t max_iter, double tol,
                                       double beta1, double beta2, int64_t checkpoint, const uint8_t* active,
                                       midagma_result* res) {
-  if (!h) return bfail(h, MIDAGMA_E_ARG, "batch_minimize: null handle");
-  if (!W || !mu || !s_dom || !lr || !lambda1 || !res) return bfail(h, MIDAGMA_E_ARG, "batch_minimize: null argument");
+  if (!h) return abi_fail(h, MIDAGMA_E_ARG, "batch_minimize: null handle");
+  if (!W || !mu || !s_dom || !lr || !lambda1 || !res)
+    return abi_fail(h, MIDAGMA_E_ARG, "batch_minimize: null argument");
   if (max_iter < 1 || checkpoint < 1)
-    return bfail(h, MIDAGMA_E_ARG, "batch_minimize: max_iter and checkpoint must be >= 1");
-  if (!h->has_cov) return bfail(h, MIDAGMA_E_ARG, "batch_minimize: set_cov before minimize");
+    return abi_fail(h, MIDAGMA_E_ARG, "batch_minimize: max_iter and checkpoint must be >= 1");
+  if (!h->has_cov) return abi_fail(h, MIDAGMA_E_ARG, "batch_minimize: set_cov before minimize");
   const int64_t dd = h->d * h->d;
   for (int64_t b = 0; b < h->B; ++b)
     if ((!active || active[b]) && !finite_block(W + b * dd, dd))
-      return bfail(h, MIDAGMA_E_ARG, "batch_minimize: array must not contain infs or NaNs");
-  return bguarded(h, [&] {
+      return abi_fail(h, MIDAGMA_E_ARG, "batch_minimize: array must not contain infs or NaNs");
+  return abi_guarded(h, [&] {
     h->minimize(W, mu, s_dom, lr, lambda1, max_iter, tol, beta1, beta2, checkpoint, active, res);
   });
 }
 
 extern "C" int64_t midagma_batch_checkpoints(midagma_batch* h, int64_t b, midagma_ckpt* out, int64_t cap) {
-  if (!h || b < 0 || b >= h->B) return bfail(h, MIDAGMA_E_ARG, "batch_checkpoints: bad arguments");
+  if (!h || b < 0 || b >= h->B) return abi_fail(h, MIDAGMA_E_ARG, "batch_checkpoints: bad arguments");
   if (!h->last_active[b] || !h->d_ckpt.p) return 0;
   int64_t n = 0;
-  const int rc = bguarded(h, [&] {
+  const int rc = abi_guarded(h, [&] {
     n = std::max<int64_t>(0, std::min<int64_t>(std::min<int64_t>(h->h_state.p[b].n_ckpt, h->ckpt_cap), cap));
     static_assert(sizeof(midagma_ckpt) == sizeof(CkptRec), "ckpt layout");
     if (n > 0 && out)
@@ -322,32 +302,33 @@ extern "C" int64_t midagma_batch_checkpoints(midagma_batch* h, int64_t b, midagm
 
 extern "C" int midagma_btrek_set(midagma_batch* h, int seq, int agg, int mode, const double* weight, double eps_inv,
                                  const int64_t* pairs, int64_t m) {
-  if (!h) return bfail(h, MIDAGMA_E_ARG, "btrek_set: null handle");
-  if (mode < 0 || mode > 2 || m < 0) return bfail(h, MIDAGMA_E_ARG, "btrek_set: bad mode or pair count");
+  if (!h) return abi_fail(h, MIDAGMA_E_ARG, "btrek_set: null handle");
+  if (mode < 0 || mode > 2 || m < 0) return abi_fail(h, MIDAGMA_E_ARG, "btrek_set: bad mode or pair count");
   if (mode != 0 && m > 0) {
-    if (!weight || !pairs) return bfail(h, MIDAGMA_E_ARG, "btrek_set: null argument");
-    if (h->d > 32) return bfail(h, MIDAGMA_E_ARG, "btrek_set: the PST regularizer in a batch needs d <= 32");
+    if (!weight || !pairs) return abi_fail(h, MIDAGMA_E_ARG, "btrek_set: null argument");
+    if (h->d > 32) return abi_fail(h, MIDAGMA_E_ARG, "btrek_set: the PST regularizer in a batch needs d <= 32");
     if (seq != midagma::TREK_EXP && seq != midagma::TREK_INV)
-      return bfail(h, MIDAGMA_E_ARG, "btrek_set: a batch runs seq exp and inv (not log or binom)");
-    if (agg < midagma::TREK_MEAN || agg > midagma::TREK_LSE) return bfail(h, MIDAGMA_E_ARG, "btrek_set: unknown agg");
+      return abi_fail(h, MIDAGMA_E_ARG, "btrek_set: a batch runs seq exp and inv (not log or binom)");
+    if (agg < midagma::TREK_MEAN || agg > midagma::TREK_LSE)
+      return abi_fail(h, MIDAGMA_E_ARG, "btrek_set: unknown agg");
     for (int64_t p = 0; p < 2 * m; ++p)
-      if (pairs[p] < 0 || pairs[p] >= h->d) return bfail(h, MIDAGMA_E_ARG, "btrek_set: pair index outside [0, d)");
+      if (pairs[p] < 0 || pairs[p] >= h->d) return abi_fail(h, MIDAGMA_E_ARG, "btrek_set: pair index outside [0, d)");
     if (!finite_block(weight, h->B) || !std::isfinite(eps_inv))
-      return bfail(h, MIDAGMA_E_ARG, "btrek_set: weight and eps_inv must be finite");
+      return abi_fail(h, MIDAGMA_E_ARG, "btrek_set: weight and eps_inv must be finite");
   }
-  return bguarded(h, [&] { h->set_trek(seq, agg, mode, weight, eps_inv, pairs, m); });
+  return abi_guarded(h, [&] { h->set_trek(seq, agg, mode, weight, eps_inv, pairs, m); });
 }
 
 extern "C" int midagma_btrek_value(midagma_batch* h, const double* W, double* value, double* grad) {
-  if (!h) return bfail(h, MIDAGMA_E_ARG, "btrek_value: null handle");
-  if (!W || !value) return bfail(h, MIDAGMA_E_ARG, "btrek_value: null argument");
+  if (!h) return abi_fail(h, MIDAGMA_E_ARG, "btrek_value: null handle");
+  if (!W || !value) return abi_fail(h, MIDAGMA_E_ARG, "btrek_value: null argument");
   if (!finite_block(W, h->B * h->d * h->d))
-    return bfail(h, MIDAGMA_E_ARG, "btrek_value: array must not contain infs or NaNs");
+    return abi_fail(h, MIDAGMA_E_ARG, "btrek_value: array must not contain infs or NaNs");
   if (!h->trek.mode) {  // no regularizer: notreks gives (0, 0) for an empty pair set
     for (int64_t b = 0; b < h->B; ++b) value[b] = 0.0;
     if (grad)
       for (int64_t e = 0; e < h->B * h->d * h->d; ++e) grad[e] = 0.0;
     return MIDAGMA_OK;
   }
-  return bguarded(h, [&] { h->trek_value(W, value, grad); });
+  return abi_guarded(h, [&] { h->trek_value(W, value, grad); });
 }

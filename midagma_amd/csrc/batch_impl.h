@@ -1,6 +1,6 @@
 // The batch of small-d problems behind the midagma_batch_* and midagma_boot_* entries: the handle
 // that batch.hip (create, set_cov, masks, minimize) and boot.hip (the bootstrap covariances written
-// into the handle's cov slabs) share, and the error plumbing of their entry points.
+// into the handle's cov slabs) share.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -61,25 +61,5 @@ struct midagma_batch {
   void trek_value(const double* Wh, double* value, double* grad);
 };
 
-namespace midagma {
-
-constexpr const char* kBatchNonFinite = "array must not contain infs or NaNs";
-
-// the message of a failed entry: on the handle, or thread-local for a call without one
-// (midagma_batch_last_error reads either)
-int batch_fail(midagma_batch* h, int code, const std::string& msg);
-
-template <class F>
-int batch_guarded(midagma_batch* h, F&& f) {
-  try {
-    if (h) HIP_TRY(hipSetDevice(h->device));
-    f();
-    return MIDAGMA_OK;
-  } catch (...) {
-    std::string msg;
-    const int rc = classify(std::current_exception(), msg);
-    return batch_fail(h, rc, msg);
-  }
-}
-
-}  // namespace midagma
+// abi.h's hook: an entry's device work runs on the batch's device
+inline void abi_select_device(const midagma_batch* h) { HIP_TRY(hipSetDevice(h->device)); }

@@ -239,7 +239,7 @@ void boot_cov(midagma_batch* h, const void* X, int64_t n, int64_t ldx, bool on_d
   int bad = 0;
   HIP_TRY(hipMemcpyAsync(&bad, flag, sizeof(int), hipMemcpyDeviceToHost, st));
   HIP_TRY(hipStreamSynchronize(st));
-  if (bad) throw std::invalid_argument(std::string("boot_cov: ") + kBatchNonFinite);  // (cov is untouched)
+  if (bad) throw std::invalid_argument(std::string("boot_cov: ") + kNonFinite);  // (cov is untouched)
   float ms = 0.f;
   HIP_TRY(hipEventElapsedTime(&ms, ev[0], ev[1]));
   h->boot_ms[0] = ms;
@@ -281,7 +281,7 @@ void boot_cov(midagma_batch* h, const void* X, int64_t n, int64_t ldx, bool on_d
       h->boot_ms[k] += ms;
     }
   }
-  if (bad) throw std::invalid_argument(std::string("boot_cov: ") + kBatchNonFinite);
+  if (bad) throw std::invalid_argument(std::string("boot_cov: ") + kNonFinite);
   h->has_cov = true;
 }
 
@@ -289,22 +289,22 @@ void boot_cov(midagma_batch* h, const void* X, int64_t n, int64_t ldx, bool on_d
 
 extern "C" int midagma_boot_cov(midagma_batch* h, const void* X, int64_t n, int64_t ldx, int on_device,
                                 uint64_t seed, int64_t first, int64_t budget_bytes) {
-  if (!h || !X) return batch_fail(h, MIDAGMA_E_ARG, "boot_cov: null argument");
-  if (n < 1 || n >= (int64_t(1) << 31)) return batch_fail(h, MIDAGMA_E_ARG, "boot_cov: need 1 <= n < 2^31");
-  if (ldx < h->d) return batch_fail(h, MIDAGMA_E_ARG, "boot_cov: ldx < d");
+  if (!h || !X) return abi_fail(h, MIDAGMA_E_ARG, "boot_cov: null argument");
+  if (n < 1 || n >= (int64_t(1) << 31)) return abi_fail(h, MIDAGMA_E_ARG, "boot_cov: need 1 <= n < 2^31");
+  if (ldx < h->d) return abi_fail(h, MIDAGMA_E_ARG, "boot_cov: ldx < d");
   if (first < 0 || first > (int64_t(1) << 32) - h->B)
-    return batch_fail(h, MIDAGMA_E_ARG, "boot_cov: need 0 <= first and first + B <= 2^32");
-  return batch_guarded(h, [&] { boot_cov(h, X, n, ldx, on_device != 0, seed, first, budget_bytes); });
+    return abi_fail(h, MIDAGMA_E_ARG, "boot_cov: need 0 <= first and first + B <= 2^32");
+  return abi_guarded(h, [&] { boot_cov(h, X, n, ldx, on_device != 0, seed, first, budget_bytes); });
 }
 
 extern "C" int midagma_boot_get_cov(midagma_batch* h, double* out) {
-  if (!h || !out) return batch_fail(h, MIDAGMA_E_ARG, "boot_get_cov: null argument");
-  if (!h->has_cov) return batch_fail(h, MIDAGMA_E_ARG, "boot_get_cov: no cov (set_cov or boot_cov first)");
-  return batch_guarded(h, [&] { h->download_all(h->cov, out); });
+  if (!h || !out) return abi_fail(h, MIDAGMA_E_ARG, "boot_get_cov: null argument");
+  if (!h->has_cov) return abi_fail(h, MIDAGMA_E_ARG, "boot_get_cov: no cov (set_cov or boot_cov first)");
+  return abi_guarded(h, [&] { h->download_all(h->cov, out); });
 }
 
 extern "C" int midagma_boot_profile(const midagma_batch* h, double* ms_out) {
-  if (!h || !ms_out) return batch_fail(nullptr, MIDAGMA_E_ARG, "boot_profile: null argument");
+  if (!h || !ms_out) return abi_fail(no_handle<midagma_batch>, MIDAGMA_E_ARG, "boot_profile: null argument");
   for (int k = 0; k < 4; ++k) ms_out[k] = h->boot_ms[k];
   return MIDAGMA_OK;
 }
@@ -312,8 +312,8 @@ extern "C" int midagma_boot_profile(const midagma_batch* h, double* ms_out) {
 // Test hook (not in the public header): the batch's cov slabs as they lie on the device, B x D x D
 // with D = 64, padding included.
 extern "C" int midagma_debug_batch_cov_slabs(midagma_batch* h, double* out) {
-  if (!h || !out) return batch_fail(h, MIDAGMA_E_ARG, "debug_batch_cov_slabs: null argument");
-  return batch_guarded(h, [&] {
+  if (!h || !out) return abi_fail(h, MIDAGMA_E_ARG, "debug_batch_cov_slabs: null argument");
+  return abi_guarded(h, [&] {
     HIP_TRY(hipMemcpyAsync(out, h->cov.p, (size_t)h->B * h->D * h->D * sizeof(double), hipMemcpyDeviceToHost,
                            h->stream));
     HIP_TRY(hipStreamSynchronize(h->stream));

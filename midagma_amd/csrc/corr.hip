@@ -40,7 +40,6 @@ constexpr int WAVES = NTHREADS / 64;
 constexpr int64_t SEG = 4096;        // keys per wave segment of the radix passes
 constexpr int RADIX = 256, PASSES = 8;
 constexpr int64_t kDefaultBudget = int64_t(2) << 30;
-constexpr const char* kNonFiniteX = "array must not contain infs or NaNs";
 
 __device__ inline uint64_t key_of(double v) {
   uint64_t b = (uint64_t)__double_as_longlong(v);
@@ -401,17 +400,6 @@ CorrPlan corr_plan(int64_t n, int64_t d, int64_t budget) {
 
 unsigned row_blocks(int64_t rows) { return (unsigned)std::max<int64_t>(1, std::min<int64_t>(rows, 4096)); }
 
-template <class F>
-int corr_guarded(F&& f) {
-  try {
-    return f();
-  } catch (...) {
-    std::string msg;
-    const int rc = classify(std::current_exception(), msg);
-    return fail_global(rc, msg);
-  }
-}
-
 const char* bad_args(const void* X, int64_t n, int64_t d, int64_t ldx, const void* out, int64_t ldo) {
   if (!X || !out) return "null pointer";
   if (!shape_ok(n, d)) return "need 2 <= n < 2^31 rows and 1 <= d <= 65535 columns";
@@ -446,9 +434,17 @@ void launch_segsort_payload(const SegSort& s, int64_t n, int64_t nseg, int32_t* 
   HIP_TRY(hipGetLastError());
 }
 
-// midagma_colrank's chunk loop up to the sorted columns, then the payloads instead of the ranks
-void colargsort_run(const double* X_dev, int64_t n, int64_t d, int64_t ldx, int32_t* order_dev, int64_t budget_bytes,
-                    hipStream_t st) {
+}  // namespace midagma
+
+namespace {
+
+// The columns of X sorted by value, a chunk of the plan's columns at a time: the scratch, the keys
+// kernel and the radix passes of each chunk, then after(s, c0, nc, tiles) on the chunk's sorted keys
+// and payloads.  Synchronises st (the scratch is freed on return); inf or nan in X throws, with
+// `who` in front of the message.
+template <class After>
+void sorted_columns(const double* X_dev, int64_t n, int64_t d, int64_t ldx, int64_t budget_bytes, hipStream_t st,
+                    const char* who, After&& after) {
   const RankPlan p = rank_plan(n, d, budget_bytes);
   DevBuf<uint64_t> keys;
   DevBuf<uint32_t> idx, hist;
@@ -459,7 +455,7 @@ void colargsort_run(const double* X_dev, int64_t n, int64_t d, int64_t ldx, int3
   hist.alloc((size_t)p.hist_count);
   oa.alloc((size_t)(2 * p.cols));
   fl.alloc(1);
-  HIP_TRY(hipMemsetAsync(fl.p, 0, sizeof(int), st));
+  flag_clear(fl.p, st);
   const int64_t half = p.cols * n;
   const SegSort s{keys.p, keys.p + half, idx.p, idx.p + half, oa.p, oa.p + p.cols, hist.p};
   for (int64_t c0 = 0; c0 < d; c0 += p.cols) {
@@ -471,21 +467,26 @@ void colargsort_run(const double* X_dev, int64_t n, int64_t d, int64_t ldx, int3
                        s.key_and, fl.p);
     HIP_TRY(hipGetLastError());
     launch_segsort(s, n, nc, st);
-    launch_segsort_payload(s, n, nc, order_dev + c0 * n, nullptr, st);
+    after(s, c0, nc, tiles);
   }
-  int bad = 0;
-  HIP_TRY(hipMemcpyAsync(&bad, fl.p, sizeof(int), hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipStreamSynchronize(st));  // (the scratch is freed on return)
-  if (bad) throw std::invalid_argument(std::string("colargsort: ") + kNonFiniteX);
+  flag_check(fl.p, st, std::string(who) + kNonFinite);
 }
 
-}  // namespace midagma
+}  // namespace
+
+void midagma::colargsort_run(const double* X_dev, int64_t n, int64_t d, int64_t ldx, int32_t* order_dev,
+                             int64_t budget_bytes, hipStream_t st) {
+  sorted_columns(X_dev, n, d, ldx, budget_bytes, st, "colargsort: ",
+                 [&](const SegSort& s, int64_t c0, int64_t nc, dim3) {
+                   launch_segsort_payload(s, n, nc, order_dev + c0 * n, nullptr, st);
+                 });
+}
 
 extern "C" int midagma_colargsort(const double* X_dev, int64_t n, int64_t d, int64_t ldx, int32_t* order_dev,
                                   int64_t budget_bytes, void* stream) {
   if (const char* why = bad_args(X_dev, n, d, ldx, order_dev, d))
-    return fail_global(MIDAGMA_E_ARG, std::string("colargsort: ") + why);
-  return corr_guarded([&] {
+    return abi_fail(nullptr, MIDAGMA_E_ARG, std::string("colargsort: ") + why);
+  return abi_guarded(nullptr, [&] {
     colargsort_run(X_dev, n, d, ldx, order_dev, budget_bytes, reinterpret_cast<hipStream_t>(stream));
     return MIDAGMA_OK;
   });
@@ -499,53 +500,26 @@ extern "C" int64_t midagma_corr_workspace(int64_t n, int64_t d, int64_t budget_b
 extern "C" int midagma_colrank(const double* X_dev, int64_t n, int64_t d, int64_t ldx, double* R_dev, int64_t ldr,
                                int64_t budget_bytes, void* stream) {
   if (const char* why = bad_args(X_dev, n, d, ldx, R_dev, ldr))
-    return fail_global(MIDAGMA_E_ARG, std::string("colrank: ") + why);
-  return corr_guarded([&] {
+    return abi_fail(nullptr, MIDAGMA_E_ARG, std::string("colrank: ") + why);
+  return abi_guarded(nullptr, [&] {
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    const RankPlan p = rank_plan(n, d, budget_bytes);
-    DevBuf<uint64_t> keys;
-    DevBuf<uint32_t> idx, hist;
-    DevBuf<unsigned long long> oa;
-    DevBuf<int> fl;
-    keys.alloc((size_t)p.key_count);
-    idx.alloc((size_t)p.idx_count);
-    hist.alloc((size_t)p.hist_count);
-    oa.alloc((size_t)(2 * p.cols));
-    fl.alloc(1);
-    HIP_TRY(hipMemsetAsync(fl.p, 0, sizeof(int), st));
-    const int64_t half = p.cols * n;
-    uint64_t *K0 = keys.p, *K1 = keys.p + half;
-    uint32_t *I0 = idx.p, *I1 = idx.p + half;
-    unsigned long long *kor = oa.p, *kand = oa.p + p.cols;
-    for (int64_t c0 = 0; c0 < d; c0 += p.cols) {
-      const int64_t nc = std::min(p.cols, d - c0);
-      HIP_TRY(hipMemsetAsync(kor, 0, (size_t)nc * 8, st));
-      HIP_TRY(hipMemsetAsync(kand, 0xff, (size_t)nc * 8, st));
-      const dim3 tiles((unsigned)((n + RT - 1) / RT), (unsigned)((nc + RT - 1) / RT));
-      hipLaunchKernelGGL(corr_keys_kernel, tiles, dim3(NTHREADS), 0, st, X_dev, n, ldx, c0, nc, K0, I0, kor, kand,
-                         fl.p);
-      HIP_TRY(hipGetLastError());
-      launch_segsort(SegSort{K0, K1, I0, I1, kor, kand, hist.p}, n, nc, st);
+    const auto ranks_out = [&](const SegSort& s, int64_t c0, int64_t nc, dim3 tiles) {
       hipLaunchKernelGGL(corr_tie_kernel, dim3((unsigned)((n + NTHREADS - 1) / NTHREADS), (unsigned)nc),
-                         dim3(NTHREADS), 0, st, K0, K1, I0, I1, n, kor, kand);
-      hipLaunchKernelGGL(corr_ranks_out_kernel, tiles, dim3(NTHREADS), 0, st, K0, K1, n, c0, nc, kor, kand, R_dev,
-                         ldr);
+                         dim3(NTHREADS), 0, st, s.K0, s.K1, s.I0, s.I1, n, s.key_or, s.key_and);
+      hipLaunchKernelGGL(corr_ranks_out_kernel, tiles, dim3(NTHREADS), 0, st, s.K0, s.K1, n, c0, nc, s.key_or,
+                         s.key_and, R_dev, ldr);
       HIP_TRY(hipGetLastError());
-    }
-    int bad = 0;
-    HIP_TRY(hipMemcpyAsync(&bad, fl.p, sizeof(int), hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));  // (the scratch is freed on return)
-    if (bad) throw std::invalid_argument(std::string("colrank: ") + kNonFiniteX);
-    return MIDAGMA_OK;
+    };
+    sorted_columns(X_dev, n, d, ldx, budget_bytes, st, "colrank: ", ranks_out);
   });
 }
 
 extern "C" int midagma_corr(const double* X_dev, int64_t n, int64_t d, int64_t ldx, double* Rho_dev, int64_t ldrho,
                             int32_t* const_col_dev, int64_t budget_bytes, void* stream) {
   if (const char* why = bad_args(X_dev, n, d, ldx, Rho_dev, ldrho))
-    return fail_global(MIDAGMA_E_ARG, std::string("corr: ") + why);
-  if (!const_col_dev) return fail_global(MIDAGMA_E_ARG, "corr: null pointer");
-  return corr_guarded([&] {
+    return abi_fail(nullptr, MIDAGMA_E_ARG, std::string("corr: ") + why);
+  if (!const_col_dev) return abi_fail(nullptr, MIDAGMA_E_ARG, "corr: null pointer");
+  return abi_guarded(nullptr, [&] {
     setup_attributes();
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     const CorrPlan p = corr_plan(n, d, budget_bytes);
@@ -555,7 +529,7 @@ extern "C" int midagma_corr(const double* X_dev, int64_t n, int64_t d, int64_t l
     part.alloc((size_t)(3 * p.parts * d));
     stat.alloc((size_t)(3 * d));
     fl.alloc(1);
-    HIP_TRY(hipMemsetAsync(fl.p, 0, sizeof(int), st));
+    flag_clear(fl.p, st);
     // the column pass, in launch_colsum's partition of the rows
     const int64_t groups = p.parts / WAVES;
     const int64_t rows_per = std::max<int64_t>(1, (n + groups - 1) / groups);
@@ -566,10 +540,7 @@ extern "C" int midagma_corr(const double* X_dev, int64_t n, int64_t d, int64_t l
     hipLaunchKernelGGL(corr_colstat_final_kernel, dim3((unsigned)((d + NTHREADS - 1) / NTHREADS)), dim3(NTHREADS), 0,
                        st, psum, pmin, pmax, used * WAVES, d, stat.p);
     HIP_TRY(hipGetLastError());
-    int bad = 0;
-    HIP_TRY(hipMemcpyAsync(&bad, fl.p, sizeof(int), hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    if (bad) throw std::invalid_argument(std::string("corr: ") + kNonFiniteX);
+    flag_check(fl.p, st, std::string("corr: ") + kNonFinite);
     // the Gram of the centred columns: midagma_gram's chunk loop on a centred staging copy
     S.alloc((size_t)(p.g.chunk * D));
     Z.alloc((size_t)((p.g.split + 2) * DD));  // [0] the running sum, [1..split] a chunk's slices, [split+1] the new sum

@@ -471,8 +471,6 @@ __global__ __launch_bounds__(DT) void dcor_value_kernel(const double* __restrict
   }
 }
 
-thread_local std::string g_derr;  // errors raised without a handle
-
 constexpr int64_t kMaxD = 65535, kMaxP = 65535, kMaxChunk = 16383;  // (4 tables an evaluation in a grid dimension of 65535)
 constexpr int64_t kMaxN = (int64_t(1) << 31) - 1;
 constexpr int64_t kDefaultBudget = int64_t(2) << 30;
@@ -501,24 +499,13 @@ struct midagma_dcor {
   PinBuf<double> hvals;
 };
 
+// abi.h's hook: an entry's device work runs on the handle's device once a set_data* has opened it
+// (before that the handle's index may name no device, and no entry has device work)
+static void abi_select_device(const midagma_dcor* h) {
+  if (h->comp) HIP_TRY(hipSetDevice(h->device));
+}
+
 namespace {
-
-int dfail(midagma_dcor* h, int code, const std::string& msg) {
-  (h ? h->err : g_derr) = msg;
-  return code;
-}
-
-template <class F>
-int dguarded(midagma_dcor* h, F&& f) {
-  try {
-    f();
-    return MIDAGMA_OK;
-  } catch (...) {
-    std::string msg;
-    const int rc = classify(std::current_exception(), msg);
-    return dfail(h, rc, msg);
-  }
-}
 
 // the block edge of n: the power of two in [64, 1024] with m^2 >= n, or 1024
 int block_edge(int64_t n) {
@@ -612,17 +599,15 @@ void device_perms(midagma_dcor* h, uint64_t seed, int64_t f0, int64_t nf, int64_
   launch_segsort_payload(s, n, nf, h->perm.p, h->inv.p, h->comp);
 }
 
-void open_device(midagma_dcor* h) {
-  int count = 0;
-  HIP_TRY(hipGetDeviceCount(&count));
-  if (h->device >= count) throw std::invalid_argument("no such device");
-  HIP_TRY(hipSetDevice(h->device));
+// the first set_data* opens the handle's device and makes its stream
+void open_handle(midagma_dcor* h) {
+  open_device(h->device, "");
   if (!h->comp) HIP_TRY(hipStreamCreateWithFlags(&h->comp, hipStreamNonBlocking));
 }
 
 }  // namespace
 
-extern "C" const char* midagma_dcor_last_error(const midagma_dcor* h) { return (h ? h->err : g_derr).c_str(); }
+extern "C" const char* midagma_dcor_last_error(const midagma_dcor* h) { return abi_last_error(h); }
 
 extern "C" void midagma_dcor_destroy(midagma_dcor* h) {
   if (!h) return;
@@ -637,18 +622,18 @@ extern "C" void midagma_dcor_destroy(midagma_dcor* h) {
 // (no device call: the device is opened by the first set_data*, so the argument checks of every
 // entry can be exercised on a machine without one)
 extern "C" int midagma_dcor_create(midagma_dcor** out, int device) {
-  if (!out || device < 0) return dfail(nullptr, MIDAGMA_E_ARG, "dcor_create: bad arguments");
+  if (!out || device < 0) return abi_fail(no_handle<midagma_dcor>, MIDAGMA_E_ARG, "dcor_create: bad arguments");
   *out = new midagma_dcor;
   (*out)->device = device;
   return MIDAGMA_OK;
 }
 
 extern "C" int midagma_dcor_set_data(midagma_dcor* h, const double* X, int64_t n, int64_t d, int64_t budget_bytes) {
-  if (!h) return dfail(nullptr, MIDAGMA_E_ARG, "dcor_set_data: null handle");
-  if (const char* why = bad_shape(X, n, d, d)) return dfail(h, MIDAGMA_E_ARG, std::string("dcor_set_data: ") + why);
+  if (!h) return abi_fail(no_handle<midagma_dcor>, MIDAGMA_E_ARG, "dcor_set_data: null handle");
+  if (const char* why = bad_shape(X, n, d, d)) return abi_fail(h, MIDAGMA_E_ARG, std::string("dcor_set_data: ") + why);
   h->n = h->d = 0;
-  return dguarded(h, [&] {
-    open_device(h);
+  return abi_guarded(h, [&] {
+    open_handle(h);
     HIP_TRY(hipStreamSynchronize(h->comp));
     DevBuf<double> Xd;
     Xd.alloc((size_t)n * d);
@@ -659,18 +644,13 @@ extern "C" int midagma_dcor_set_data(midagma_dcor* h, const double* X, int64_t n
 
 extern "C" int midagma_dcor_set_data_dev(midagma_dcor* h, const double* X_dev, int64_t n, int64_t d, int64_t ld,
                                          int64_t budget_bytes, void* hip_stream) {
-  if (!h) return dfail(nullptr, MIDAGMA_E_ARG, "dcor_set_data_dev: null handle");
+  if (!h) return abi_fail(no_handle<midagma_dcor>, MIDAGMA_E_ARG, "dcor_set_data_dev: null handle");
   if (const char* why = bad_shape(X_dev, n, d, ld))
-    return dfail(h, MIDAGMA_E_ARG, std::string("dcor_set_data_dev: ") + why);
+    return abi_fail(h, MIDAGMA_E_ARG, std::string("dcor_set_data_dev: ") + why);
   h->n = h->d = 0;  // the handle holds no data until the new one is checked
-  return dguarded(h, [&] {
-    open_device(h);
-    hipPointerAttribute_t attr;
-    if (hipPointerGetAttributes(&attr, X_dev) != hipSuccess || attr.type != hipMemoryTypeDevice ||
-        attr.device != h->device) {
-      (void)hipGetLastError();
-      throw std::invalid_argument("dcor_set_data_dev: X is not memory of the handle's device");
-    }
+  return abi_guarded(h, [&] {
+    open_handle(h);
+    require_device_memory(X_dev, h->device, "dcor_set_data_dev");
     HIP_TRY(hipStreamSynchronize(h->comp));  // nothing of an earlier run still reads the columns' arrays
     // on the caller's stream, behind X's producer; prepare's synchronise (the marks are read on the
     // host) also orders the arrays before everything the handle's own stream runs later
@@ -697,9 +677,9 @@ const char* bad_run(const midagma_dcor* h, const int64_t* pairs, int64_t m, int6
 extern "C" int midagma_dcor_run(midagma_dcor* h, const int64_t* pairs, int64_t m, int64_t P, const int32_t* perms,
                                 uint64_t seed, int unbiased, int block, int64_t budget_bytes, double* stat,
                                 int64_t* ge, double* null_out) {
-  if (!h) return dfail(nullptr, MIDAGMA_E_ARG, "dcor_run: null handle");
+  if (!h) return abi_fail(no_handle<midagma_dcor>, MIDAGMA_E_ARG, "dcor_run: null handle");
   if (const char* why = bad_run(h, pairs, m, P, unbiased, block, stat, ge))
-    return dfail(h, MIDAGMA_E_ARG, std::string("dcor_run: ") + why);
+    return abi_fail(h, MIDAGMA_E_ARG, std::string("dcor_run: ") + why);
   const int64_t n = h->n;
   if (perms) {  // every index is read as an address offset on the device, and the inverse needs a bijection
     std::vector<uint8_t> seen((size_t)n);
@@ -707,8 +687,8 @@ extern "C" int midagma_dcor_run(midagma_dcor* h, const int64_t* pairs, int64_t m
       std::fill(seen.begin(), seen.end(), 0);
       const int32_t* row = perms + f * n;
       for (int64_t a = 0; a < n; ++a) {
-        if (row[a] < 0 || row[a] >= n) return dfail(h, MIDAGMA_E_ARG, "dcor_run: permutation index outside [0, n)");
-        if (seen[row[a]]) return dfail(h, MIDAGMA_E_ARG, "dcor_run: a row of perms is not a permutation");
+        if (row[a] < 0 || row[a] >= n) return abi_fail(h, MIDAGMA_E_ARG, "dcor_run: permutation index outside [0, n)");
+        if (seen[row[a]]) return abi_fail(h, MIDAGMA_E_ARG, "dcor_run: a row of perms is not a permutation");
         seen[row[a]] = 1;
       }
     }
@@ -720,8 +700,7 @@ extern "C" int midagma_dcor_run(midagma_dcor* h, const int64_t* pairs, int64_t m
   const int threads = std::min(DT, (pl.m + 63) / 64 * 64);
   const int ne_thr = (pl.m + threads - 1) / threads;  // 1 .. 4
 
-  const int rc = dguarded(h, [&] {
-    HIP_TRY(hipSetDevice(h->device));
+  const int rc = abi_guarded(h, [&] {
     h->dpairs.alloc((size_t)(2 * m));
     HIP_TRY(hipMemcpyAsync(h->dpairs.p, pairs, 2 * m * sizeof(int64_t), hipMemcpyHostToDevice, h->comp));
     double obs = 0.0;  // the observed value of the pair whose permutations are being counted
@@ -783,13 +762,12 @@ extern "C" int midagma_dcor_run(midagma_dcor* h, const int64_t* pairs, int64_t m
 
 extern "C" int midagma_dcor_perms(midagma_dcor* h, int64_t q, int64_t P, uint64_t seed, int32_t* perms_out,
                                   int32_t* inverse_out) {
-  if (!h) return dfail(nullptr, MIDAGMA_E_ARG, "dcor_perms: null handle");
-  if (h->n == 0) return dfail(h, MIDAGMA_E_ARG, "dcor_perms: set the data first");
+  if (!h) return abi_fail(no_handle<midagma_dcor>, MIDAGMA_E_ARG, "dcor_perms: null handle");
+  if (h->n == 0) return abi_fail(h, MIDAGMA_E_ARG, "dcor_perms: set the data first");
   if (q < 0 || q > 0xffffffffll || P < 1 || P > kMaxP || !perms_out)
-    return dfail(h, MIDAGMA_E_ARG, "dcor_perms: need 0 <= q < 2^32, 1 <= P <= 65535 and an output");
+    return abi_fail(h, MIDAGMA_E_ARG, "dcor_perms: need 0 <= q < 2^32, 1 <= P <= 65535 and an output");
   const int64_t n = h->n;
-  return dguarded(h, [&] {
-    HIP_TRY(hipSetDevice(h->device));
+  return abi_guarded(h, [&] {
     for (int64_t p = 0; p < P; ++p) {  // (one at a time: the scratch of one evaluation)
       h->perm.alloc((size_t)n), h->inv.alloc((size_t)n);
       device_perms(h, seed, q * P + p, 1, P);

@@ -11,6 +11,7 @@
 #include <algorithm>
 #include <cmath>
 
+#include "devmem.h"
 #include "launch.h"
 
 namespace midagma {
@@ -167,3 +168,80 @@ GramPlan gram_plan(int64_t n, int64_t d, int64_t chunk_rows) {
 }
 
 }  // namespace midagma
+
+using namespace midagma;
+
+extern "C" {
+
+// ABI 7: fit()'s data preparation on device memory (linear.py:406-428), csrc/gram.hip.
+int midagma_colsum_dev(const double* X, int64_t n, int64_t d, int64_t ldx, double* out_dev, void* stream) {
+  if (n < 0 || d < 1 || ldx < d || !out_dev || (n > 0 && !X))
+    return abi_fail(nullptr, MIDAGMA_E_ARG, "colsum_dev: bad arguments");
+  return abi_guarded(nullptr, [&] {
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    DevBuf<> part;
+    part.alloc((size_t)colsum_parts(n) * d);
+    launch_colsum(X, n, d, ldx, part.p, out_dev, st);
+    HIP_TRY(hipStreamSynchronize(st));  // the partials are freed on return
+    return MIDAGMA_OK;
+  });
+}
+
+int midagma_center_dev(double* X, int64_t n, int64_t d, int64_t ldx, const double* colsum_dev, double nrows,
+                       void* stream) {
+  if (n < 0 || d < 1 || ldx < d || !colsum_dev || (n > 0 && !X) || !(nrows > 0))
+    return abi_fail(nullptr, MIDAGMA_E_ARG, "center_dev: bad arguments");
+  return abi_guarded(nullptr, [&] {
+    launch_center(X, n, d, ldx, colsum_dev, nrows, reinterpret_cast<hipStream_t>(stream));
+    return MIDAGMA_OK;
+  });
+}
+
+int midagma_gram(const double* X, int64_t n, int64_t d, int64_t ldx, int on_device, double* G_dev, int64_t ldg,
+                 void* stream) {
+  if (n < 0 || d < 1 || ldx < d || !G_dev || ldg < d || (n > 0 && !X))
+    return abi_fail(nullptr, MIDAGMA_E_ARG, "gram: bad arguments");
+  return abi_guarded(nullptr, [&] {
+    setup_attributes();
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    static const int64_t chunk_rows = [] {
+      const char* e = getenv("MIDAGMA_GRAM_CHUNK_ROWS");
+      return e ? std::max<int64_t>(256, atoll(e)) : int64_t(262144);
+    }();
+    const GramPlan p = gram_plan(n, d, chunk_rows);
+    const int64_t D = p.D, DD = D * D;
+    DevBuf<> S, Z, fl;
+    S.alloc((size_t)p.chunk * D);
+    Z.alloc((size_t)(p.split + 2) * DD);  // [0] the running sum, [1..split] a chunk's slices, [split+1] the new sum
+    fl.alloc(1);
+    int* flag = reinterpret_cast<int*>(fl.p);
+    HIP_TRY(hipMemsetAsync(flag, 0, sizeof(int), st));
+    HIP_TRY(hipMemsetAsync(Z.p, 0, DD * sizeof(double), st));
+    if (!on_device) HIP_TRY(hipMemsetAsync(S.p, 0, (size_t)p.chunk * D * sizeof(double), st));
+    for (int64_t c = 0; c < p.nchunks; ++c) {
+      const int64_t r0 = c * p.chunk, rows = std::min(p.chunk, n - r0);
+      const int64_t rpad = (rows + 255) / 256 * 256;
+      if (on_device) {
+        launch_stage_rows(X + r0 * ldx, ldx, rows, d, S.p, D, rpad, flag, st);
+      } else {
+        if (rows < rpad) HIP_TRY(hipMemsetAsync(S.p + rows * D, 0, (rpad - rows) * D * sizeof(double), st));
+        HIP_TRY(hipMemcpy2DAsync(S.p, D * sizeof(double), X + r0 * ldx, ldx * sizeof(double), d * sizeof(double),
+                                 rows, hipMemcpyHostToDevice, st));
+        launch_nonfinite_or(S.p, rows, d, D, flag, st);
+      }
+      // (the running sum is slice 0 of the sum, so the slices are summed at every split)
+      launch_gemm(GemmSpec{D, D, rpad, S.p, D, true, S.p, D, B_PLAIN, Z.p + DD, D, p.split, DD}, nullptr, st);
+      launch_sum_slices(Z.p, p.split + 1, DD, DD, Z.p + (p.split + 1) * DD, nullptr, st);
+      HIP_TRY(hipMemcpyAsync(Z.p, Z.p + (p.split + 1) * DD, DD * sizeof(double), hipMemcpyDeviceToDevice, st));
+    }
+    HIP_TRY(hipMemcpy2DAsync(G_dev, ldg * sizeof(double), Z.p, D * sizeof(double), d * sizeof(double), d,
+                             hipMemcpyDeviceToDevice, st));
+    int bad = 0;
+    HIP_TRY(hipMemcpyAsync(&bad, flag, sizeof(int), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if (bad) throw std::invalid_argument(std::string("gram: ") + kNonFinite);
+    return MIDAGMA_OK;
+  });
+}
+
+}  // extern "C"

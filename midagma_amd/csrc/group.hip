@@ -228,25 +228,10 @@ void group_clear_handback(midagma_group* g) {
 
 }  // namespace midagma
 
+// abi.h's hook: a group entry's own device work runs on its first member's device
+static void abi_select_device(const midagma_group* g) { HIP_TRY(hipSetDevice(g->devices[0])); }
+
 namespace {
-thread_local std::string g_group_error;
-
-int gfail(midagma_group* g, int code, const std::string& msg) {
-  (g ? g->err : g_group_error) = msg;
-  return code;
-}
-
-template <class F>
-int gguard(midagma_group* g, F&& f) {
-  try {
-    HIP_TRY(hipSetDevice(g->devices[0]));
-    return f();
-  } catch (...) {
-    std::string msg;
-    const int rc = classify(std::current_exception(), msg);
-    return gfail(g, rc, msg);
-  }
-}
 
 bool same_result(const midagma_result& a, const midagma_result& b) {
   return a.iters == b.iters && a.status == b.status && a.halvings == b.halvings && a.slots == b.slots &&
@@ -259,24 +244,28 @@ extern "C" {
 int midagma_group_create(midagma_group** out, int loss, int64_t d, const int* devices, int ndev, int flags) {
   if (!out || !devices || ndev < 1 || d < 1 || (loss != MIDAGMA_LOSS_L2 && loss != MIDAGMA_LOSS_LOGISTIC) ||
       (flags & ~MIDAGMA_GROUP_EMULATE))
-    return gfail(nullptr, MIDAGMA_E_ARG, "group_create: bad arguments");
+    return abi_fail(no_handle<midagma_group>, MIDAGMA_E_ARG, "group_create: bad arguments");
   const bool emulate = (flags & MIDAGMA_GROUP_EMULATE) != 0;
   int count = 0;
-  if (hipGetDeviceCount(&count) != hipSuccess) return gfail(nullptr, MIDAGMA_E_HIP, "group_create: no HIP device");
+  if (hipGetDeviceCount(&count) != hipSuccess)
+    return abi_fail(no_handle<midagma_group>, MIDAGMA_E_HIP, "group_create: no HIP device");
   for (int k = 0; k < ndev; ++k) {
     if (devices[k] < 0 || devices[k] >= count)
-      return gfail(nullptr, MIDAGMA_E_ARG, "group_create: device " + std::to_string(devices[k]) + " out of range");
+      return abi_fail(no_handle<midagma_group>, MIDAGMA_E_ARG,
+                      "group_create: device " + std::to_string(devices[k]) + " out of range");
     for (int j = 0; j < k; ++j) {
       if (!emulate && devices[j] == devices[k])
-        return gfail(nullptr, MIDAGMA_E_ARG,
+        return abi_fail(no_handle<midagma_group>, MIDAGMA_E_ARG,
                      "group_create: a device appears twice (one RCCL rank per device; MIDAGMA_GROUP_EMULATE "
                      "puts every member on one device)");
     }
     if (emulate && devices[k] != devices[0])
-      return gfail(nullptr, MIDAGMA_E_ARG, "group_create: an emulated group keeps every member on one device");
+      return abi_fail(no_handle<midagma_group>, MIDAGMA_E_ARG,
+                      "group_create: an emulated group keeps every member on one device");
   }
   if (emulate && ndev > kMaxEmulated)
-    return gfail(nullptr, MIDAGMA_E_ARG, "group_create: an emulated group holds at most 16 members");
+    return abi_fail(no_handle<midagma_group>, MIDAGMA_E_ARG,
+                    "group_create: an emulated group holds at most 16 members");
   midagma_group* g = new midagma_group();
   g->emulated = emulate;
   g->loss = loss;
@@ -288,11 +277,11 @@ int midagma_group_create(midagma_group** out, int loss, int64_t d, const int* de
     if (rc != MIDAGMA_OK) {
       const std::string why = std::string("group_create: member ") + std::to_string(k) + ": " + midagma_last_error(nullptr);
       delete g;
-      return gfail(nullptr, rc, why);
+      return abi_fail(no_handle<midagma_group>, rc, why);
     }
     g->m.push_back(s);
   }
-  const int rc = gguard(g, [&] {
+  const int rc = abi_guarded(g, [&] {
     if (emulate) {
       for (midagma_solver* s : g->m) s->group = g;
     } else {
@@ -313,7 +302,7 @@ int midagma_group_create(midagma_group** out, int loss, int64_t d, const int* de
   if (rc != MIDAGMA_OK) {
     const std::string why = g->err;
     delete g;
-    return gfail(nullptr, rc, why);
+    return abi_fail(no_handle<midagma_group>, rc, why);
   }
   *out = g;
   return MIDAGMA_OK;
@@ -321,7 +310,7 @@ int midagma_group_create(midagma_group** out, int loss, int64_t d, const int* de
 
 void midagma_group_destroy(midagma_group* g) { delete g; }
 
-const char* midagma_group_last_error(const midagma_group* g) { return g ? g->err.c_str() : g_group_error.c_str(); }
+const char* midagma_group_last_error(const midagma_group* g) { return abi_last_error(g); }
 
 int midagma_group_size(const midagma_group* g) { return g ? (int)g->m.size() : 0; }
 
@@ -332,23 +321,24 @@ midagma_solver* midagma_group_member(midagma_group* g, int k) {
 }
 
 int midagma_group_set_data(midagma_group* g, const double* X, int64_t n) {
-  if (!g || !X) return gfail(g, MIDAGMA_E_ARG, "group_set_data: null argument");
+  if (!g || !X) return abi_fail(g, MIDAGMA_E_ARG, "group_set_data: null argument");
   const int64_t N = (int64_t)g->m.size();
-  if (n < N) return gfail(g, MIDAGMA_E_ARG, "group_set_data: fewer rows than members");
+  if (n < N) return abi_fail(g, MIDAGMA_E_ARG, "group_set_data: fewer rows than members");
   const int64_t base = n / N, extra = n % N;
   for (int64_t k = 0; k < N; ++k) {
     const int64_t lo = k * base + std::min(k, extra), rows = base + (k < extra ? 1 : 0);
     const int rc = midagma_set_data(g->m[(size_t)k], X + lo * g->d, rows, n, 0);
     if (rc != MIDAGMA_OK)
-      return gfail(g, rc, "group_set_data: member " + std::to_string(k) + ": " + midagma_last_error(g->m[(size_t)k]));
+      return abi_fail(g, rc,
+                      "group_set_data: member " + std::to_string(k) + ": " + midagma_last_error(g->m[(size_t)k]));
   }
   return MIDAGMA_OK;
 }
 
 int midagma_group_allreduce_zbuf(midagma_group* g) {
-  if (!g) return gfail(g, MIDAGMA_E_ARG, "group_allreduce_zbuf: null group");
+  if (!g) return abi_fail(g, MIDAGMA_E_ARG, "group_allreduce_zbuf: null group");
   if (g->emulated) {
-    return gguard(g, [&] {
+    return abi_guarded(g, [&] {
       for (midagma_solver* s : g->m) HIP_TRY(hipStreamSynchronize(s->stream));
       g->enqueue_emulated_allreduce();
       HIP_TRY(hipStreamSynchronize(g->s0()));
@@ -365,15 +355,15 @@ int midagma_group_allreduce_zbuf(midagma_group* g) {
 int midagma_group_minimize(midagma_group* g, double* W, double mu, int64_t max_iter, double s_dom, double lr,
                            double tol, double beta1, double beta2, double lambda1, int64_t checkpoint,
                            midagma_result* res) {
-  if (!g || !W) return gfail(g, MIDAGMA_E_ARG, "group_minimize: null argument");
+  if (!g || !W) return abi_fail(g, MIDAGMA_E_ARG, "group_minimize: null argument");
   const int64_t d = g->d, N = (int64_t)g->m.size();
-  if (!all_finite_w(W, d * d)) return gfail(g, MIDAGMA_E_ARG, "group_minimize: array must not contain infs or NaNs");
+  if (!all_finite_w(W, d * d)) return abi_fail(g, MIDAGMA_E_ARG, "group_minimize: array must not contain infs or NaNs");
   std::vector<std::vector<double>> Wk((size_t)N, std::vector<double>((size_t)(d * d)));
   std::vector<midagma_result> rk((size_t)N);
   for (auto& w : Wk) std::memcpy(w.data(), W, (size_t)(d * d) * sizeof(double));
   int rc;
   if (g->emulated) {
-    rc = gguard(g, [&] {
+    rc = abi_guarded(g, [&] {
       for (midagma_solver* s : g->m) s->begin(W, mu, max_iter, s_dom, lr, tol, beta1, beta2, lambda1, checkpoint);
       gmark("begun");
       // the combined graphs bake every member's buffers and settings in: captured afresh per call
@@ -418,15 +408,15 @@ int midagma_group_minimize(midagma_group* g, double* W, double mu, int64_t max_i
   for (int64_t k = 1; k < N; ++k) {
     if (std::memcmp(Wk[(size_t)k].data(), Wk[0].data(), (size_t)(d * d) * sizeof(double)) != 0 ||
         !same_result(rk[(size_t)k], rk[0]))
-      return gfail(g, MIDAGMA_E_STATE,
+      return abi_fail(g, MIDAGMA_E_STATE,
                    "device group: member " + std::to_string(k) + " ended with a different W or state than member 0 "
                    "(replicas diverged)");
   }
   std::memcpy(W, Wk[0].data(), (size_t)(d * d) * sizeof(double));
   if (res) *res = rk[0];
   if (rk[0].status == MIDAGMA_ST_SINGULAR) {
-    if (!all_finite_w(W, d * d)) return gfail(g, MIDAGMA_E_ARG, "group_minimize: array must not contain infs or NaNs");
-    return gfail(g, MIDAGMA_E_SINGULAR, "singular matrix: inverse of sI - W*W is not finite");
+    if (!all_finite_w(W, d * d)) return abi_fail(g, MIDAGMA_E_ARG, "group_minimize: array must not contain infs or NaNs");
+    return abi_fail(g, MIDAGMA_E_SINGULAR, "singular matrix: inverse of sI - W*W is not finite");
   }
   return MIDAGMA_OK;
 }

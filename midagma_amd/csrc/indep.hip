@@ -433,8 +433,6 @@ __global__ __launch_bounds__(1024) void indep_median_kernel(const double* __rest
   if (tid == 0) med[v] = m > 0.0 ? m : 1.0;
 }
 
-thread_local std::string g_err;  // errors raised without a handle
-
 }  // namespace
 }  // namespace midagma
 
@@ -477,24 +475,10 @@ struct midagma_indep {
   double bw_ms = 0.0;  // the last median_bandwidths' kernel time, ms
 };
 
+// abi.h's hook: an entry's device work runs on the handle's device
+static void abi_select_device(const midagma_indep* h) { HIP_TRY(hipSetDevice(h->device)); }
+
 namespace {
-
-int ifail(midagma_indep* h, int code, const std::string& msg) {
-  (h ? h->err : g_err) = msg;
-  return code;
-}
-
-template <class F>
-int iguarded(midagma_indep* h, F&& f) {
-  try {
-    f();
-    return MIDAGMA_OK;
-  } catch (...) {
-    std::string msg;
-    const int rc = classify(std::current_exception(), msg);
-    return ifail(h, rc, msg);
-  }
-}
 
 int64_t tiles_of(int64_t n) {
   const int64_t nt = (n + IT - 1) / IT;
@@ -542,17 +526,14 @@ void prepare_stats(midagma_indep* h, int kind) {
 
 }  // namespace
 
-extern "C" const char* midagma_indep_last_error(const midagma_indep* h) { return (h ? h->err : g_err).c_str(); }
+extern "C" const char* midagma_indep_last_error(const midagma_indep* h) { return abi_last_error(h); }
 
 extern "C" int midagma_indep_create(midagma_indep** out, int device) {
-  if (!out || device < 0) return ifail(nullptr, MIDAGMA_E_ARG, "indep_create: bad arguments");
+  if (!out || device < 0) return abi_fail(no_handle<midagma_indep>, MIDAGMA_E_ARG, "indep_create: bad arguments");
   *out = nullptr;
   midagma_indep* h = nullptr;
-  const int rc = iguarded(nullptr, [&] {
-    int count = 0;
-    HIP_TRY(hipGetDeviceCount(&count));
-    if (device >= count) throw std::invalid_argument("indep_create: no such device");
-    HIP_TRY(hipSetDevice(device));
+  const int rc = abi_guarded(no_handle<midagma_indep>, [&] {
+    open_device(device, "indep_create: ");
     h = new midagma_indep;
     h->device = device;
     HIP_TRY(hipStreamCreateWithFlags(&h->comp, hipStreamNonBlocking));
@@ -583,20 +564,19 @@ extern "C" void midagma_indep_destroy(midagma_indep* h) {
 }
 
 extern "C" int midagma_indep_set_data(midagma_indep* h, const double* X, int64_t n, int64_t d) {
-  if (!h) return ifail(nullptr, MIDAGMA_E_ARG, "indep_set_data: null handle");
+  if (!h) return abi_fail(no_handle<midagma_indep>, MIDAGMA_E_ARG, "indep_set_data: null handle");
   if (!X || n < 2 || n > kMaxN || d < 1 || d > kMaxD)
-    return ifail(h, MIDAGMA_E_ARG, "indep_set_data: need X, 2 <= n <= 16384 and 1 <= d <= 65535");
+    return abi_fail(h, MIDAGMA_E_ARG, "indep_set_data: need X, 2 <= n <= 16384 and 1 <= d <= 65535");
   std::vector<double> xt(static_cast<size_t>(n) * d);
   std::vector<uint8_t> constant(d, 1);
   for (int64_t a = 0; a < n; ++a)
     for (int64_t v = 0; v < d; ++v) {
       const double val = X[a * d + v];
-      if (!std::isfinite(val)) return ifail(h, MIDAGMA_E_ARG, "indep_set_data: X holds inf or nan");
+      if (!std::isfinite(val)) return abi_fail(h, MIDAGMA_E_ARG, "indep_set_data: X holds inf or nan");
       xt[v * n + a] = val;
       if (val != X[v]) constant[v] = 0;
     }
-  return iguarded(h, [&] {
-    HIP_TRY(hipSetDevice(h->device));
+  return abi_guarded(h, [&] {
     HIP_TRY(hipStreamSynchronize(h->comp));
     h->XT.alloc(xt.size());
     HIP_TRY(hipMemcpy(h->XT.p, xt.data(), xt.size() * sizeof(double), hipMemcpyHostToDevice));
@@ -609,21 +589,15 @@ extern "C" int midagma_indep_set_data(midagma_indep* h, const double* X, int64_t
 
 extern "C" int midagma_indep_set_data_dev(midagma_indep* h, const double* X_dev, int64_t n, int64_t d, int64_t ld,
                                           void* hip_stream) {
-  if (!h) return ifail(nullptr, MIDAGMA_E_ARG, "indep_set_data_dev: null handle");
+  if (!h) return abi_fail(no_handle<midagma_indep>, MIDAGMA_E_ARG, "indep_set_data_dev: null handle");
   if (!X_dev || n < 2 || n > kMaxN || d < 1 || d > kMaxD || ld < d)
-    return ifail(h, MIDAGMA_E_ARG, "indep_set_data_dev: need X, 2 <= n <= 16384, 1 <= d <= 65535 and ld >= d");
+    return abi_fail(h, MIDAGMA_E_ARG, "indep_set_data_dev: need X, 2 <= n <= 16384, 1 <= d <= 65535 and ld >= d");
   hipStream_t s = static_cast<hipStream_t>(hip_stream);
   std::vector<uint8_t> flags(2 * d);
   h->n = h->d = 0;  // the handle holds no data until the new one is checked
   h->have_bw = h->have_stats[0] = h->have_stats[1] = false;
-  const int rc = iguarded(h, [&] {
-    HIP_TRY(hipSetDevice(h->device));
-    hipPointerAttribute_t attr;
-    if (hipPointerGetAttributes(&attr, X_dev) != hipSuccess || attr.type != hipMemoryTypeDevice ||
-        attr.device != h->device) {
-      (void)hipGetLastError();
-      throw std::invalid_argument("indep_set_data_dev: X is not memory of the handle's device");
-    }
+  const int rc = abi_guarded(h, [&] {
+    require_device_memory(X_dev, h->device, "indep_set_data_dev");
     HIP_TRY(hipStreamSynchronize(h->comp));  // nothing of an earlier run still reads XT
     const int chunks = static_cast<int>((n + TCHUNK - 1) / TCHUNK);
     h->XT.alloc(static_cast<size_t>(n) * d);
@@ -641,7 +615,7 @@ extern "C" int midagma_indep_set_data_dev(midagma_indep* h, const double* X_dev,
   });
   if (rc != MIDAGMA_OK) return rc;
   for (int64_t v = 0; v < d; ++v)
-    if (flags[v]) return ifail(h, MIDAGMA_E_ARG, "indep_set_data_dev: X holds inf or nan");
+    if (flags[v]) return abi_fail(h, MIDAGMA_E_ARG, "indep_set_data_dev: X holds inf or nan");
   h->constant.assign(d, 0);
   for (int64_t v = 0; v < d; ++v) h->constant[v] = flags[d + v] ? 0 : 1;
   h->n = n;
@@ -657,11 +631,10 @@ int install_bandwidths(midagma_indep* h, const double* sigma2, const char* who) 
   std::vector<double> c(d);
   for (int64_t v = 0; v < d; ++v) {
     if (!(sigma2[v] > 0.0) || !std::isfinite(sigma2[v]))
-      return ifail(h, MIDAGMA_E_ARG, std::string(who) + ": squared bandwidths must be finite and > 0");
+      return abi_fail(h, MIDAGMA_E_ARG, std::string(who) + ": squared bandwidths must be finite and > 0");
     c[v] = 1.0 / (2.0 * sigma2[v]);
   }
-  return iguarded(h, [&] {
-    HIP_TRY(hipSetDevice(h->device));
+  return abi_guarded(h, [&] {
     HIP_TRY(hipStreamSynchronize(h->comp));
     h->c.alloc(d);
     HIP_TRY(hipMemcpy(h->c.p, c.data(), d * sizeof(double), hipMemcpyHostToDevice));
@@ -673,17 +646,17 @@ int install_bandwidths(midagma_indep* h, const double* sigma2, const char* who) 
 }  // namespace
 
 extern "C" int midagma_indep_set_bandwidths(midagma_indep* h, const double* sigma2, int64_t d) {
-  if (!h) return ifail(nullptr, MIDAGMA_E_ARG, "indep_set_bandwidths: null handle");
-  if (h->n == 0) return ifail(h, MIDAGMA_E_ARG, "indep_set_bandwidths: set the data first");
-  if (!sigma2 || d != h->d) return ifail(h, MIDAGMA_E_ARG, "indep_set_bandwidths: need d squared bandwidths");
+  if (!h) return abi_fail(no_handle<midagma_indep>, MIDAGMA_E_ARG, "indep_set_bandwidths: null handle");
+  if (h->n == 0) return abi_fail(h, MIDAGMA_E_ARG, "indep_set_bandwidths: set the data first");
+  if (!sigma2 || d != h->d) return abi_fail(h, MIDAGMA_E_ARG, "indep_set_bandwidths: need d squared bandwidths");
   return install_bandwidths(h, sigma2, "indep_set_bandwidths");
 }
 
 extern "C" int midagma_indep_median_bandwidths(midagma_indep* h, const int64_t* cols, int64_t ncols,
                                                double* sigma2_out) {
-  if (!h) return ifail(nullptr, MIDAGMA_E_ARG, "indep_median_bandwidths: null handle");
-  if (h->n == 0) return ifail(h, MIDAGMA_E_ARG, "indep_median_bandwidths: set the data first");
-  if (cols && ncols < 0) return ifail(h, MIDAGMA_E_ARG, "indep_median_bandwidths: ncols < 0");
+  if (!h) return abi_fail(no_handle<midagma_indep>, MIDAGMA_E_ARG, "indep_median_bandwidths: null handle");
+  if (h->n == 0) return abi_fail(h, MIDAGMA_E_ARG, "indep_median_bandwidths: set the data first");
+  if (cols && ncols < 0) return abi_fail(h, MIDAGMA_E_ARG, "indep_median_bandwidths: ncols < 0");
   const int64_t n = h->n, d = h->d;
   // the listed columns, each once, ascending (a column's value does not depend on the list)
   std::vector<int64_t> list;
@@ -691,7 +664,7 @@ extern "C" int midagma_indep_median_bandwidths(midagma_indep* h, const int64_t* 
     std::vector<uint8_t> mark(d, 0);
     for (int64_t k = 0; k < ncols; ++k) {
       if (cols[k] < 0 || cols[k] >= d)
-        return ifail(h, MIDAGMA_E_ARG, "indep_median_bandwidths: column index outside [0, d)");
+        return abi_fail(h, MIDAGMA_E_ARG, "indep_median_bandwidths: column index outside [0, d)");
       mark[cols[k]] = 1;
     }
     for (int64_t v = 0; v < d; ++v)
@@ -701,8 +674,7 @@ extern "C" int midagma_indep_median_bandwidths(midagma_indep* h, const int64_t* 
   std::vector<double> med(d), s2(d, 1.0);
   h->bw_ms = 0.0;
   if (m > 0) {
-    const int rc = iguarded(h, [&] {
-      HIP_TRY(hipSetDevice(h->device));
+    const int rc = abi_guarded(h, [&] {
       int sz = 2;
       while (sz < n) sz <<= 1;
       const int threads = sz <= 2048 ? 256 : 1024;
@@ -740,7 +712,7 @@ extern "C" int midagma_indep_median_bandwidths(midagma_indep* h, const int64_t* 
 }
 
 extern "C" int midagma_indep_bandwidth_profile(const midagma_indep* h, double* ms_out) {
-  if (!h || !ms_out) return ifail(nullptr, MIDAGMA_E_ARG, "indep_bandwidth_profile: bad arguments");
+  if (!h || !ms_out) return abi_fail(no_handle<midagma_indep>, MIDAGMA_E_ARG, "indep_bandwidth_profile: bad arguments");
   *ms_out = h->bw_ms;
   return MIDAGMA_OK;
 }
@@ -751,7 +723,7 @@ extern "C" int64_t midagma_indep_batch_pairs(const midagma_indep* h, int64_t P, 
 }
 
 extern "C" int midagma_indep_profile(const midagma_indep* h, double* ms_out) {
-  if (!h || !ms_out) return ifail(nullptr, MIDAGMA_E_ARG, "indep_profile: bad arguments");
+  if (!h || !ms_out) return abi_fail(no_handle<midagma_indep>, MIDAGMA_E_ARG, "indep_profile: bad arguments");
   std::copy(h->prof, h->prof + 4, ms_out);
   return MIDAGMA_OK;
 }
@@ -759,22 +731,23 @@ extern "C" int midagma_indep_profile(const midagma_indep* h, double* ms_out) {
 extern "C" int midagma_indep_run(midagma_indep* h, int kind, const int64_t* pairs, int64_t m, int64_t P,
                                  const int32_t* perms, uint64_t seed, int64_t budget_bytes, double* stat, int64_t* ge,
                                  double* null_out, int32_t* perms_out) {
-  if (!h) return ifail(nullptr, MIDAGMA_E_ARG, "indep_run: null handle");
+  if (!h) return abi_fail(no_handle<midagma_indep>, MIDAGMA_E_ARG, "indep_run: null handle");
   if ((kind != KIND_HSIC && kind != KIND_DCOR) || m < 0 || P < 0 || P > kMaxP || (m > 0 && (!pairs || !stat || !ge)))
-    return ifail(h, MIDAGMA_E_ARG, "indep_run: bad arguments (kind 0 hsic / 1 dcor, 0 <= P <= 65535)");
-  if (h->n == 0) return ifail(h, MIDAGMA_E_ARG, "indep_run: set the data first");
-  if (kind == KIND_HSIC && !h->have_bw) return ifail(h, MIDAGMA_E_ARG, "indep_run: hsic needs the bandwidths");
+    return abi_fail(h, MIDAGMA_E_ARG, "indep_run: bad arguments (kind 0 hsic / 1 dcor, 0 <= P <= 65535)");
+  if (h->n == 0) return abi_fail(h, MIDAGMA_E_ARG, "indep_run: set the data first");
+  if (kind == KIND_HSIC && !h->have_bw) return abi_fail(h, MIDAGMA_E_ARG, "indep_run: hsic needs the bandwidths");
   const int64_t n = h->n, d = h->d;
   for (int64_t k = 0; k < 2 * m; ++k)
-    if (pairs[k] < 0 || pairs[k] >= d) return ifail(h, MIDAGMA_E_ARG, "indep_run: pair index outside [0, d)");
-  if (2 * pair_bytes(n, P) > (int64_t(8) << 30)) return ifail(h, MIDAGMA_E_ARG, "indep_run: P too large for this n");
+    if (pairs[k] < 0 || pairs[k] >= d) return abi_fail(h, MIDAGMA_E_ARG, "indep_run: pair index outside [0, d)");
+  if (2 * pair_bytes(n, P) > (int64_t(8) << 30)) return abi_fail(h, MIDAGMA_E_ARG, "indep_run: P too large for this n");
   using clock = std::chrono::steady_clock;
   auto ms_since = [](clock::time_point t0) { return std::chrono::duration<double, std::milli>(clock::now() - t0).count(); };
   h->prof[0] = h->prof[1] = h->prof[2] = h->prof[3] = 0.0;
   const clock::time_point t_check = clock::now();
   if (perms)  // every index is read as an address offset on the device
     for (int64_t k = 0, e = m * P * n; k < e; ++k)
-      if (perms[k] < 0 || perms[k] >= n) return ifail(h, MIDAGMA_E_ARG, "indep_run: permutation index outside [0, n)");
+      if (perms[k] < 0 || perms[k] >= n)
+        return abi_fail(h, MIDAGMA_E_ARG, "indep_run: permutation index outside [0, n)");
   h->prof[0] += ms_since(t_check);
   if (m == 0) return MIDAGMA_OK;
 
@@ -806,8 +779,7 @@ extern "C" int midagma_indep_run(midagma_indep* h, int kind, const int64_t* pair
       HIP_TRY(hipMemcpy(perms_out + s.q0 * P * n, s.dperm.p, s.mb * P * n * sizeof(int32_t), hipMemcpyDeviceToHost));
   };
 
-  const int rc = iguarded(h, [&] {
-    HIP_TRY(hipSetDevice(h->device));
+  const int rc = abi_guarded(h, [&] {
     prepare_stats(h, kind);
     int64_t b = 0;
     for (int64_t q0 = 0; q0 < m; q0 += mbmax, ++b) {

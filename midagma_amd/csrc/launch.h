@@ -8,37 +8,11 @@
 #include <vector>
 
 #include "../../include/midagma_hip.h"
+#include "abi.h"
 #include "common.h"
 #include "knobs.h"
 
 namespace midagma {
-
-struct HipError : std::runtime_error {
-  hipError_t code;
-  HipError(hipError_t e, const char* what, const char* file, int line)
-      : std::runtime_error(std::string("HIP error ") + hipGetErrorString(e) + " at " + file + ":" +
-                           std::to_string(line) + " (" + what + ")"),
-        code(e) {}
-};
-
-// an exception as a C ABI code with its message: what every entry point returns for a throw
-inline int classify(std::exception_ptr e, std::string& msg) {
-  try {
-    std::rethrow_exception(e);
-  } catch (const HipError& x) {
-    msg = x.what();
-    return MIDAGMA_E_HIP;
-  } catch (const std::invalid_argument& x) {
-    msg = x.what();
-    return MIDAGMA_E_ARG;
-  } catch (const std::exception& x) {
-    msg = x.what();
-    return MIDAGMA_E_STATE;
-  } catch (...) {
-    msg = "unknown error";
-    return MIDAGMA_E_STATE;
-  }
-}
 
 struct GJWork {
   double* P;       // >= 2 x 32 x 32  (double-buffered inverse of the diagonal block)
@@ -624,9 +598,7 @@ struct GramPlan {
 };
 GramPlan gram_plan(int64_t n, int64_t d, int64_t chunk_rows);
 
-// --- solver.hip (for the entries of other files that have no handle: corr.hip) ---
-// records msg as midagma_last_error(NULL)'s message of this thread and returns code
-int fail_global(int code, const std::string& msg);
+// --- solver.hip ---------------------------------------------------------------
 // the GEMM and Gauss-Jordan kernels' function attributes, once per process
 void setup_attributes();
 

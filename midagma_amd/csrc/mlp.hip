@@ -789,6 +789,156 @@ void launch_ldfast_post(const double* piv, int64_t d, double dls, double* h, con
 
 }  // namespace midagma
 
+using namespace midagma;
+
+// ---- the C entries of the DagmaMLP step ----
+extern "C" int64_t midagma_mlp_tail_scratch(int64_t n, int64_t d, int64_t m1) {
+  if (n < 1 || d < 1 || m1 < 1) return 0;
+  return mlp_tail_scratch(n, d, m1);
+}
+
+extern "C" int midagma_mlp_tail_fwd(const double* Z, const double* b1, const double* w2, const double* b2,
+                                    const double* X, int64_t n, int64_t d, int64_t m1, double* R, double* scratch,
+                                    double* ssq, void* stream) {
+  if (!Z || !w2 || !b2 || !X || !R || !scratch || !ssq || n < 1 || d < 1 || m1 < 1 || d * m1 > MLP_TAIL_MAX_DM)
+    return abi_fail(nullptr, MIDAGMA_E_ARG, "mlp_tail_fwd: bad arguments");
+  return abi_guarded(nullptr, [&] {
+    launch_mlp_tail_fwd(Z, b1, w2, b2, X, n, d, (int)m1, R, scratch, ssq, reinterpret_cast<hipStream_t>(stream));
+    return MIDAGMA_OK;
+  });
+}
+
+extern "C" int midagma_mlp_tail_bwd(const double* Z, const double* b1, const double* w2, const double* R,
+                                    const double* g, int64_t n, int64_t d, int64_t m1, double* dZ, double* dw2,
+                                    double* db2, double* db1, double* scratch, void* stream) {
+  if (!Z || !w2 || !R || !g || !dZ || !dw2 || !db2 || !scratch || n < 1 || d < 1 || m1 < 1 ||
+      d * m1 > MLP_TAIL_MAX_DM)
+    return abi_fail(nullptr, MIDAGMA_E_ARG, "mlp_tail_bwd: bad arguments");
+  return abi_guarded(nullptr, [&] {
+    launch_mlp_tail_bwd(Z, b1, w2, R, g, n, d, (int)m1, dZ, dw2, db2, db1, scratch,
+                        reinterpret_cast<hipStream_t>(stream));
+    return MIDAGMA_OK;
+  });
+}
+
+extern "C" int64_t midagma_fc1_terms_parts(int64_t d) { return d < 1 ? 0 : fc1_terms_parts(d); }
+
+extern "C" int midagma_fc1_terms(const double* W1, int64_t d, int64_t m1, double* A, double* l1part, void* stream) {
+  if (!W1 || !A || !l1part || d < 1 || m1 < 1) return abi_fail(nullptr, MIDAGMA_E_ARG, "fc1_terms: bad arguments");
+  return abi_guarded(nullptr, [&] {
+    launch_fc1_terms(W1, d, (int)m1, A, l1part, reinterpret_cast<hipStream_t>(stream));
+    return MIDAGMA_OK;
+  });
+}
+
+extern "C" int midagma_fc1_terms_bwd(const double* W1, int64_t d, int64_t m1, const double* gA, const double* gscale,
+                                     const double* gl1part, const double* lin, int64_t nlin, double* dW1,
+                                     void* stream) {
+  if (!W1 || !gA || !gl1part || !dW1 || d < 1 || m1 < 1 || nlin < 0 || (nlin > 0 && !lin))
+    return abi_fail(nullptr, MIDAGMA_E_ARG, "fc1_terms_bwd: bad arguments");
+  return abi_guarded(nullptr, [&] {
+    launch_fc1_terms_bwd(W1, d, (int)m1, gA, gscale, gl1part, lin, (int)nlin, dW1,
+                         reinterpret_cast<hipStream_t>(stream));
+    return MIDAGMA_OK;
+  });
+}
+
+extern "C" int midagma_mlp_objective(const double* ssq, const double* l1part, int64_t np, const double* h, double mu,
+                                     double lambda1, double half_d, double inv_n, double* obj, void* stream) {
+  if (!ssq || !l1part || !h || !obj || np < 1) return abi_fail(nullptr, MIDAGMA_E_ARG, "mlp_objective: bad arguments");
+  return abi_guarded(nullptr, [&] {
+    launch_mlp_objective(ssq, l1part, np, h, mu, lambda1, half_d, inv_n, obj, reinterpret_cast<hipStream_t>(stream));
+    return MIDAGMA_OK;
+  });
+}
+
+extern "C" int midagma_mlp_objective_bwd(const double* g, const double* ssq, int64_t np, double mu, double lambda1,
+                                         double half_d, double inv_n, double* gssq, double* gl1part, double* gh,
+                                         void* stream) {
+  if (!g || (!ssq) != (!gssq) || !gl1part || !gh || np < 1)
+    return abi_fail(nullptr, MIDAGMA_E_ARG, "mlp_objective_bwd: bad arguments");
+  return abi_guarded(nullptr, [&] {
+    launch_mlp_objective_bwd(g, ssq, np, mu, lambda1, half_d, inv_n, gssq, gl1part, gh,
+                             reinterpret_cast<hipStream_t>(stream));
+    return MIDAGMA_OK;
+  });
+}
+
+// ABI 6: the [d, m1, 1] objective's step with the scalar objective's backward folded into its
+// consumers (no mlp_sum / mlp_objective_bwd launches): the tail forward leaves its n row partials,
+// the objective sums them (and advances the Adam table counter), the tail backward and the fc1
+// terms' backward derive d obj / d ssq, d h and d l1 from gobj themselves.  Bit-identical to the
+// ABI-5 sequence (the same sums in the same order, the same scalar arithmetic).
+extern "C" int midagma_mlp_tail_fwd_part(const double* Z, const double* b1, const double* w2, const double* b2,
+                                         const double* X, int64_t n, int64_t d, int64_t m1, double* R, double* part,
+                                         void* stream) {
+  if (!Z || !w2 || !b2 || !X || !R || !part || n < 1 || d < 1 || m1 < 1 || d * m1 > MLP_TAIL_MAX_DM)
+    return abi_fail(nullptr, MIDAGMA_E_ARG, "mlp_tail_fwd_part: bad arguments");
+  return abi_guarded(nullptr, [&] {
+    launch_mlp_tail_fwd(Z, b1, w2, b2, X, n, d, (int)m1, R, part, nullptr, reinterpret_cast<hipStream_t>(stream));
+    return MIDAGMA_OK;
+  });
+}
+
+extern "C" int midagma_mlp_tail_bwd_obj(const double* Z, const double* b1, const double* w2, const double* R,
+                                        const double* part, const double* gobj, double mu, double half_d,
+                                        double inv_n, int64_t n, int64_t d, int64_t m1, double* dZ, double* dw2,
+                                        double* db2, double* db1, double* scratch, void* stream) {
+  // (ABI 9: dw2 = db2 = db1 = NULL leaves the chunk partials in scratch for midagma_mlp_step)
+  const bool sums = dw2 || db2 || db1;
+  if (!Z || !w2 || !R || !part || !gobj || !dZ || (sums && (!dw2 || !db2)) || !scratch || n < 1 || d < 1 ||
+      m1 < 1 || d * m1 > MLP_TAIL_MAX_DM)
+    return abi_fail(nullptr, MIDAGMA_E_ARG, "mlp_tail_bwd_obj: bad arguments");
+  return abi_guarded(nullptr, [&] {
+    launch_mlp_tail_bwd(Z, b1, w2, R, nullptr, n, d, (int)m1, dZ, dw2, db2, db1, scratch,
+                        reinterpret_cast<hipStream_t>(stream), part, gobj, mu, half_d, inv_n, sums);
+    return MIDAGMA_OK;
+  });
+}
+
+extern "C" int midagma_mlp_step(double* const* params, double* const* exp_avg, double* const* exp_avg_sq, int64_t n,
+                                int64_t d, int64_t m1, const double* gA, const double* gobj, double mu,
+                                double lambda1, const double* lin, int64_t nlin, const double* scratch,
+                                const double* table, const int64_t* counter, double w1, double beta2, double c2,
+                                double eps, double wd, const double* gate, double* A, double* l1part, void* stream) {
+  if (!params || !exp_avg || !exp_avg_sq || !gA || !gobj || !scratch || !table || !counter || !A || !l1part ||
+      n < 1 || d < 1 || m1 < 1 || d * m1 > MLP_TAIL_MAX_DM || nlin < 0 || (nlin > 0 && !lin))
+    return abi_fail(nullptr, MIDAGMA_E_ARG, "mlp_step: bad arguments");
+  for (int q = 0; q < 4; ++q)
+    if (!params[q] || !exp_avg[q] || !exp_avg_sq[q]) return abi_fail(nullptr, MIDAGMA_E_ARG, "mlp_step: bad tensor");
+  const MlpStepPtrs p{params[0], params[1], params[2], params[3], exp_avg[0], exp_avg_sq[0], exp_avg[1],
+                      exp_avg_sq[1], exp_avg[2], exp_avg_sq[2], exp_avg[3], exp_avg_sq[3]};
+  return abi_guarded(nullptr, [&] {
+    launch_mlp_step(p, n, d, (int)m1, gA, gobj, mu, lambda1, lin, (int)nlin, scratch, table, counter, w1, beta2, c2,
+                    eps, wd, gate, A, l1part, reinterpret_cast<hipStream_t>(stream));
+    return MIDAGMA_OK;
+  });
+}
+
+extern "C" int midagma_fc1_terms_bwd_obj(const double* W1, int64_t d, int64_t m1, const double* gA, const double* gobj,
+                                         double mu, double lambda1, const double* lin, int64_t nlin, double* dW1,
+                                         void* stream) {
+  if (!W1 || !gA || !gobj || !dW1 || d < 1 || m1 < 1 || nlin < 0 || (nlin > 0 && !lin))
+    return abi_fail(nullptr, MIDAGMA_E_ARG, "fc1_terms_bwd_obj: bad arguments");
+  return abi_guarded(nullptr, [&] {
+    launch_fc1_terms_bwd(W1, d, (int)m1, gA, nullptr, nullptr, lin, (int)nlin, dW1,
+                         reinterpret_cast<hipStream_t>(stream), gobj, mu, lambda1);
+    return MIDAGMA_OK;
+  });
+}
+
+extern "C" int midagma_mlp_objective_part(const double* part, int64_t npart, const double* l1part, int64_t np,
+                                          const double* h, double mu, double lambda1, double half_d, double inv_n,
+                                          double* obj, int64_t* counter, void* stream) {
+  if (!part || npart < 1 || !l1part || !h || !obj || np < 1)
+    return abi_fail(nullptr, MIDAGMA_E_ARG, "mlp_objective_part: bad arguments");
+  return abi_guarded(nullptr, [&] {
+    launch_mlp_objective(nullptr, l1part, np, h, mu, lambda1, half_d, inv_n, obj,
+                         reinterpret_cast<hipStream_t>(stream), part, npart, counter);
+    return MIDAGMA_OK;
+  });
+}
+
 #ifdef MIDAGMA_EXPERIMENTS
 // ---- fc1 and the tail fused on the f64 MFMA (experiments build; BASELINE config 5) -----------
 // Forward: Z = X W1^T (nonlinear.py:99-100, fc1 without its bias) in 64 x TC tiles, TC = 16 NCB a
@@ -1145,5 +1295,36 @@ void launch_mlp_tail_bwd_lin(const double* S, const double* w2, const double* R,
 }
 
 }  // namespace midagma
+
+// fc1 and the tail fused on the MFMA (mlp.hip; measured slower at config 5):
+// not in the public header, bound by nonlinear.py when the loaded library has them
+extern "C" int64_t midagma_mlp_fused_parts(int64_t n, int64_t d, int64_t m1) { return mlp_fused_parts(n, d, m1); }
+
+extern "C" int64_t midagma_mlp_fused_splits(int64_t n) { return n < 1 ? 0 : mlp_fused_splits(n); }
+
+extern "C" int midagma_mlp_fc1_tail_fwd(const double* X, const double* W1, const double* b1, const double* w2,
+                                        const double* b2, int64_t n, int64_t d, int64_t m1, double* S, double* R,
+                                        double* part, void* stream) {
+  if (!X || !W1 || !w2 || !b2 || !S || !R || !part || mlp_fused_parts(n, d, m1) < 1)
+    return abi_fail(nullptr, MIDAGMA_E_ARG, "mlp_fc1_tail_fwd: bad arguments");
+  return abi_guarded(nullptr, [&] {
+    launch_mlp_fc1_tail_fwd(X, W1, b1, w2, b2, n, d, (int)m1, S, R, part, reinterpret_cast<hipStream_t>(stream));
+    return MIDAGMA_OK;
+  });
+}
+
+extern "C" int midagma_mlp_tail_bwd_lin(const double* S, const double* w2, const double* R, const double* X,
+                                        const double* part, int64_t npart, const double* gobj, double mu,
+                                        double half_d, double inv_n, int64_t n, int64_t d, int64_t m1, double* lin,
+                                        double* dw2, double* db2, double* db1, double* scratch, void* stream) {
+  if (!S || !w2 || !R || !X || !part || npart < 1 || !gobj || !lin || !dw2 || !db2 || !scratch ||
+      mlp_fused_parts(n, d, m1) < 1)
+    return abi_fail(nullptr, MIDAGMA_E_ARG, "mlp_tail_bwd_lin: bad arguments");
+  return abi_guarded(nullptr, [&] {
+    launch_mlp_tail_bwd_lin(S, w2, R, X, part, npart, gobj, mu, half_d, inv_n, n, d, (int)m1, lin, dw2, db2, db1,
+                            scratch, reinterpret_cast<hipStream_t>(stream));
+    return MIDAGMA_OK;
+  });
+}
 
 #endif  // MIDAGMA_EXPERIMENTS

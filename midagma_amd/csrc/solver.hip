@@ -1,5 +1,5 @@
-// Host orchestration + C ABI (include/midagma_hip.h).  The solver object and its drivers:
-// solver_impl.h.
+// The midagma_solver entries of the C ABI (include/midagma_hip.h) and the solver's debug hooks.
+// The solver object and its drivers: solver_impl.h; the entry-point layer: abi.h.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -13,7 +13,6 @@
 #include "solver_impl.h"
 
 namespace {
-thread_local std::string g_global_error;
 
 // scipy's check_finite (linear.py:226 -> sla.inv(..., check_finite=True)): a non-finite input
 // is a ValueError, not a singular matrix
@@ -23,50 +22,24 @@ bool all_finite(const double* p, int64_t rows, int64_t cols, int64_t ld) {
       if (!std::isfinite(p[i * ld + j])) return false;
   return true;
 }
-constexpr const char* kNonFinite = "array must not contain infs or NaNs";
-}  // namespace
-
-namespace {
 
 __global__ void div_kernel(const double* __restrict__ x, double n, double* __restrict__ y, int64_t count) {
   for (int64_t i = (int64_t)blockIdx.x * NTHREADS + threadIdx.x; i < count; i += (int64_t)gridDim.x * NTHREADS)
     y[i] = x[i] / n;
 }
 
-int fail(midagma_solver* s, int code, const std::string& msg) {
-  if (s)
-    s->err = msg;
-  else
-    g_global_error = msg;
-  return code;
-}
+}  // namespace
 
-template <class F>
-int guarded(midagma_solver* s, F&& f) {
-  try {
-    if (s) HIP_TRY(hipSetDevice(s->device));
-    return f();
-  } catch (...) {
-    std::string msg;
-    const int rc = classify(std::current_exception(), msg);
-    return fail(s, rc, msg);
-  }
-}
+// abi.h's hook: an entry's device work runs on the solver's device
+static void abi_select_device(const midagma_solver* s) { HIP_TRY(hipSetDevice(s->device)); }
 
-std::once_flag g_attr_once;
-void setup_attributes_once() {
-  std::call_once(g_attr_once, [] {
+void midagma::setup_attributes() {
+  static std::once_flag once;
+  std::call_once(once, [] {
     gj_setup_attributes();
     gemm_setup_attributes();
   });
 }
-
-}  // namespace
-
-namespace midagma {
-int fail_global(int code, const std::string& msg) { return fail(nullptr, code, msg); }
-void setup_attributes() { setup_attributes_once(); }
-}  // namespace midagma
 
 namespace {
 
@@ -75,8 +48,8 @@ namespace {
 // non-finite, e.g. from non-finite data) and LinAlgError when the finite matrix is singular.
 int singular_or_nonfinite(midagma_solver* s, int rc, const midagma_result* res, const double* W) {
   if (rc != MIDAGMA_OK || !res || res->status != MIDAGMA_ST_SINGULAR) return rc;
-  if (!all_finite(W, s->d, s->d, s->d)) return fail(s, MIDAGMA_E_ARG, std::string("minimize: ") + kNonFinite);
-  return fail(s, MIDAGMA_E_SINGULAR, "singular matrix: inverse of sI - W*W is not finite");
+  if (!all_finite(W, s->d, s->d, s->d)) return abi_fail(s, MIDAGMA_E_ARG, std::string("minimize: ") + kNonFinite);
+  return abi_fail(s, MIDAGMA_E_SINGULAR, "singular matrix: inverse of sI - W*W is not finite");
 }
 
 }  // namespace
@@ -86,18 +59,18 @@ extern "C" {
 int midagma_abi_version(void) { return MIDAGMA_ABI_VERSION; }
 
 int midagma_device_count(int* n) {
-  return guarded(nullptr, [&] {
+  return abi_guarded(nullptr, [&] {
     HIP_TRY(hipGetDeviceCount(n));
     return MIDAGMA_OK;
   });
 }
 
-const char* midagma_last_error(const midagma_solver* s) { return s ? s->err.c_str() : g_global_error.c_str(); }
+const char* midagma_last_error(const midagma_solver* s) { return abi_last_error(s); }
 
 int midagma_create(midagma_solver** out, int loss, int mode, int64_t d, int device, void* stream) {
   if (!out || d < 1 || (loss != 0 && loss != 1) || (mode != 0 && mode != 1) ||
       (loss == MIDAGMA_LOSS_LOGISTIC && mode == MIDAGMA_MODE_COV))
-    return fail(nullptr, MIDAGMA_E_ARG, "midagma_create: bad arguments (logistic needs data mode)");
+    return abi_fail(nullptr, MIDAGMA_E_ARG, "midagma_create: bad arguments (logistic needs data mode)");
   midagma_solver* s = new midagma_solver();
   s->loss = loss;
   s->mode = mode;
@@ -116,8 +89,8 @@ int midagma_create(midagma_solver** out, int loss, int mode, int64_t d, int devi
   if (mode == MIDAGMA_MODE_COV && d > 256 && (pad_b2 == 1 || (pad_b2 < 0 && d <= 640)))
     s->D = (d + 255) / 256 * 256;
   s->device = device;
-  int rc = guarded(s, [&] {
-    setup_attributes_once();
+  int rc = abi_guarded(s, [&] {
+    setup_attributes();
     if (stream) {
       s->stream = reinterpret_cast<hipStream_t>(stream);
     } else {
@@ -129,7 +102,7 @@ int midagma_create(midagma_solver** out, int loss, int mode, int64_t d, int devi
     return MIDAGMA_OK;
   });
   if (rc != MIDAGMA_OK) {
-    g_global_error = s->err;
+    abi_fail(nullptr, rc, s->err);
     delete s;
     return rc;
   }
@@ -148,9 +121,9 @@ void* midagma_stream(midagma_solver* s) { return s ? reinterpret_cast<void*>(s->
 int64_t midagma_padded_dim(const midagma_solver* s) { return s ? s->D : 0; }
 
 int midagma_set_cov(midagma_solver* s, const double* cov, int64_t ld) {
-  if (!s || !cov || ld < s->d) return fail(s, MIDAGMA_E_ARG, "set_cov: bad arguments");
-  if (!all_finite(cov, s->d, s->d, ld)) return fail(s, MIDAGMA_E_ARG, std::string("set_cov: ") + kNonFinite);
-  return guarded(s, [&] {
+  if (!s || !cov || ld < s->d) return abi_fail(s, MIDAGMA_E_ARG, "set_cov: bad arguments");
+  if (!all_finite(cov, s->d, s->d, ld)) return abi_fail(s, MIDAGMA_E_ARG, std::string("set_cov: ") + kNonFinite);
+  return abi_guarded(s, [&] {
     s->upload_matrix(s->cov, cov, ld);
     HIP_TRY(hipStreamSynchronize(s->stream));
     s->has_cov = true;
@@ -159,8 +132,8 @@ int midagma_set_cov(midagma_solver* s, const double* cov, int64_t ld) {
 }
 
 int midagma_set_masks(midagma_solver* s, const double* mask_inc, const double* mask_exc) {
-  if (!s) return fail(s, MIDAGMA_E_ARG, "set_masks: null solver");
-  return guarded(s, [&] {
+  if (!s) return abi_fail(s, MIDAGMA_E_ARG, "set_masks: null solver");
+  return abi_guarded(s, [&] {
     const size_t DD = (size_t)s->D * s->D;
     const bool inc = mask_inc != nullptr, exc = mask_exc != nullptr;
     if (inc) {
@@ -187,10 +160,10 @@ int midagma_set_masks(midagma_solver* s, const double* mask_inc, const double* m
 
 int midagma_set_data(midagma_solver* s, const double* X, int64_t n_local, int64_t n_global, int on_device) {
   if (!s || !X || n_local < 1 || n_global < n_local || s->mode != MIDAGMA_MODE_DATA)
-    return fail(s, MIDAGMA_E_ARG, "set_data: bad arguments (data mode only)");
+    return abi_fail(s, MIDAGMA_E_ARG, "set_data: bad arguments (data mode only)");
   if (!on_device && !all_finite(X, n_local, s->d, s->d))
-    return fail(s, MIDAGMA_E_ARG, std::string("set_data: ") + kNonFinite);
-  return guarded(s, [&] {
+    return abi_fail(s, MIDAGMA_E_ARG, std::string("set_data: ") + kNonFinite);
+  return abi_guarded(s, [&] {
     const int64_t D = s->D;
     s->n_local = n_local;
     s->n_global = n_global;
@@ -307,8 +280,8 @@ int midagma_set_data(midagma_solver* s, const double* X, int64_t n_local, int64_
 }
 
 int midagma_data_gram(midagma_solver* s) {
-  if (!s || !s->has_data) return fail(s, MIDAGMA_E_STATE, "data_gram: set_data first");
-  return guarded(s, [&] {
+  if (!s || !s->has_data) return abi_fail(s, MIDAGMA_E_STATE, "data_gram: set_data first");
+  return abi_guarded(s, [&] {
     GemmSpec gs = s->xty_spec();  // X^T X: the X^T Y GEMM with Y = X
     gs.B = s->X.p;
     launch_gemm_summed(gs, s->Zparts.p, s->zbuf, nullptr, s->stream);
@@ -318,8 +291,8 @@ int midagma_data_gram(midagma_solver* s) {
 }
 
 int midagma_cov_from_zbuf(midagma_solver* s, double n) {
-  if (!s || !(n > 0)) return fail(s, MIDAGMA_E_ARG, "cov_from_zbuf: n must be > 0");
-  return guarded(s, [&] {
+  if (!s || !(n > 0)) return abi_fail(s, MIDAGMA_E_ARG, "cov_from_zbuf: n must be > 0");
+  return abi_guarded(s, [&] {
     // cov = (X^T X) / float(n), a division as in linear.py:428
     const int64_t DD = s->D * s->D;
     hipLaunchKernelGGL(div_kernel, dim3(4096), dim3(NTHREADS), 0, s->stream, s->zbuf, n, s->cov.p, DD);
@@ -331,9 +304,9 @@ int midagma_cov_from_zbuf(midagma_solver* s, double n) {
 }
 
 int midagma_get_cov(midagma_solver* s, double* out, int64_t ld) {
-  if (!s || !out || ld < s->d) return fail(s, MIDAGMA_E_ARG, "get_cov: bad arguments");
-  if (!s->has_cov) return fail(s, MIDAGMA_E_STATE, "get_cov: no cov (set_cov or cov_from_zbuf first)");
-  return guarded(s, [&] {
+  if (!s || !out || ld < s->d) return abi_fail(s, MIDAGMA_E_ARG, "get_cov: bad arguments");
+  if (!s->has_cov) return abi_fail(s, MIDAGMA_E_STATE, "get_cov: no cov (set_cov or cov_from_zbuf first)");
+  return abi_guarded(s, [&] {
     HIP_TRY(hipMemcpy2DAsync(out, ld * sizeof(double), s->cov.p, s->D * sizeof(double), s->d * sizeof(double), s->d,
                              hipMemcpyDeviceToHost, s->stream));
     HIP_TRY(hipStreamSynchronize(s->stream));
@@ -341,80 +314,9 @@ int midagma_get_cov(midagma_solver* s, double* out, int64_t ld) {
   });
 }
 
-// ABI 7: fit()'s data preparation on device memory (linear.py:406-428), csrc/gram.hip.
-int midagma_colsum_dev(const double* X, int64_t n, int64_t d, int64_t ldx, double* out_dev, void* stream) {
-  if (n < 0 || d < 1 || ldx < d || !out_dev || (n > 0 && !X))
-    return fail(nullptr, MIDAGMA_E_ARG, "colsum_dev: bad arguments");
-  return guarded(nullptr, [&] {
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    DevBuf<> part;
-    part.alloc((size_t)colsum_parts(n) * d);
-    launch_colsum(X, n, d, ldx, part.p, out_dev, st);
-    HIP_TRY(hipStreamSynchronize(st));  // the partials are freed on return
-    return MIDAGMA_OK;
-  });
-}
-
-int midagma_center_dev(double* X, int64_t n, int64_t d, int64_t ldx, const double* colsum_dev, double nrows,
-                       void* stream) {
-  if (n < 0 || d < 1 || ldx < d || !colsum_dev || (n > 0 && !X) || !(nrows > 0))
-    return fail(nullptr, MIDAGMA_E_ARG, "center_dev: bad arguments");
-  return guarded(nullptr, [&] {
-    launch_center(X, n, d, ldx, colsum_dev, nrows, reinterpret_cast<hipStream_t>(stream));
-    return MIDAGMA_OK;
-  });
-}
-
-int midagma_gram(const double* X, int64_t n, int64_t d, int64_t ldx, int on_device, double* G_dev, int64_t ldg,
-                 void* stream) {
-  if (n < 0 || d < 1 || ldx < d || !G_dev || ldg < d || (n > 0 && !X))
-    return fail(nullptr, MIDAGMA_E_ARG, "gram: bad arguments");
-  return guarded(nullptr, [&] {
-    setup_attributes_once();
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    static const int64_t chunk_rows = [] {
-      const char* e = getenv("MIDAGMA_GRAM_CHUNK_ROWS");
-      return e ? std::max<int64_t>(256, atoll(e)) : int64_t(262144);
-    }();
-    const GramPlan p = gram_plan(n, d, chunk_rows);
-    const int64_t D = p.D, DD = D * D;
-    DevBuf<> S, Z, fl;
-    S.alloc((size_t)p.chunk * D);
-    Z.alloc((size_t)(p.split + 2) * DD);  // [0] the running sum, [1..split] a chunk's slices, [split+1] the new sum
-    fl.alloc(1);
-    int* flag = reinterpret_cast<int*>(fl.p);
-    HIP_TRY(hipMemsetAsync(flag, 0, sizeof(int), st));
-    HIP_TRY(hipMemsetAsync(Z.p, 0, DD * sizeof(double), st));
-    if (!on_device) HIP_TRY(hipMemsetAsync(S.p, 0, (size_t)p.chunk * D * sizeof(double), st));
-    for (int64_t c = 0; c < p.nchunks; ++c) {
-      const int64_t r0 = c * p.chunk, rows = std::min(p.chunk, n - r0);
-      const int64_t rpad = (rows + 255) / 256 * 256;
-      if (on_device) {
-        launch_stage_rows(X + r0 * ldx, ldx, rows, d, S.p, D, rpad, flag, st);
-      } else {
-        if (rows < rpad) HIP_TRY(hipMemsetAsync(S.p + rows * D, 0, (rpad - rows) * D * sizeof(double), st));
-        HIP_TRY(hipMemcpy2DAsync(S.p, D * sizeof(double), X + r0 * ldx, ldx * sizeof(double), d * sizeof(double),
-                                 rows, hipMemcpyHostToDevice, st));
-        launch_nonfinite_or(S.p, rows, d, D, flag, st);
-      }
-      // (the running sum is slice 0 of the sum, so the slices are summed at every split)
-      launch_gemm(GemmSpec{D, D, rpad, S.p, D, true, S.p, D, B_PLAIN, Z.p + DD, D, p.split, DD}, nullptr, st);
-      launch_sum_slices(Z.p, p.split + 1, DD, DD, Z.p + (p.split + 1) * DD, nullptr, st);
-      HIP_TRY(hipMemcpyAsync(Z.p, Z.p + (p.split + 1) * DD, DD * sizeof(double), hipMemcpyDeviceToDevice, st));
-    }
-    HIP_TRY(hipMemcpy2DAsync(G_dev, ldg * sizeof(double), Z.p, D * sizeof(double), d * sizeof(double), d,
-                             hipMemcpyDeviceToDevice, st));
-    int bad = 0;
-    HIP_TRY(hipMemcpyAsync(&bad, flag, sizeof(int), hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    if (bad) throw std::invalid_argument(std::string("gram: ") + kNonFinite);
-    return MIDAGMA_OK;
-  });
-}
-
 int midagma_set_cov_dev(midagma_solver* s, const double* G_dev, int64_t ldg, double divisor) {
-  if (!s || !G_dev || ldg < s->d || !(divisor > 0)) return fail(s, MIDAGMA_E_ARG, "set_cov_dev: bad arguments");
-  return guarded(s, [&] {
+  if (!s || !G_dev || ldg < s->d || !(divisor > 0)) return abi_fail(s, MIDAGMA_E_ARG, "set_cov_dev: bad arguments");
+  return abi_guarded(s, [&] {
     // cov = (X^T X) / float(n), a division as in linear.py:428 (the caller all-reduced the Gram)
     int* flag = reinterpret_cast<int*>(s->partials.p);
     HIP_TRY(hipMemsetAsync(flag, 0, sizeof(int), s->stream));
@@ -429,14 +331,14 @@ int midagma_set_cov_dev(midagma_solver* s, const double* G_dev, int64_t ldg, dou
 }
 
 int midagma_comm_unique_id(void* out, int64_t cap) {
-  if (!out || cap < 128) return fail(nullptr, MIDAGMA_E_ARG, "comm_unique_id: needs a 128-byte buffer");
-  return guarded(nullptr, [&] { return comm_unique_id(out); });
+  if (!out || cap < 128) return abi_fail(nullptr, MIDAGMA_E_ARG, "comm_unique_id: needs a 128-byte buffer");
+  return abi_guarded(nullptr, [&] { return comm_unique_id(out); });
 }
 
 int midagma_comm_init(midagma_solver* s, const void* id, int64_t id_len, int nranks, int rank) {
   if (!s || !id || id_len != 128 || nranks < 1 || rank < 0 || rank >= nranks || s->mode != MIDAGMA_MODE_DATA)
-    return fail(s, MIDAGMA_E_ARG, "comm_init: bad arguments (data mode, a 128-byte unique id, 0 <= rank < nranks)");
-  return guarded(s, [&] {
+    return abi_fail(s, MIDAGMA_E_ARG, "comm_init: bad arguments (data mode, a 128-byte unique id, 0 <= rank < nranks)");
+  return abi_guarded(s, [&] {
     HIP_TRY(hipStreamSynchronize(s->stream));
     comm_destroy(s->comm);
     s->comm = nullptr;
@@ -452,8 +354,8 @@ int midagma_comm_init(midagma_solver* s, const void* id, int64_t id_len, int nra
 int midagma_comm_ranks(const midagma_solver* s) { return s ? (s->comm ? s->comm_ranks : 0) : 0; }
 
 int midagma_comm_allreduce_zbuf(midagma_solver* s) {
-  if (!s || !s->comm) return fail(s, MIDAGMA_E_STATE, "comm_allreduce_zbuf: comm_init first");
-  return guarded(s, [&] {
+  if (!s || !s->comm) return abi_fail(s, MIDAGMA_E_STATE, "comm_allreduce_zbuf: comm_init first");
+  return abi_guarded(s, [&] {
     comm_allreduce(s->comm, s->zbuf, (size_t)(s->D * s->D + 64), false, s->stream);
     return MIDAGMA_OK;
   });
@@ -462,8 +364,8 @@ int midagma_comm_allreduce_zbuf(midagma_solver* s) {
 int64_t midagma_zbuf_len(const midagma_solver* s) { return s ? s->D * s->D + 64 : 0; }
 
 int midagma_bind_zbuf(midagma_solver* s, void* dev_ptr, int64_t len) {
-  if (!s || len < s->D * s->D + 64) return fail(s, MIDAGMA_E_ARG, "bind_zbuf: buffer too small");
-  return guarded(s, [&] {
+  if (!s || len < s->D * s->D + 64) return abi_fail(s, MIDAGMA_E_ARG, "bind_zbuf: buffer too small");
+  return abi_guarded(s, [&] {
     s->zbuf = dev_ptr ? static_cast<double*>(dev_ptr) : s->zown.p;
     s->graphs_valid = false;
     return MIDAGMA_OK;
@@ -472,9 +374,9 @@ int midagma_bind_zbuf(midagma_solver* s, void* dev_ptr, int64_t len) {
 
 int midagma_minimize(midagma_solver* s, double* W, double mu, int64_t max_iter, double s_dom, double lr, double tol,
                      double beta1, double beta2, double lambda1, int64_t checkpoint, midagma_result* res) {
-  if (!s || !W) return fail(s, MIDAGMA_E_ARG, "minimize: null argument");
-  if (!all_finite(W, s->d, s->d, s->d)) return fail(s, MIDAGMA_E_ARG, std::string("minimize: ") + kNonFinite);
-  int rc = guarded(s, [&] {
+  if (!s || !W) return abi_fail(s, MIDAGMA_E_ARG, "minimize: null argument");
+  if (!all_finite(W, s->d, s->d, s->d)) return abi_fail(s, MIDAGMA_E_ARG, std::string("minimize: ") + kNonFinite);
+  int rc = abi_guarded(s, [&] {
     s->begin(W, mu, max_iter, s_dom, lr, tol, beta1, beta2, lambda1, checkpoint);
     s->run_loop(max_iter, checkpoint);
     s->finish(W, res);
@@ -485,9 +387,9 @@ int midagma_minimize(midagma_solver* s, double* W, double mu, int64_t max_iter, 
 
 int midagma_begin(midagma_solver* s, const double* W, double mu, int64_t max_iter, double s_dom, double lr,
                   double tol, double beta1, double beta2, double lambda1, int64_t checkpoint) {
-  if (!s || !W) return fail(s, MIDAGMA_E_ARG, "begin: null argument");
-  if (!all_finite(W, s->d, s->d, s->d)) return fail(s, MIDAGMA_E_ARG, std::string("begin: ") + kNonFinite);
-  return guarded(s, [&] {
+  if (!s || !W) return abi_fail(s, MIDAGMA_E_ARG, "begin: null argument");
+  if (!all_finite(W, s->d, s->d, s->d)) return abi_fail(s, MIDAGMA_E_ARG, std::string("begin: ") + kNonFinite);
+  return abi_guarded(s, [&] {
     s->begin(W, mu, max_iter, s_dom, lr, tol, beta1, beta2, lambda1, checkpoint);
     s->ensure_graphs();
     return MIDAGMA_OK;
@@ -495,8 +397,8 @@ int midagma_begin(midagma_solver* s, const double* W, double mu, int64_t max_ite
 }
 
 int midagma_run_slots(midagma_solver* s, int64_t n) {
-  if (!s || !s->begun || n < 0) return fail(s, MIDAGMA_E_STATE, "run_slots: call begin first");
-  return guarded(s, [&] {
+  if (!s || !s->begun || n < 0) return abi_fail(s, MIDAGMA_E_STATE, "run_slots: call begin first");
+  return abi_guarded(s, [&] {
     if (s->blocked()) {
       s->drive_blocked(n);
       return MIDAGMA_OK;
@@ -511,16 +413,16 @@ int midagma_run_slots(midagma_solver* s, int64_t n) {
 }
 
 int midagma_sync(midagma_solver* s) {
-  if (!s) return fail(s, MIDAGMA_E_ARG, "null solver");
-  return guarded(s, [&] {
+  if (!s) return abi_fail(s, MIDAGMA_E_ARG, "null solver");
+  return abi_guarded(s, [&] {
     HIP_TRY(hipStreamSynchronize(s->stream));
     return MIDAGMA_OK;
   });
 }
 
 int midagma_profile_parts(midagma_solver* s, int reps, double* ms_out) {
-  if (!s || !s->begun || reps < 1 || !ms_out) return fail(s, MIDAGMA_E_STATE, "profile_parts: call begin first");
-  return guarded(s, [&] {
+  if (!s || !s->begun || reps < 1 || !ms_out) return abi_fail(s, MIDAGMA_E_STATE, "profile_parts: call begin first");
+  return abi_guarded(s, [&] {
     Event a, b;
     a.create();
     b.create();
@@ -569,24 +471,24 @@ int midagma_profile_parts(midagma_solver* s, int reps, double* ms_out) {
 }
 
 int midagma_step_partial(midagma_solver* s) {
-  if (!s || !s->begun) return fail(s, MIDAGMA_E_STATE, "step_partial: call begin first");
-  return guarded(s, [&] {
+  if (!s || !s->begun) return abi_fail(s, MIDAGMA_E_STATE, "step_partial: call begin first");
+  return abi_guarded(s, [&] {
     HIP_TRY(hipGraphLaunch(s->g_part1, s->stream));
     return MIDAGMA_OK;
   });
 }
 
 int midagma_step_finish(midagma_solver* s) {
-  if (!s || !s->begun) return fail(s, MIDAGMA_E_STATE, "step_finish: call begin first");
-  return guarded(s, [&] {
+  if (!s || !s->begun) return abi_fail(s, MIDAGMA_E_STATE, "step_finish: call begin first");
+  return abi_guarded(s, [&] {
     HIP_TRY(hipGraphLaunch(s->g_part2, s->stream));
     return MIDAGMA_OK;
   });
 }
 
 int midagma_poll(midagma_solver* s, midagma_result* res) {
-  if (!s) return fail(s, MIDAGMA_E_ARG, "null solver");
-  return guarded(s, [&] {
+  if (!s) return abi_fail(s, MIDAGMA_E_ARG, "null solver");
+  return abi_guarded(s, [&] {
     HIP_TRY(hipMemcpyAsync(&s->h_state.p[1], s->d_state.p, sizeof(State), hipMemcpyDeviceToHost, s->stream));
     HIP_TRY(hipStreamSynchronize(s->stream));
     s->check_handoff(s->h_state.p[1]);
@@ -596,8 +498,8 @@ int midagma_poll(midagma_solver* s, midagma_result* res) {
 }
 
 int midagma_end(midagma_solver* s, double* W, midagma_result* res) {
-  if (!s || !W || !s->begun) return fail(s, MIDAGMA_E_STATE, "end: call begin first");
-  int rc = guarded(s, [&] {
+  if (!s || !W || !s->begun) return abi_fail(s, MIDAGMA_E_STATE, "end: call begin first");
+  int rc = abi_guarded(s, [&] {
     s->finish(W, res);
     return MIDAGMA_OK;
   });
@@ -605,8 +507,8 @@ int midagma_end(midagma_solver* s, double* W, midagma_result* res) {
 }
 
 int midagma_set_w_float32(midagma_solver* s, int float32) {
-  if (!s) return fail(s, MIDAGMA_E_ARG, "null solver");
-  return guarded(s, [&] {
+  if (!s) return abi_fail(s, MIDAGMA_E_ARG, "null solver");
+  return abi_guarded(s, [&] {
     const bool on = float32 != 0;
     if (on != s->w32) s->graphs_valid = false;  // the float32 slots carry numpy's L1 sum
     if (on && !s->l1w.p) s->l1w.alloc((size_t)(1 + (np_l1_chunks(s->d) + 1) / 2));
@@ -656,7 +558,7 @@ extern "C" int midagma_debug_xty_form(midagma_solver* s, int mode, int split) {
 // inverse) is running; handbacks counts the hand-backs the scheduler has re-run.
 extern "C" int midagma_debug_spoil_warm(midagma_solver* s) {
   if (!s || !s->blocked()) return -1;
-  return guarded(s, [&] {
+  return abi_guarded(s, [&] {
     for (DevBuf<>* b : {&s->Pst2, &s->Pst2b})
       if (b->p) HIP_TRY(hipMemsetAsync(b->p, 0, b->n * sizeof(double), s->stream));
     HIP_TRY(hipStreamSynchronize(s->stream));
@@ -706,7 +608,7 @@ extern "C" int midagma_debug_at_fold(midagma_solver* s, int on) {
   const int old = s->at_fold ? 1 : 0;
   if (on < 0 || (on != 0) == s->at_fold) return old;
   if (on && !(s->mode == MIDAGMA_MODE_COV && s->blocked())) return -1;
-  return guarded(s, [&] {
+  return abi_guarded(s, [&] {
     if (on && !s->A0.p) s->A0.alloc(s->D * s->D);
     s->at_fold = on != 0;
     s->graphs_valid = false;
@@ -767,7 +669,7 @@ extern "C" int midagma_debug_blocked(midagma_solver* s, double* out, int64_t cap
 int64_t midagma_checkpoints(midagma_solver* s, midagma_ckpt* out, int64_t cap) {
   if (!s || !s->d_ckpt.p) return 0;
   int64_t n = 0;
-  int rc = guarded(s, [&] {
+  int rc = abi_guarded(s, [&] {
     State st{};
     HIP_TRY(hipMemcpy(&st, s->d_state.p, sizeof(State), hipMemcpyDeviceToHost));
     n = std::min<int64_t>(std::min<int64_t>(st.n_ckpt, s->ckpt_cap), cap);
@@ -780,8 +682,8 @@ int64_t midagma_checkpoints(midagma_solver* s, midagma_ckpt* out, int64_t cap) {
 
 int midagma_set_trek(midagma_solver* s, int seq, int agg, int mode, double weight, double eps_inv, int64_t K,
                      const int64_t* pairs, int64_t m) {
-  if (!s || (m > 0 && !pairs) || m < 0) return fail(s, MIDAGMA_E_ARG, "set_trek: bad arguments");
-  return guarded(s, [&] {
+  if (!s || (m > 0 && !pairs) || m < 0) return abi_fail(s, MIDAGMA_E_ARG, "set_trek: bad arguments");
+  return abi_guarded(s, [&] {
     s->set_trek(seq, agg, mode, weight, eps_inv, K, pairs, m);
     HIP_TRY(hipStreamSynchronize(s->stream));
     return MIDAGMA_OK;
@@ -790,8 +692,8 @@ int midagma_set_trek(midagma_solver* s, int seq, int agg, int mode, double weigh
 
 int midagma_set_trek_tcc(midagma_solver* s, int mode, double weight, double w, double eps, const int64_t* pairs,
                          int64_t m) {
-  if (!s || (m > 0 && !pairs) || m < 0) return fail(s, MIDAGMA_E_ARG, "set_trek_tcc: bad arguments");
-  return guarded(s, [&] {
+  if (!s || (m > 0 && !pairs) || m < 0) return abi_fail(s, MIDAGMA_E_ARG, "set_trek_tcc: bad arguments");
+  return abi_guarded(s, [&] {
     s->set_trek_tcc(mode, weight, w, eps, pairs, m);
     HIP_TRY(hipStreamSynchronize(s->stream));
     return MIDAGMA_OK;
@@ -799,8 +701,8 @@ int midagma_set_trek_tcc(midagma_solver* s, int mode, double weight, double w, d
 }
 
 int midagma_trek(midagma_solver* s, const double* W, double* value, double* G) {
-  if (!s || !W || !value) return fail(s, MIDAGMA_E_ARG, "trek: null argument");
-  return guarded(s, [&] {
+  if (!s || !W || !value) return abi_fail(s, MIDAGMA_E_ARG, "trek: null argument");
+  return abi_guarded(s, [&] {
     const int64_t D = s->D, d = s->d, DD = D * D;
     if (!s->trek_on) {  // trek_value_grad: (0, zeros) when disabled (notreks.py)
       *value = 0.0;
@@ -837,9 +739,9 @@ int midagma_trek(midagma_solver* s, const double* W, double* value, double* G) {
 }
 
 int midagma_h(midagma_solver* s, const double* W, double s_dom, double* h, double* G) {
-  if (!s || !W || !h) return fail(s, MIDAGMA_E_ARG, "h: null argument");
-  if (!all_finite(W, s->d, s->d, s->d)) return fail(s, MIDAGMA_E_ARG, std::string("h: ") + kNonFinite);
-  return guarded(s, [&] {
+  if (!s || !W || !h) return abi_fail(s, MIDAGMA_E_ARG, "h: null argument");
+  if (!all_finite(W, s->d, s->d, s->d)) return abi_fail(s, MIDAGMA_E_ARG, std::string("h: ") + kNonFinite);
+  return abi_guarded(s, [&] {
     const int64_t D = s->D, d = s->d, DD = D * D;
     s->scratch.alloc(DD);
     HIP_TRY(hipMemsetAsync(s->scratch.p, 0, DD * sizeof(double), s->stream));
@@ -881,9 +783,9 @@ static void host_trace_l1(midagma_solver* s, const double* Wd, const double* Z, 
 }
 
 int midagma_score(midagma_solver* s, const double* W, double* loss, double* G) {
-  if (!s || !W || !loss) return fail(s, MIDAGMA_E_ARG, "score: null argument");
-  if (s->mode != MIDAGMA_MODE_COV || !s->has_cov) return fail(s, MIDAGMA_E_STATE, "score: cov mode with set_cov");
-  return guarded(s, [&] {
+  if (!s || !W || !loss) return abi_fail(s, MIDAGMA_E_ARG, "score: null argument");
+  if (s->mode != MIDAGMA_MODE_COV || !s->has_cov) return abi_fail(s, MIDAGMA_E_STATE, "score: cov mode with set_cov");
+  return abi_guarded(s, [&] {
     const int64_t D = s->D, d = s->d, DD = D * D;
     s->scratch.alloc(DD);
     HIP_TRY(hipMemsetAsync(s->scratch.p, 0, DD * sizeof(double), s->stream));
@@ -907,8 +809,8 @@ int midagma_score(midagma_solver* s, const double* W, double* loss, double* G) {
 
 int midagma_score_partial(midagma_solver* s, const double* W) {
   if (!s || !W || s->mode != MIDAGMA_MODE_DATA || !s->has_data)
-    return fail(s, MIDAGMA_E_STATE, "score_partial: data mode with set_data");
-  return guarded(s, [&] {
+    return abi_fail(s, MIDAGMA_E_STATE, "score_partial: data mode with set_data");
+  return abi_guarded(s, [&] {
     const int64_t DD = s->D * s->D;
     s->scratch.alloc(DD);
     HIP_TRY(hipMemsetAsync(s->scratch.p, 0, DD * sizeof(double), s->stream));
@@ -922,8 +824,8 @@ int midagma_score_partial(midagma_solver* s, const double* W) {
 }
 
 int midagma_score_finish(midagma_solver* s, double* loss, double* G) {
-  if (!s || !loss || s->mode != MIDAGMA_MODE_DATA) return fail(s, MIDAGMA_E_STATE, "score_finish: data mode");
-  return guarded(s, [&] {
+  if (!s || !loss || s->mode != MIDAGMA_MODE_DATA) return abi_fail(s, MIDAGMA_E_STATE, "score_finish: data mode");
+  return abi_guarded(s, [&] {
     const int64_t D = s->D, d = s->d, DD = D * D;
     const double n = (double)s->n_global;
     if (s->loss == MIDAGMA_LOSS_L2) {
@@ -955,552 +857,6 @@ int midagma_score_finish(midagma_solver* s, double* loss, double* G) {
 }
 
 }  // extern "C"
-
-// ---- device-pointer log-det / inverse for torch (DagmaMLP.h_func) ------------
-namespace {
-struct LogdetWorkspace {
-  int device = -1;
-  int64_t D = 0;
-  DevBuf<> A, P, R, C, piv;
-};
-std::mutex g_ws_mu;
-// The per-device cache, kept for the life of the process.  Pointers that are never deleted, on
-// purpose: an owning object with static storage would free its buffers from a static destructor,
-// when the HIP runtime may already be gone (devmem.h).
-std::vector<LogdetWorkspace*> g_ws;
-}  // namespace
-
-// the workspace of padded size D for the current device, created on first use (g_ws_mu held)
-static LogdetWorkspace* logdet_ws(int64_t D) {
-  int dev = 0;
-  HIP_TRY(hipGetDevice(&dev));
-  for (auto* w : g_ws)
-    if (w->device == dev && w->D == D) return w;
-  LogdetWorkspace* ws = new LogdetWorkspace();
-  ws->device = dev;
-  ws->D = D;
-  ws->A.alloc((size_t)D * D);
-  ws->P.alloc(64 * 64);
-  ws->R.alloc((size_t)64 * D);
-  ws->C.alloc((size_t)D * 64);
-  ws->piv.alloc(D);
-  g_ws.push_back(ws);
-  return ws;
-}
-
-// the h log-det's: 32-padded, the 32-block Gauss-Jordan's own granularity
-static LogdetWorkspace* logdet_h_ws(int64_t d) {
-  std::lock_guard<std::mutex> lock(g_ws_mu);
-  return logdet_ws((d + 31) / 32 * 32);
-}
-
-// part 0: build + the Gauss-Jordan prologue; parts 1 .. D/32: its block steps; part D/32 + 1: the
-// epilogue (h and (sI - A)^-T).  part < 0: all of them.
-static void logdet_h_enqueue(const double* A, int64_t d, int64_t lda, double s, double* h_dev, double* Mt_dev,
-                             int64_t ldm, hipStream_t st, int part) {
-  setup_attributes_once();
-  LogdetWorkspace* ws = logdet_h_ws(d);
-  const int64_t D = ws->D;
-  const int K = (int)(D / 32);
-  const GJWork w{ws->P.p, ws->R.p, ws->C.p, ws->piv.p};
-  if (part < 0 || part == 0) {
-    launch_build_at(A, lda, false, ws->A.p, D, d, s, nullptr, nullptr, st);
-    launch_gj_prologue(ws->A.p, D, D, w, nullptr, st);
-  }
-  for (int k = 0; k < K; ++k)
-    if (part < 0 || part == k + 1) launch_gj_step(ws->A.p, D, D, w, nullptr, k, st);
-  if (part < 0 || part == K + 1)
-    launch_logdet_post(ws->piv.p, d, (double)d * std::log(s), h_dev, ws->A.p, D, Mt_dev, ldm, st);
-}
-
-extern "C" int midagma_logdet_h_dev(const double* A, int64_t d, int64_t lda, double s, double* h_dev, double* Mt_dev,
-                                    int64_t ldm, void* stream) {
-  if (!A || !h_dev || d < 1 || lda < d || !(s > 0.0) || (Mt_dev && ldm < d))
-    return fail(nullptr, MIDAGMA_E_ARG, "logdet_h_dev: bad arguments");
-  return guarded(nullptr, [&] {
-    logdet_h_enqueue(A, d, lda, s, h_dev, Mt_dev, ldm, reinterpret_cast<hipStream_t>(stream), -1);
-    return MIDAGMA_OK;
-  });
-}
-
-extern "C" int64_t midagma_logdet_h_parts(int64_t d) { return d < 1 ? 0 : (d + 31) / 32 + 2; }
-
-// ---- the h log-det's warm-started fast path (ABI 6; mlp.hip) -------------------------------------
-struct midagma_ldfast {
-  int device = 0;
-  int64_t d = 0, Dgj = 0;  // Gauss-Jordan workspace: 32-padded, as midagma_logdet_h_dev
-  int B = 0;               // series block: 128 or 256 (0: d > 256, every step exact)
-  DevBuf<> ring0, ring1, Y0, Y1, Q0, Q1, P, part, done, hlast;
-  DevBuf<> A, Pgj, Rgj, Cgj, piv;
-  DevBuf<State> st;    // the ring's state (slots: step index; warm_run; status of the series)
-  DevBuf<State> gjst;  // the Gauss-Jordan gate of a fast step (ST_RUNNING: run the chain)
-  int64_t* counter = nullptr;  // advanced by a fast step's end (midagma_ldfast_set_counter)
-  std::string err;
-  GJWork gjw() const { return GJWork{Pgj.p, Rgj.p, Cgj.p, piv.p}; }
-  SeriesWork sw() const {
-    return SeriesWork{ring0.p, ring1.p, {Y0.p, Y1.p}, {Q0.p, Q1.p}, P.p, part.p, reinterpret_cast<int*>(done.p)};
-  }
-};
-
-extern "C" int midagma_ldfast_create(midagma_ldfast** out, int64_t d) {
-  if (!out || d < 1) return fail(nullptr, MIDAGMA_E_ARG, "ldfast_create: bad arguments");
-  auto* h = new midagma_ldfast();
-  int rc = guarded(nullptr, [&] {
-    setup_attributes_once();
-    HIP_TRY(hipGetDevice(&h->device));
-    h->d = d;
-    h->Dgj = (d + 31) / 32 * 32;
-    h->B = d <= 128 ? 128 : (d <= 256 ? 256 : 0);
-    const size_t DD = (size_t)h->Dgj * h->Dgj;
-    h->A.alloc(DD);
-    h->Pgj.alloc(64 * 64);
-    h->Rgj.alloc((size_t)64 * h->Dgj);
-    h->Cgj.alloc((size_t)h->Dgj * 64);
-    h->piv.alloc(h->Dgj);
-    h->hlast.alloc(1);
-    if (h->B) {
-      const size_t BB = (size_t)h->B * h->B;
-      for (DevBuf<>* b : {&h->ring0, &h->ring1, &h->Y0, &h->Y1, &h->Q0, &h->Q1, &h->P}) b->alloc(BB);
-      h->part.alloc((size_t)(NM_PASSES + 1) * PART_STRIDE);
-      h->done.alloc(1);
-    }
-    h->st.alloc(1);
-    h->gjst.alloc(1);
-    return midagma_ldfast_reset(h);
-  });
-  if (rc != MIDAGMA_OK) {
-    delete h;
-    return rc;
-  }
-  *out = h;
-  return MIDAGMA_OK;
-}
-
-extern "C" void midagma_ldfast_destroy(midagma_ldfast* h) {
-  if (!h) return;
-  (void)hipSetDevice(h->device);
-  (void)hipDeviceSynchronize();
-  delete h;
-}
-
-extern "C" int midagma_ldfast_reset(midagma_ldfast* h) {
-  if (!h) return fail(nullptr, MIDAGMA_E_ARG, "ldfast_reset: null handle");
-  return guarded(nullptr, [&] {
-    HIP_TRY(hipSetDevice(h->device));
-    State st{};
-    st.status = ST_RUNNING;
-    st.slots = -1;        // step 0: opened by ldfast_begin (exact) or counted by the fast step's end
-    st.ckpt_pending = 1;  // no warm start: the first step runs the Gauss-Jordan chain
-    State gj{};
-    gj.status = ST_DONE;
-    HIP_TRY(hipMemcpy(h->st.p, &st, sizeof(State), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(h->gjst.p, &gj, sizeof(State), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemset(h->hlast.p, 0, sizeof(double)));
-    if (h->done.p) HIP_TRY(hipMemset(h->done.p, 0, sizeof(double)));
-    return MIDAGMA_OK;
-  });
-}
-
-// fast: 0 the series residual (opening the step), 1 .. 3 the passes, 4 certificate + the gated
-// chain with the step's end; exact: 0 begin + build + prologue, 1 .. Dgj/32 the block steps, last
-// the end
-static constexpr int kLdfastPasses = 3;
-extern "C" int64_t midagma_ldfast_parts(const midagma_ldfast* h, int exact) {
-  if (!h) return 0;
-  return (exact || !h->B) ? h->Dgj / 32 + 2 : kLdfastPasses + 2;
-}
-
-extern "C" int midagma_ldfast_enqueue(midagma_ldfast* h, const double* A, int64_t d_in, int64_t lda, double s,
-                                      double* h_dev, double* Mt_dev, int64_t ldm, void* stream, int exact, int64_t part) {
-  if (!h || d_in != h->d)  // the handle's buffers and warm-start ring are sized for its d
-    return fail(nullptr, MIDAGMA_E_ARG, "ldfast_enqueue: A's d differs from the handle's");
-  if (!A || !h_dev || !Mt_dev || lda < h->d || ldm < h->d || !(s > 0.0) || part >= midagma_ldfast_parts(h, exact))
-    return fail(nullptr, MIDAGMA_E_ARG, "ldfast_enqueue: bad arguments");
-  return guarded(nullptr, [&] {
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    const int64_t d = h->d, D = h->Dgj;
-    const int K = (int)(D / 32);
-    const double dls = (double)d * std::log(s);
-    const bool ex = exact || !h->B;
-    auto want = [&](int64_t p) { return part < 0 || part == p; };
-    if (ex) {  // the Gauss-Jordan chain, ungated
-      if (want(0)) {
-        launch_ldfast_begin(h->st.p, h->gjst.p, st);
-        launch_build_at(A, lda, false, h->A.p, D, d, s, nullptr, nullptr, st);
-        launch_gj_prologue(h->A.p, D, D, h->gjw(), nullptr, st);
-      }
-      for (int k = 0; k < K; ++k)
-        if (want(k + 1)) launch_gj_step(h->A.p, D, D, h->gjw(), nullptr, k, st);
-      if (want(K + 1))
-        launch_ldfast_post(h->piv.p, d, dls, h_dev, h->A.p, D, Mt_dev, ldm, h->P.p, h->B, h->ring0.p, h->ring1.p,
-                           h->st.p, h->gjst.p, h->hlast.p, true, st);
-      return MIDAGMA_OK;
-    }
-    const SeriesWork w = h->sw();
-    if (want(0)) launch_ldfast_resid(A, lda, d, s, h->B, w, h->st.p, h->gjst.p, st);
-    // the passes one by one (each its own part: the caller interleaves them)
-    for (int p = 1; p <= kLdfastPasses; ++p)
-      if (want(p)) launch_series_pass(h->B, w, h->st.p, p, st);
-    if (want(kLdfastPasses + 1)) {
-      launch_ldfast_certify(h->P.p, h->B, d, Mt_dev, ldm, h->st.p, reinterpret_cast<const int*>(h->done.p), h->gjst.p,
-                            h->ring0.p, h->ring1.p, st);
-      // gated: opened by the certificate.  One launch, the whole Gauss-Jordan chain in one
-      // workgroup (bit-identical; slow when open, which the bench window never is): a closed gate
-      // costs one launch instead of the chain's 2 + D/32, and that launch also ends the step
-      // (ldfast_post's fast-step work in the same workgroup: one dependent launch fewer)
-      const LdfastEnd end{h->piv.p, d, dls, h_dev, Mt_dev, ldm, h->B, h->ring0.p, h->ring1.p, h->st.p, h->hlast.p,
-                          h->counter};
-      launch_gj_inverse_1wg(A, lda, h->A.p, D, d, s, h->gjw(), h->gjst.p, st, end);
-    }
-    return MIDAGMA_OK;
-  });
-}
-
-extern "C" int midagma_ldfast_set_counter(midagma_ldfast* h, int64_t* counter) {
-  if (!h) return fail(nullptr, MIDAGMA_E_ARG, "ldfast_set_counter: null handle");
-  // a handle without the fast path (d > 256: every step runs the Gauss-Jordan chain, which never
-  // advances the counter) cannot honour the contract: refuse instead of stalling the caller's table
-  if (counter && !h->B) return fail(nullptr, MIDAGMA_E_ARG, "ldfast_set_counter: the handle has no fast path (d > 256)");
-  h->counter = counter;
-  return MIDAGMA_OK;
-}
-
-extern "C" int midagma_ldfast_stats(midagma_ldfast* h, int64_t* steps, int64_t* exact_steps) {
-  if (!h) return fail(nullptr, MIDAGMA_E_ARG, "ldfast_stats: null handle");
-  return guarded(nullptr, [&] {
-    HIP_TRY(hipSetDevice(h->device));
-    HIP_TRY(hipDeviceSynchronize());
-    State st{};
-    HIP_TRY(hipMemcpy(&st, h->st.p, sizeof(State), hipMemcpyDeviceToHost));
-    if (steps) *steps = st.iter;
-    if (exact_steps) *exact_steps = st.halvings;
-    return MIDAGMA_OK;
-  });
-}
-
-extern "C" int midagma_logdet_h_dev_part(const double* A, int64_t d, int64_t lda, double s, double* h_dev,
-                                         double* Mt_dev, int64_t ldm, void* stream, int64_t part) {
-  if (!A || !h_dev || d < 1 || lda < d || !(s > 0.0) || (Mt_dev && ldm < d) || part < 0 ||
-      part >= midagma_logdet_h_parts(d))
-    return fail(nullptr, MIDAGMA_E_ARG, "logdet_h_dev_part: bad arguments");
-  return guarded(nullptr, [&] {
-    logdet_h_enqueue(A, d, lda, s, h_dev, Mt_dev, ldm, reinterpret_cast<hipStream_t>(stream), (int)part);
-    return MIDAGMA_OK;
-  });
-}
-
-extern "C" int midagma_logdet_inv_dev(const double* A, int64_t d, int64_t lda, double s_dom, double* logdet_dev,
-                                      double* Mt_dev, int64_t ldm, void* stream) {
-  if (!A || d < 1 || lda < d || (Mt_dev && ldm < d))
-    return fail(nullptr, MIDAGMA_E_ARG, "logdet_inv_dev: bad arguments");
-  return guarded(nullptr, [&] {
-    setup_attributes_once();
-    const int64_t D = round_up64(d);
-    std::lock_guard<std::mutex> lock(g_ws_mu);
-    LogdetWorkspace* ws = logdet_ws(D);
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    launch_build_at(A, lda, false, ws->A.p, D, d, s_dom, nullptr, nullptr, st);
-    launch_gj_inverse(ws->A.p, D, D, GJWork{ws->P.p, ws->R.p, ws->C.p, ws->piv.p}, nullptr, st);
-    if (logdet_dev) launch_sum_vector(ws->piv.p, d, logdet_dev, nullptr, st);
-    if (Mt_dev)
-      HIP_TRY(hipMemcpy2DAsync(Mt_dev, ldm * sizeof(double), ws->A.p, D * sizeof(double), d * sizeof(double), d,
-                               hipMemcpyDeviceToDevice, st));
-    return MIDAGMA_OK;
-  });
-}
-
-// ---------------------------------------------------------------------------
-// Linear-SEM generator (sem.hip; utils.py:99-172)
-extern "C" int midagma_sem_linear(const double* W, int64_t d, int64_t row0, int64_t n_rows, int sem_type,
-                                  const double* noise_scale, uint64_t seed, double* X_dev, int64_t ldx,
-                                  void* stream) {
-  if (!W || d < 1 || d > (1 << 30)) return fail(nullptr, MIDAGMA_E_ARG, "sem_linear: bad W / d");
-  SemGraph g;
-  if (!sem_levels(W, d, g)) return fail(nullptr, MIDAGMA_E_ARG, "sem_linear: W must be a DAG");
-  if (row0 < 0 || n_rows < 0 || ldx < d || sem_type < 0 || sem_type > 5 || (n_rows > 0 && !X_dev))
-    return fail(nullptr, MIDAGMA_E_ARG, "sem_linear: bad arguments");
-  if (n_rows == 0) return MIDAGMA_OK;
-  return guarded(nullptr, [&] {
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    std::vector<double> scale(d, 1.0);
-    if (noise_scale) std::copy(noise_scale, noise_scale + d, scale.begin());
-    // slab: rows of the node-major scratch, even, ~MIDAGMA_SEM_SLAB_MB (default 2048) MB
-    int64_t budget = 2048;
-    if (const char* e = getenv("MIDAGMA_SEM_SLAB_MB")) budget = std::max<int64_t>(1, atoll(e));
-    const int64_t first = row0 & ~int64_t(1), end = row0 + n_rows;
-    int64_t S = std::max<int64_t>(1024, (budget << 20) / (8 * d));
-    S = std::min<int64_t>(S, (end - first + 1) & ~int64_t(1));
-    S = (S + 1) & ~int64_t(1);
-    const size_t nnz = g.pidx.size();
-    DevBuf<int32_t> ints;
-    DevBuf<double> dbls, xt;
-    ints.alloc(g.nodes.size() + g.pptr.size() + std::max<size_t>(nnz, 1));
-    dbls.alloc(std::max<size_t>(nnz, 1) + d);
-    xt.alloc(static_cast<size_t>(S) * d);
-    int32_t* ip = ints.p;
-    double* dp = dbls.p;
-    SemDev dev{ip, ip + g.nodes.size(), ip + g.nodes.size() + g.pptr.size(), dp, dp + std::max<size_t>(nnz, 1)};
-    HIP_TRY(hipMemcpyAsync(ip, g.nodes.data(), g.nodes.size() * sizeof(int32_t), hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(ip + g.nodes.size(), g.pptr.data(), g.pptr.size() * sizeof(int32_t),
-                           hipMemcpyHostToDevice, st));
-    if (nnz) {
-      HIP_TRY(hipMemcpyAsync(const_cast<int32_t*>(dev.pidx), g.pidx.data(), nnz * sizeof(int32_t),
-                             hipMemcpyHostToDevice, st));
-      HIP_TRY(hipMemcpyAsync(dp, g.pw.data(), nnz * sizeof(double), hipMemcpyHostToDevice, st));
-    }
-    HIP_TRY(hipMemcpyAsync(const_cast<double*>(dev.scale), scale.data(), d * sizeof(double), hipMemcpyHostToDevice,
-                           st));
-    for (int64_t a = first; a < end; a += S) {
-      const int64_t rows = std::min<int64_t>(S, end - a);
-      const int64_t skip = a < row0 ? row0 - a : 0;
-      launch_sem_slab(dev, g.level_off, d, sem_type, seed, a, rows, skip, xt.p, S,
-                      X_dev + (a + skip - row0) * ldx, ldx, st);
-    }
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipStreamSynchronize(st));  // the scratch is freed on return
-    return MIDAGMA_OK;
-  });
-}
-
-// ---------------------------------------------------------------------------
-// Gated Adam step (adam.hip) for DagmaNonlinear on torch tensors
-extern "C" int64_t midagma_mlp_tail_scratch(int64_t n, int64_t d, int64_t m1) {
-  if (n < 1 || d < 1 || m1 < 1) return 0;
-  return mlp_tail_scratch(n, d, m1);
-}
-
-extern "C" int midagma_mlp_tail_fwd(const double* Z, const double* b1, const double* w2, const double* b2,
-                                    const double* X, int64_t n, int64_t d, int64_t m1, double* R, double* scratch,
-                                    double* ssq, void* stream) {
-  if (!Z || !w2 || !b2 || !X || !R || !scratch || !ssq || n < 1 || d < 1 || m1 < 1 || d * m1 > MLP_TAIL_MAX_DM)
-    return fail(nullptr, MIDAGMA_E_ARG, "mlp_tail_fwd: bad arguments");
-  return guarded(nullptr, [&] {
-    launch_mlp_tail_fwd(Z, b1, w2, b2, X, n, d, (int)m1, R, scratch, ssq, reinterpret_cast<hipStream_t>(stream));
-    return MIDAGMA_OK;
-  });
-}
-
-extern "C" int midagma_mlp_tail_bwd(const double* Z, const double* b1, const double* w2, const double* R,
-                                    const double* g, int64_t n, int64_t d, int64_t m1, double* dZ, double* dw2,
-                                    double* db2, double* db1, double* scratch, void* stream) {
-  if (!Z || !w2 || !R || !g || !dZ || !dw2 || !db2 || !scratch || n < 1 || d < 1 || m1 < 1 ||
-      d * m1 > MLP_TAIL_MAX_DM)
-    return fail(nullptr, MIDAGMA_E_ARG, "mlp_tail_bwd: bad arguments");
-  return guarded(nullptr, [&] {
-    launch_mlp_tail_bwd(Z, b1, w2, R, g, n, d, (int)m1, dZ, dw2, db2, db1, scratch,
-                        reinterpret_cast<hipStream_t>(stream));
-    return MIDAGMA_OK;
-  });
-}
-
-extern "C" int64_t midagma_fc1_terms_parts(int64_t d) { return d < 1 ? 0 : fc1_terms_parts(d); }
-
-extern "C" int midagma_fc1_terms(const double* W1, int64_t d, int64_t m1, double* A, double* l1part, void* stream) {
-  if (!W1 || !A || !l1part || d < 1 || m1 < 1) return fail(nullptr, MIDAGMA_E_ARG, "fc1_terms: bad arguments");
-  return guarded(nullptr, [&] {
-    launch_fc1_terms(W1, d, (int)m1, A, l1part, reinterpret_cast<hipStream_t>(stream));
-    return MIDAGMA_OK;
-  });
-}
-
-extern "C" int midagma_fc1_terms_bwd(const double* W1, int64_t d, int64_t m1, const double* gA, const double* gscale,
-                                     const double* gl1part, const double* lin, int64_t nlin, double* dW1,
-                                     void* stream) {
-  if (!W1 || !gA || !gl1part || !dW1 || d < 1 || m1 < 1 || nlin < 0 || (nlin > 0 && !lin))
-    return fail(nullptr, MIDAGMA_E_ARG, "fc1_terms_bwd: bad arguments");
-  return guarded(nullptr, [&] {
-    launch_fc1_terms_bwd(W1, d, (int)m1, gA, gscale, gl1part, lin, (int)nlin, dW1,
-                         reinterpret_cast<hipStream_t>(stream));
-    return MIDAGMA_OK;
-  });
-}
-
-extern "C" int midagma_mlp_objective(const double* ssq, const double* l1part, int64_t np, const double* h, double mu,
-                                     double lambda1, double half_d, double inv_n, double* obj, void* stream) {
-  if (!ssq || !l1part || !h || !obj || np < 1) return fail(nullptr, MIDAGMA_E_ARG, "mlp_objective: bad arguments");
-  return guarded(nullptr, [&] {
-    launch_mlp_objective(ssq, l1part, np, h, mu, lambda1, half_d, inv_n, obj, reinterpret_cast<hipStream_t>(stream));
-    return MIDAGMA_OK;
-  });
-}
-
-extern "C" int midagma_mlp_objective_bwd(const double* g, const double* ssq, int64_t np, double mu, double lambda1,
-                                         double half_d, double inv_n, double* gssq, double* gl1part, double* gh,
-                                         void* stream) {
-  if (!g || (!ssq) != (!gssq) || !gl1part || !gh || np < 1)
-    return fail(nullptr, MIDAGMA_E_ARG, "mlp_objective_bwd: bad arguments");
-  return guarded(nullptr, [&] {
-    launch_mlp_objective_bwd(g, ssq, np, mu, lambda1, half_d, inv_n, gssq, gl1part, gh,
-                             reinterpret_cast<hipStream_t>(stream));
-    return MIDAGMA_OK;
-  });
-}
-
-// ABI 6: the [d, m1, 1] objective's step with the scalar objective's backward folded into its
-// consumers (no mlp_sum / mlp_objective_bwd launches): the tail forward leaves its n row partials,
-// the objective sums them (and advances the Adam table counter), the tail backward and the fc1
-// terms' backward derive d obj / d ssq, d h and d l1 from gobj themselves.  Bit-identical to the
-// ABI-5 sequence (the same sums in the same order, the same scalar arithmetic).
-extern "C" int midagma_mlp_tail_fwd_part(const double* Z, const double* b1, const double* w2, const double* b2,
-                                         const double* X, int64_t n, int64_t d, int64_t m1, double* R, double* part,
-                                         void* stream) {
-  if (!Z || !w2 || !b2 || !X || !R || !part || n < 1 || d < 1 || m1 < 1 || d * m1 > MLP_TAIL_MAX_DM)
-    return fail(nullptr, MIDAGMA_E_ARG, "mlp_tail_fwd_part: bad arguments");
-  return guarded(nullptr, [&] {
-    launch_mlp_tail_fwd(Z, b1, w2, b2, X, n, d, (int)m1, R, part, nullptr, reinterpret_cast<hipStream_t>(stream));
-    return MIDAGMA_OK;
-  });
-}
-
-extern "C" int midagma_mlp_tail_bwd_obj(const double* Z, const double* b1, const double* w2, const double* R,
-                                        const double* part, const double* gobj, double mu, double half_d,
-                                        double inv_n, int64_t n, int64_t d, int64_t m1, double* dZ, double* dw2,
-                                        double* db2, double* db1, double* scratch, void* stream) {
-  // (ABI 9: dw2 = db2 = db1 = NULL leaves the chunk partials in scratch for midagma_mlp_step)
-  const bool sums = dw2 || db2 || db1;
-  if (!Z || !w2 || !R || !part || !gobj || !dZ || (sums && (!dw2 || !db2)) || !scratch || n < 1 || d < 1 ||
-      m1 < 1 || d * m1 > MLP_TAIL_MAX_DM)
-    return fail(nullptr, MIDAGMA_E_ARG, "mlp_tail_bwd_obj: bad arguments");
-  return guarded(nullptr, [&] {
-    launch_mlp_tail_bwd(Z, b1, w2, R, nullptr, n, d, (int)m1, dZ, dw2, db2, db1, scratch,
-                        reinterpret_cast<hipStream_t>(stream), part, gobj, mu, half_d, inv_n, sums);
-    return MIDAGMA_OK;
-  });
-}
-
-extern "C" int midagma_mlp_step(double* const* params, double* const* exp_avg, double* const* exp_avg_sq, int64_t n,
-                                int64_t d, int64_t m1, const double* gA, const double* gobj, double mu,
-                                double lambda1, const double* lin, int64_t nlin, const double* scratch,
-                                const double* table, const int64_t* counter, double w1, double beta2, double c2,
-                                double eps, double wd, const double* gate, double* A, double* l1part, void* stream) {
-  if (!params || !exp_avg || !exp_avg_sq || !gA || !gobj || !scratch || !table || !counter || !A || !l1part ||
-      n < 1 || d < 1 || m1 < 1 || d * m1 > MLP_TAIL_MAX_DM || nlin < 0 || (nlin > 0 && !lin))
-    return fail(nullptr, MIDAGMA_E_ARG, "mlp_step: bad arguments");
-  for (int q = 0; q < 4; ++q)
-    if (!params[q] || !exp_avg[q] || !exp_avg_sq[q]) return fail(nullptr, MIDAGMA_E_ARG, "mlp_step: bad tensor");
-  const MlpStepPtrs p{params[0], params[1], params[2], params[3], exp_avg[0], exp_avg_sq[0], exp_avg[1],
-                      exp_avg_sq[1], exp_avg[2], exp_avg_sq[2], exp_avg[3], exp_avg_sq[3]};
-  return guarded(nullptr, [&] {
-    launch_mlp_step(p, n, d, (int)m1, gA, gobj, mu, lambda1, lin, (int)nlin, scratch, table, counter, w1, beta2, c2,
-                    eps, wd, gate, A, l1part, reinterpret_cast<hipStream_t>(stream));
-    return MIDAGMA_OK;
-  });
-}
-
-#ifdef MIDAGMA_EXPERIMENTS
-// fc1 and the tail fused on the MFMA (mlp.hip; measured slower at config 5):
-// not in the public header, bound by nonlinear.py when the loaded library has them
-extern "C" int64_t midagma_mlp_fused_parts(int64_t n, int64_t d, int64_t m1) { return mlp_fused_parts(n, d, m1); }
-
-extern "C" int64_t midagma_mlp_fused_splits(int64_t n) { return n < 1 ? 0 : mlp_fused_splits(n); }
-
-extern "C" int midagma_mlp_fc1_tail_fwd(const double* X, const double* W1, const double* b1, const double* w2,
-                                        const double* b2, int64_t n, int64_t d, int64_t m1, double* S, double* R,
-                                        double* part, void* stream) {
-  if (!X || !W1 || !w2 || !b2 || !S || !R || !part || mlp_fused_parts(n, d, m1) < 1)
-    return fail(nullptr, MIDAGMA_E_ARG, "mlp_fc1_tail_fwd: bad arguments");
-  return guarded(nullptr, [&] {
-    launch_mlp_fc1_tail_fwd(X, W1, b1, w2, b2, n, d, (int)m1, S, R, part, reinterpret_cast<hipStream_t>(stream));
-    return MIDAGMA_OK;
-  });
-}
-
-extern "C" int midagma_mlp_tail_bwd_lin(const double* S, const double* w2, const double* R, const double* X,
-                                        const double* part, int64_t npart, const double* gobj, double mu,
-                                        double half_d, double inv_n, int64_t n, int64_t d, int64_t m1, double* lin,
-                                        double* dw2, double* db2, double* db1, double* scratch, void* stream) {
-  if (!S || !w2 || !R || !X || !part || npart < 1 || !gobj || !lin || !dw2 || !db2 || !scratch ||
-      mlp_fused_parts(n, d, m1) < 1)
-    return fail(nullptr, MIDAGMA_E_ARG, "mlp_tail_bwd_lin: bad arguments");
-  return guarded(nullptr, [&] {
-    launch_mlp_tail_bwd_lin(S, w2, R, X, part, npart, gobj, mu, half_d, inv_n, n, d, (int)m1, lin, dw2, db2, db1,
-                            scratch, reinterpret_cast<hipStream_t>(stream));
-    return MIDAGMA_OK;
-  });
-}
-#endif
-
-extern "C" int midagma_fc1_terms_bwd_obj(const double* W1, int64_t d, int64_t m1, const double* gA, const double* gobj,
-                                         double mu, double lambda1, const double* lin, int64_t nlin, double* dW1,
-                                         void* stream) {
-  if (!W1 || !gA || !gobj || !dW1 || d < 1 || m1 < 1 || nlin < 0 || (nlin > 0 && !lin))
-    return fail(nullptr, MIDAGMA_E_ARG, "fc1_terms_bwd_obj: bad arguments");
-  return guarded(nullptr, [&] {
-    launch_fc1_terms_bwd(W1, d, (int)m1, gA, nullptr, nullptr, lin, (int)nlin, dW1,
-                         reinterpret_cast<hipStream_t>(stream), gobj, mu, lambda1);
-    return MIDAGMA_OK;
-  });
-}
-
-extern "C" int midagma_mlp_objective_part(const double* part, int64_t npart, const double* l1part, int64_t np,
-                                          const double* h, double mu, double lambda1, double half_d, double inv_n,
-                                          double* obj, int64_t* counter, void* stream) {
-  if (!part || npart < 1 || !l1part || !h || !obj || np < 1)
-    return fail(nullptr, MIDAGMA_E_ARG, "mlp_objective_part: bad arguments");
-  return guarded(nullptr, [&] {
-    launch_mlp_objective(nullptr, l1part, np, h, mu, lambda1, half_d, inv_n, obj,
-                         reinterpret_cast<hipStream_t>(stream), part, npart, counter);
-    return MIDAGMA_OK;
-  });
-}
-
-extern "C" int midagma_adam_step(double* p, const double* g, double* m, double* v, int64_t n, double step_size,
-                                 double w1, double beta2, double c2, double bc2_sqrt, double eps, double wd,
-                                 const double* gate, void* stream) {
-  if (!p || !g || !m || !v || n < 0) return fail(nullptr, MIDAGMA_E_ARG, "adam_step: bad arguments");
-  if (n == 0) return MIDAGMA_OK;
-  return guarded(nullptr, [&] {
-    launch_adam_gated(p, g, m, v, n, AdamCoef{step_size, w1, beta2, c2, bc2_sqrt, eps, wd}, gate,
-                      reinterpret_cast<hipStream_t>(stream));
-    return MIDAGMA_OK;
-  });
-}
-
-extern "C" int midagma_adam_step_table(double* p, const double* g, double* m, double* v, int64_t n,
-                                       const double* table, const int64_t* counter, double w1, double beta2,
-                                       double c2, double eps, double wd, const double* gate, void* stream) {
-  if (!p || !g || !m || !v || !table || !counter || n < 0) return fail(nullptr, MIDAGMA_E_ARG, "adam_step_table: bad arguments");
-  if (n == 0) return MIDAGMA_OK;
-  return guarded(nullptr, [&] {
-    launch_adam_gated_table(p, g, m, v, n, AdamCoef{0.0, w1, beta2, c2, 1.0, eps, wd}, table, counter, gate,
-                            reinterpret_cast<hipStream_t>(stream));
-    return MIDAGMA_OK;
-  });
-}
-
-extern "C" int midagma_adam_step_table_multi(int64_t k, double* const* p, const double* const* g, double* const* m,
-                                             double* const* v, const int64_t* n, const double* table,
-                                             const int64_t* counter, double w1, double beta2, double c2, double eps,
-                                             double wd, const double* gate, void* stream) {
-  if (k < 1 || k > ADAM_MULTI || !p || !g || !m || !v || !n || !table || !counter)
-    return fail(nullptr, MIDAGMA_E_ARG, "adam_step_table_multi: bad arguments");
-  AdamSet set{};
-  set.k = (int)k;
-  set.off[0] = 0;
-  for (int64_t q = 0; q < k; ++q) {
-    if (!p[q] || !g[q] || !m[q] || !v[q] || n[q] < 0)
-      return fail(nullptr, MIDAGMA_E_ARG, "adam_step_table_multi: bad tensor");
-    set.p[q] = p[q];
-    set.g[q] = g[q];
-    set.m[q] = m[q];
-    set.v[q] = v[q];
-    set.off[q + 1] = set.off[q] + n[q];
-  }
-  if (set.off[k] == 0) return MIDAGMA_OK;
-  return guarded(nullptr, [&] {
-    launch_adam_gated_table_multi(set, AdamCoef{0.0, w1, beta2, c2, 1.0, eps, wd}, table, counter, gate,
-                                  reinterpret_cast<hipStream_t>(stream));
-    return MIDAGMA_OK;
-  });
-}
-
-extern "C" int midagma_counter_advance(int64_t* counter, void* stream) {
-  if (!counter) return fail(nullptr, MIDAGMA_E_ARG, "counter_advance: null counter");
-  return guarded(nullptr, [&] {
-    launch_counter_advance(counter, reinterpret_cast<hipStream_t>(stream));
-    return MIDAGMA_OK;
-  });
-}
 
 #ifdef MIDAGMA_EXPERIMENTS
 // Diagnostics (not part of the ABI header): the one-launch inverse's task plan for D, passes

@@ -54,7 +54,7 @@ from typing import Iterable, List, Literal, Optional, Tuple
 
 import numpy as np
 
-from .solver import HipDcor, HipIndep, is_device_tensor
+from .solver import HipDcor, HipIndep, _device_x, _host_x, is_device_tensor
 
 __all__ = ["IndepTestResult", "hsic_stat", "dcor_stat", "permutation_null", "test_pairwise_independence",
            "get_I_from_full_pairwise_tests", "summarize_I", "median_sigma2", "correlation_tests",
@@ -95,31 +95,13 @@ def _sigma2(x, sigma) -> float:
     return s2 if s2 > 0 else 1.0
 
 
-def _as_data(X):
+def _as_data(X, max_n=HipIndep.MAX_N):
     """A C-contiguous float64 copy (the caller's X is never touched), checked; a device tensor is
-    checked for dtype and shape and returned as it is (the engine only reads it, and checks it for
-    inf and nan on the device)."""
+    checked for dtype and shape and returned with unit column stride (the engine only reads it, and
+    checks it for inf and nan on the device)."""
     if is_device_tensor(X):
-        import torch
-        if X.dtype != torch.float64:
-            raise ValueError("a device X must be a float64 tensor")
-        if X.dim() != 2:
-            raise ValueError("X must be a 2-d array (n samples x d variables)")
-        if X.shape[0] < 2:
-            raise ValueError("need at least 2 samples")
-        if X.shape[0] > HipIndep.MAX_N:
-            raise ValueError(f"at most {HipIndep.MAX_N} samples are supported, got {X.shape[0]}")
-        return X
-    X = np.array(X, dtype=np.float64, order="C", copy=True)
-    if X.ndim != 2:
-        raise ValueError("X must be a 2-d array (n samples x d variables)")
-    if X.shape[0] < 2:
-        raise ValueError("need at least 2 samples")
-    if X.shape[0] > HipIndep.MAX_N:
-        raise ValueError(f"at most {HipIndep.MAX_N} samples are supported, got {X.shape[0]}")
-    if not np.isfinite(X).all():
-        raise ValueError("X holds inf or nan")
-    return X
+        return _device_x(X, "X", max_n)
+    return _host_x(X, "X", max_n, copy=True)
 
 
 def _as_pairs(pairs, d: int) -> np.ndarray:
@@ -424,21 +406,6 @@ def _I_from_pvalues(p: np.ndarray, alpha: float, bonferroni: bool, undirected: b
     return np.stack([i[keep], j[keep]], axis=1).astype(int)
 
 
-def _as_dcor_data(X):
-    """`_as_data` without the cap on n (the engine checks a device X for inf and nan itself)."""
-    if is_device_tensor(X):
-        HipDcor._check_tensor(X)
-        return X
-    X = np.array(X, dtype=np.float64, order="C", copy=True)
-    if X.ndim != 2:
-        raise ValueError("X must be a 2-d array (n samples x d variables)")
-    if X.shape[0] < 2:
-        raise ValueError("need at least 2 samples")
-    if not np.isfinite(X).all():
-        raise ValueError("X holds inf or nan")
-    return X
-
-
 def _dcor_null(eng: HipDcor, pairs: np.ndarray, P: int, seed: int, perms, unbiased: bool, budget_bytes: int,
                return_null: bool, block: int):
     n, m = eng.n, len(pairs)
@@ -472,7 +439,7 @@ def dcor_null(X, pairs, *, num_perm: int = 200, seed: int = 0, perms="numpy", un
     block: the block edge (0: the rule; tests); results do not depend on the budget."""
     if isinstance(perms, str) and perms not in ("numpy", "device"):
         raise ValueError("perms must be 'numpy', 'device' or an int32 array (m, num_perm, n)")
-    X = _as_dcor_data(X)
+    X = _as_data(X, max_n=None)
     n, d = int(X.shape[0]), int(X.shape[1])
     pairs = _as_pairs(pairs, d)
     P = int(num_perm)
@@ -507,7 +474,7 @@ def dcor_tests(X, *, pvalue: str = "permutation", num_perm: int = 200, seed: int
         raise ValueError("pvalue must be 'permutation' or 'chi2'")
     if isinstance(perms, str) and perms not in ("numpy", "device"):
         raise ValueError("perms must be 'numpy' or 'device'")
-    X = _as_dcor_data(X)
+    X = _as_data(X, max_n=None)
     n, d = int(X.shape[0]), int(X.shape[1])
     if pvalue == "chi2" and n < 4:
         raise ValueError("the chi-square test needs n >= 4")

@@ -115,37 +115,57 @@ def gram(X, device: int | None = None):
     return G
 
 
+def _check_shape(shape, what: str, max_n):
+    if len(shape) != 2:
+        raise ValueError(f"{what}: X must be 2-d (n samples x d variables)")
+    n, d = int(shape[0]), int(shape[1])
+    if max_n is not None and not 2 <= n <= max_n:
+        raise ValueError(f"{what}: need 2 <= n <= {max_n} samples, got {n}")
+    if n < 2 or d < 1:
+        raise ValueError(f"{what}: need at least 2 samples and 1 variable")
+
+
+def _device_x(X, what: str, max_n: int | None = None):
+    """A device X checked (a 2-d float64 tensor, n >= 2 samples, at most max_n, of d >= 1 variables)
+    and returned with unit column stride: as it is, anything else through `.contiguous()`.  The
+    library looks for inf and nan on the device."""
+    import torch
+    if X.dtype != torch.float64:
+        raise ValueError(f"{what}: a device tensor X must be float64")
+    _check_shape(X.shape, what, max_n)
+    if X.stride(1) != 1 or X.stride(0) < X.shape[1]:
+        X = X.contiguous()
+    return X
+
+
+def _host_x(X, what: str, max_n: int | None = None, copy: bool = False):
+    """A host X as a C-contiguous float64 array (copy=True: always a copy, so the caller's X is
+    never touched; else a view where X already is one), checked as `_device_x` and for inf and nan."""
+    X = np.array(X, dtype=np.float64, order="C", copy=True) if copy else _as_f64(X)
+    _check_shape(X.shape, what, max_n)
+    if not np.isfinite(X).all():
+        raise ValueError(f"{what}: X holds inf or nan")
+    return X
+
+
 def _device_matrix(X, what: str, device=None):
     """X as a 2-d float64 CUDA tensor with unit column stride: a device tensor as it is (checked),
     a host float64 array uploaded with torch (to `device`; None: torch's current device).  No GPU:
     HipSolverError (there is no CPU path)."""
     import torch
     if is_device_tensor(X):
-        if X.dtype != torch.float64:
-            raise ValueError(f"{what}: a device X must be a float64 tensor")
-        if X.dim() != 2:
-            raise ValueError(f"{what}: X must be 2-d (n samples x d variables)")
-        if X.stride(1) != 1 or X.stride(0) < X.shape[1]:
-            X = X.contiguous()
-    else:
-        if hasattr(X, "data_ptr"):  # a host torch tensor
-            X = X.detach().numpy()
-        X = np.asarray(X)
-        if X.dtype != np.float64:
-            raise ValueError(f"{what}: X must be float64, got {X.dtype}")
-        if X.ndim != 2:
-            raise ValueError(f"{what}: X must be 2-d (n samples x d variables)")
-    if int(X.shape[0]) < 2 or int(X.shape[1]) < 1:
-        raise ValueError(f"{what}: need at least 2 samples and 1 variable")
-    if is_device_tensor(X):
-        return X
-    if not np.isfinite(X).all():
-        raise ValueError(f"{what}: X holds inf or nan")
+        return _device_x(X, what)
+    if hasattr(X, "data_ptr"):  # a host torch tensor
+        X = X.detach().numpy()
+    X = np.asarray(X)
+    if X.dtype != np.float64:
+        raise ValueError(f"{what}: X must be float64, got {X.dtype}")
+    X = _host_x(X, what)
     _lib.lib()
     if not torch.cuda.is_available():
         raise _lib.HipSolverError(f"{what}: no GPU (there is no CPU path)")
     dev = torch.device("cuda", torch.cuda.current_device() if device is None else int(device))
-    return torch.from_numpy(np.ascontiguousarray(X)).to(dev)
+    return torch.from_numpy(X).to(dev)
 
 
 def column_ranks(X, budget_bytes: int = 0):
@@ -184,8 +204,34 @@ def correlation(X, *, ranks: bool = False, budget_bytes: int = 0):
     return Rho, const.cpu().numpy().astype(bool)
 
 
-class HipSolver:
+class _Handle:
+    """A handle of one family of the C ABI.  A subclass names the family once (its `*_destroy` and
+    `*_last_error` symbols) and sets self.L and self.h; it inherits close, __del__ and _check."""
+
+    _destroy = _last_error = ""
+    L = h = None
+
+    def _check(self, rc, handle, what):
+        """Raise for a negative rc with the family's message: of `handle`, or (None) the family's
+        last message of this thread raised without one."""
+        return check(rc, handle, what, getattr(self.L, self._last_error))
+
+    def close(self):
+        if self.h:
+            getattr(self.L, self._destroy)(self.h)
+            self.h = None
+
+    def __del__(self):  # pragma: no cover
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class HipSolver(_Handle):
     """Owns device buffers for one d and one score mode on one GPU."""
+
+    _destroy, _last_error = "midagma_destroy", "midagma_last_error"
 
     def __init__(self, d: int, loss: str = "l2", mode: str = "cov", device: int = 0, stream: int | None = None,
                  _handle=None):
@@ -207,16 +253,9 @@ class HipSolver:
         self.D = int(self.L.midagma_padded_dim(self.h))
 
     def close(self):
-        if getattr(self, "h", None):
-            if self._owned:
-                self.L.midagma_destroy(self.h)
+        if not getattr(self, "_owned", True):
             self.h = None
-
-    def __del__(self):  # pragma: no cover
-        try:
-            self.close()
-        except Exception:
-            pass
+        super().close()
 
     @property
     def stream(self) -> int:
@@ -530,7 +569,7 @@ def row_range(n: int, parts: int, k: int):
     return lo, lo + base + (1 if k < extra else 0)
 
 
-class HipGroup:
+class HipGroup(_Handle):
     """Data mode on several devices from ONE process (ABI 11, `midagma_group_*`): member k is a
     data-mode `HipSolver` on devices[k] holding row shard k of X, and every slot sums the members'
     score partials (the Python side stays single-process; the reference's own
@@ -546,9 +585,11 @@ class HipGroup:
     every member and reading results from member 0."""
 
     is_group = True
+    _destroy, _last_error = "midagma_group_destroy", "midagma_group_last_error"
 
     def __init__(self, d: int, loss: str = "l2", devices=(0,), emulate: bool | None = None):
         self.L = _lib.lib()
+        self.members = []
         self.d, self.loss, self.mode = int(d), loss, "data"
         devices = [int(x) for x in devices]
         if not devices:
@@ -558,8 +599,8 @@ class HipGroup:
         lt = {"l2": _lib.LOSS_L2, "logistic": _lib.LOSS_LOGISTIC}[loss]
         arr = (C.c_int * len(devices))(*devices)
         h = C.c_void_p()
-        check(self.L.midagma_group_create(C.byref(h), lt, self.d, arr, len(devices),
-                                          _lib.GROUP_EMULATE if emulate else 0), None, "group_create", group=True)
+        self._check(self.L.midagma_group_create(C.byref(h), lt, self.d, arr, len(devices),
+                                                _lib.GROUP_EMULATE if emulate else 0), None, "group_create")
         self.h = h
         self.devices = devices
         self.device = devices[0]
@@ -568,21 +609,10 @@ class HipGroup:
                         for k, dv in enumerate(devices)]
         self.D = self.members[0].D
 
-    def _check(self, rc, what):
-        return check(rc, self.h, what, group=True)
-
     def close(self):
-        if getattr(self, "h", None):
-            for m in self.members:
-                m.close()
-            self.L.midagma_group_destroy(self.h)
-            self.h = None
-
-    def __del__(self):  # pragma: no cover
-        try:
-            self.close()
-        except Exception:
-            pass
+        for m in self.members:
+            m.close()
+        super().close()
 
     @property
     def size(self) -> int:
@@ -607,7 +637,7 @@ class HipGroup:
                 m.set_data(part, n_global=n)
             return
         X = _as_f64(X)
-        self._check(self.L.midagma_group_set_data(self.h, X.ctypes.data_as(_lib._dp), n), "group_set_data")
+        self._check(self.L.midagma_group_set_data(self.h, X.ctypes.data_as(_lib._dp), n), self.h, "group_set_data")
 
     def set_cov(self, cov):
         for m in self.members:
@@ -638,7 +668,7 @@ class HipGroup:
 
     def allreduce_zbuf(self):
         """Every member's score buffer <- the sum over the members (RCCL, or the emulated sum)."""
-        self._check(self.L.midagma_group_allreduce_zbuf(self.h), "group_allreduce_zbuf")
+        self._check(self.L.midagma_group_allreduce_zbuf(self.h), self.h, "group_allreduce_zbuf")
 
     comm_allreduce_zbuf = allreduce_zbuf
 
@@ -663,7 +693,7 @@ class HipGroup:
         res = _lib.MidagmaResult()
         self._check(self.L.midagma_group_minimize(self.h, dptr(W), float(mu), int(max_iter), float(s), float(lr),
                                                   float(tol), float(beta_1), float(beta_2), float(lambda1),
-                                                  int(checkpoint), C.byref(res)), "group_minimize")
+                                                  int(checkpoint), C.byref(res)), self.h, "group_minimize")
         return MinimizeResult.from_c(res, self.checkpoints() if want_checkpoints else ())
 
     def checkpoints(self):
@@ -689,7 +719,7 @@ class HipGroup:
         return self.score_finish()
 
 
-class HipIndep:
+class HipIndep(_Handle):
     """Pairwise permutation independence tests on one GPU (`midagma_indep_*`, csrc/indep.hip):
     the engine under `midagma_amd.mi_tests`.  Holds a device copy of X (n x d).
 
@@ -700,6 +730,7 @@ class HipIndep:
 
     KINDS = {"hsic": 0, "dcor": 1}
     MAX_N = 16384
+    _destroy, _last_error = "midagma_indep_destroy", "midagma_indep_last_error"
 
     def __init__(self, X, device: int = 0):
         self.L = _lib.lib()
@@ -707,10 +738,10 @@ class HipIndep:
         self.n = self.d = 0
         on_device = is_device_tensor(X)
         if on_device:
-            self._check_tensor(X)
+            X = _device_x(X, "HipIndep", self.MAX_N)
             device = X.device.index
         else:
-            X = self._check_array(X)
+            X = _host_x(X, "HipIndep", self.MAX_N)  # (the library copies it to the device and never writes it)
         h = C.c_void_p()
         self._check(self.L.midagma_indep_create(C.byref(h), int(device)), None, "indep_create")
         self.h = h
@@ -720,62 +751,21 @@ class HipIndep:
             self.close()
             raise
 
-    def _check_tensor(self, X):
-        import torch
-        if X.dtype != torch.float64 or X.dim() != 2:
-            raise ValueError("a device X must be a 2-d float64 tensor (n x d)")
-        if int(X.shape[0]) < 2 or int(X.shape[0]) > self.MAX_N:
-            raise ValueError(f"need 2 <= n <= {self.MAX_N} samples, got {int(X.shape[0])}")
-        if int(X.shape[1]) < 1:
-            raise ValueError("need at least one variable")
-
-    def _check_array(self, X) -> np.ndarray:
-        X = _as_f64(X)  # (the library copies it to the device and never writes it)
-        if X.ndim != 2:
-            raise ValueError("X must be n x d")
-        if X.shape[0] < 2 or X.shape[0] > self.MAX_N:
-            raise ValueError(f"need 2 <= n <= {self.MAX_N} samples, got {X.shape[0]}")
-        if not np.isfinite(X).all():
-            raise ValueError("X holds inf or nan")
-        return X
-
     def set_data(self, X):
         """Replace the engine's data (bandwidths and pre-passes are dropped).  A device tensor must
         live on the engine's device.  When the library rejects a device X (inf or nan), the engine
         holds no data: every later call raises ValueError until a set_data succeeds."""
         self.n = self.d = 0
         if is_device_tensor(X):
-            self._check_tensor(X)
-            if X.stride(1) != 1 or X.stride(0) < X.shape[1]:
-                X = X.contiguous()
+            X = _device_x(X, "HipIndep", self.MAX_N)
             n, d, ld = _rows(X)
             rc = self.L.midagma_indep_set_data_dev(self.h, C.c_void_p(X.data_ptr()), n, d, ld, _cur_stream(X.device))
             self._check(rc, self.h, "indep_set_data_dev")
         else:
-            X = self._check_array(X)
+            X = _host_x(X, "HipIndep", self.MAX_N)
             n, d = int(X.shape[0]), int(X.shape[1])
             self._check(self.L.midagma_indep_set_data(self.h, dptr(X), n, d), self.h, "indep_set_data")
         self.n, self.d = n, d
-
-    def _check(self, rc, handle, what):
-        if rc >= 0:
-            return rc
-        m = self.L.midagma_indep_last_error(handle)
-        msg = m.decode() if m else ""
-        if rc == _lib.E_ARG:
-            raise ValueError(f"{what}: {msg}")
-        raise _lib.HipSolverError(f"{what} failed ({rc}): {msg}")
-
-    def close(self):
-        if getattr(self, "h", None):
-            self.L.midagma_indep_destroy(self.h)
-            self.h = None
-
-    def __del__(self):  # pragma: no cover
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def set_bandwidths(self, sigma2):
         """The RBF kernels' sigma^2 per variable (hsic)."""
@@ -863,7 +853,7 @@ def column_argsort(X, budget_bytes: int = 0):
     return order
 
 
-class HipDcor:
+class HipDcor(_Handle):
     """dCor permutation tests of pairs of columns without the n^2 sum, on one GPU
     (`midagma_dcor_*`, csrc/dcor.hip): the engine under `mi_tests.dcor_null` / `dcor_tests`, for
     2 <= n < 2^31.  Holds the per-column sorts, centred values and row sums of X (24 bytes a value).
@@ -872,16 +862,18 @@ class HipDcor:
     lives on the tensor's device (`device` is ignored), reads X there on torch's current stream
     without a host copy and never writes it.  No synchronise is needed around the call."""
 
+    _destroy, _last_error = "midagma_dcor_destroy", "midagma_dcor_last_error"
+
     def __init__(self, X, device: int = 0, budget_bytes: int = 0):
         self.L = _lib.lib()
         self.h = None
         self.n = self.d = 0
         on_device = is_device_tensor(X)
         if on_device:
-            self._check_tensor(X)
+            X = _device_x(X, "HipDcor")
             device = X.device.index
         else:
-            X = self._check_array(X)
+            X = _host_x(X, "HipDcor")  # (the library copies it to the device and never writes it)
         h = C.c_void_p()
         self._check(self.L.midagma_dcor_create(C.byref(h), int(device)), None, "dcor_create")
         self.h = h
@@ -891,63 +883,22 @@ class HipDcor:
             self.close()
             raise
 
-    @staticmethod
-    def _check_tensor(X):
-        import torch
-        if X.dtype != torch.float64 or X.dim() != 2:
-            raise ValueError("a device X must be a 2-d float64 tensor (n x d)")
-        if int(X.shape[0]) < 2 or int(X.shape[1]) < 1:
-            raise ValueError("need at least 2 samples and 1 variable")
-
-    @staticmethod
-    def _check_array(X) -> np.ndarray:
-        X = _as_f64(X)  # (the library copies it to the device and never writes it)
-        if X.ndim != 2:
-            raise ValueError("X must be n x d")
-        if X.shape[0] < 2 or X.shape[1] < 1:
-            raise ValueError("need at least 2 samples and 1 variable")
-        if not np.isfinite(X).all():
-            raise ValueError("X holds inf or nan")
-        return X
-
     def set_data(self, X, budget_bytes: int = 0):
         """Replace the engine's data and run the per-column pre-pass.  When the library rejects a
         device X (inf or nan), the engine holds no data."""
         self.n = self.d = 0
         if is_device_tensor(X):
-            self._check_tensor(X)
-            if X.stride(1) != 1 or X.stride(0) < X.shape[1]:
-                X = X.contiguous()
+            X = _device_x(X, "HipDcor")
             n, d, ld = _rows(X)
             rc = self.L.midagma_dcor_set_data_dev(self.h, C.c_void_p(X.data_ptr()), n, d, ld, int(budget_bytes),
                                                   _cur_stream(X.device))
             self._check(rc, self.h, "dcor_set_data_dev")
         else:
-            X = self._check_array(X)
+            X = _host_x(X, "HipDcor")
             n, d = int(X.shape[0]), int(X.shape[1])
             self._check(self.L.midagma_dcor_set_data(self.h, dptr(X), n, d, int(budget_bytes)), self.h,
                         "dcor_set_data")
         self.n, self.d = n, d
-
-    def _check(self, rc, handle, what):
-        if rc >= 0:
-            return rc
-        m = self.L.midagma_dcor_last_error(handle)
-        msg = m.decode() if m else ""
-        if rc == _lib.E_ARG:
-            raise ValueError(f"{what}: {msg}")
-        raise _lib.HipSolverError(f"{what} failed ({rc}): {msg}")
-
-    def close(self):
-        if getattr(self, "h", None):
-            self.L.midagma_dcor_destroy(self.h)
-            self.h = None
-
-    def __del__(self):  # pragma: no cover
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def run(self, pairs, P: int, perms=None, seed: int = 0, *, unbiased: bool = False, block: int = 0,
             budget_bytes: int = 0, return_null: bool = False):
@@ -984,7 +935,7 @@ class HipDcor:
         return (out, inv) if inverse else out
 
 
-class HipBatch:
+class HipBatch(_Handle):
     """B independent small-d problems (d <= 64, l2, cov mode, float64) on one GPU, one persistent
     workgroup each (`midagma_batch_*`, csrc/batch.hip).  The problems share d and the loop
     settings; each has its own covariance, masks, mu, s, lr and lambda1.  Problem b's W, result
@@ -996,6 +947,7 @@ class HipBatch:
     rounding, not bit for bit."""
 
     MAX_D, MAX_B, MAX_D_TREK = 64, 16384, 32
+    _destroy, _last_error = "midagma_batch_destroy", "midagma_batch_last_error"
 
     def __init__(self, d: int, B: int, device: int = 0):
         self.L = _lib.lib()
@@ -1005,26 +957,6 @@ class HipBatch:
         h = C.c_void_p()
         self._check(self.L.midagma_batch_create(C.byref(h), self.d, self.B, self.device), None, "batch_create")
         self.h = h
-
-    def _check(self, rc, handle, what):
-        if rc >= 0:
-            return rc
-        m = self.L.midagma_batch_last_error(handle)
-        msg = m.decode() if m else ""
-        if rc == _lib.E_ARG:
-            raise ValueError(f"{what}: {msg}")
-        raise _lib.HipSolverError(f"{what} failed ({rc}): {msg}")
-
-    def close(self):
-        if getattr(self, "h", None):
-            self.L.midagma_batch_destroy(self.h)
-            self.h = None
-
-    def __del__(self):  # pragma: no cover
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def _stack(self, a, what) -> np.ndarray:
         a = _as_f64(a)

@@ -110,3 +110,35 @@ def test_group_entry_points_validate_without_a_device():
         # no device: creating a group fails loudly (no CPU path)
         rc = L.midagma_group_create(C.byref(out), 0, 10, devs, 2, _lib.GROUP_EMULATE)
         assert rc < 0
+
+
+def test_no_handle_messages_stay_per_family():
+    """A call that fails before it has a handle leaves its message in its own family's slot of the
+    calling thread (csrc/abi.h): each *_last_error(NULL) reads its family's, and midagma_last_error(NULL)
+    is not overwritten by the others.  No device call."""
+    import ctypes as C
+    from midagma_amd import _lib
+    L = _lib.load()
+    out = C.c_void_p()
+    assert L.midagma_create(None, 0, 0, 10, 0, None) == -3
+    mine = L.midagma_last_error(None)
+    assert b"midagma_create: bad arguments" in mine
+    devs = (C.c_int * 2)(0, 0)
+    assert L.midagma_indep_create(None, 0) == -3
+    assert L.midagma_batch_create(None, 8, 4, 0) == -3
+    assert L.midagma_dcor_create(None, 0) == -3
+    assert L.midagma_group_create(C.byref(out), 0, 10, devs, 0, 0) == -3
+    assert L.midagma_indep_last_error(None) == b"indep_create: bad arguments"
+    assert L.midagma_batch_last_error(None) == b"batch_create: need 1 <= d <= 64, 1 <= B <= 16384 and a device"
+    assert L.midagma_dcor_last_error(None) == b"dcor_create: bad arguments"
+    assert L.midagma_group_last_error(None) == b"group_create: bad arguments"
+    assert L.midagma_last_error(None) == mine
+
+
+def test_handle_less_entry_reports_through_midagma_last_error():
+    """An entry that takes no handle (midagma_colrank, refused for a null X before any device call)
+    leaves its message where midagma_last_error(NULL) reads it."""
+    from midagma_amd import _lib
+    L = _lib.load()
+    assert L.midagma_colrank(None, 10, 3, 3, None, 3, 0, None) == -3
+    assert L.midagma_last_error(None) == b"colrank: null pointer"
