@@ -702,6 +702,7 @@ int midagma_set_trek_tcc(midagma_solver* s, int mode, double weight, double w, d
 
 int midagma_trek(midagma_solver* s, const double* W, double* value, double* G) {
   if (!s || !W || !value) return abi_fail(s, MIDAGMA_E_ARG, "trek: null argument");
+  if (!all_finite(W, s->d, s->d, s->d)) return abi_fail(s, MIDAGMA_E_ARG, std::string("trek: ") + kNonFinite);
   return abi_guarded(s, [&] {
     const int64_t D = s->D, d = s->d, DD = D * D;
     if (!s->trek_on) {  // trek_value_grad: (0, zeros) when disabled (notreks.py)

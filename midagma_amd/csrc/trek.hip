@@ -75,7 +75,9 @@ __global__ void trek_scale_kernel(const double* __restrict__ colpart, int64_t nb
   if (threadIdx.x != 0) return;
   const double nrm = red[0];
   int s = 0;
-  while (s < smax && nrm / ldexp(1.0, s) > theta) ++s;  // smax caps it (norm guard below)
+  // smax caps it and nothing guards the norm: past theta 2^smax (||W o W||_1 > 1024) the Taylor
+  // polynomial is outside its range, and exp overflows double long before
+  while (s < smax && nrm / ldexp(1.0, s) > theta) ++s;
   scal[1] = ldexp(1.0, -s);
   scal[2] = (double)s;
   scal[5] = nrm;

@@ -1,5 +1,7 @@
 """PST trek regularizer on the GPU (csrc/trek.hip) vs the reference's trek_value_grad
-(fixtures) and the oracle, standalone and inside the minimize loop (linear.py:251-258)."""
+(fixtures) and the oracle, standalone and inside the minimize loop (linear.py:251-258).
+The padded sizes, gemm_dd splits, squaring counts, pair-list edges and loop modes these cases do
+not reach are in tests/test_gpu_trek_shapes.py, against a long-double reference."""
 import numpy as np
 import pytest
 
