@@ -583,6 +583,66 @@ int midagma_dcor_run(midagma_dcor* h, const int64_t* pairs, int64_t m, int64_t P
 int midagma_dcor_perms(midagma_dcor* h, int64_t q, int64_t P, uint64_t seed, int32_t* perms_out,
                        int32_t* inverse_out);
 int midagma_dcor_block(int64_t n);
+
+/* HSIC permutation tests of pairs of columns from low-rank factors of the RBF Gram matrices
+ * (additive, ABI 11; csrc/hsic.hip): midagma_indep_run's hsic statistic to within 4 eta (1 + eta)
+ * plus rounding, for 2 <= n < 2^31.  A column's Gram matrix K is replaced by F F^T, F (n x r) its
+ * pivoted incomplete Cholesky factor stopped when the largest residual diagonal entry is <= eta =
+ * tol, so max |K - F F^T| <= eta; with Fc, Gc the column-centred factors of the pair's columns,
+ * HSIC(x, y[pi]) = || Fc^T Gc[pi, :] ||_F^2 / n^2, an FP64 MFMA GEMM over the rows in which a
+ * permutation gathers rows of Gc.  Not the midagma_indep_ prefix: none of that handle's entries
+ * applies to this one.  Errors: midagma_hsic_last_error(handle) (or (NULL)).  One host thread
+ * drives a handle at a time.  Results are the same bits run to run and do not depend on
+ * budget_bytes.
+ * create: no device call; the device is opened by the first set_data*.
+ * set_data / set_data_dev: as midagma_dcor_set_data / _dev (arguments, checks, the stream-ordering
+ *   rule; X is never written).  The handle keeps the columns by row and sorted (16 bytes a value).
+ *   Bandwidths and factors are dropped.
+ * set_bandwidths / median_bandwidths: as the midagma_indep_ entries; the medians are numpy's bit for
+ *   bit at any n (the sorted column in global memory, one launch a bisection round, the decision on
+ *   the device).  Factors are dropped.
+ * factor: factors the ncols listed columns at tol (1e-14 <= tol <= 1e-3) and keeps the factors on
+ *   the handle; rank_out / resid_out (nullable, ncols each): the rank and the largest residual
+ *   diagonal entry reached.  Pivot: the largest residual diagonal entry, ties to the smallest row;
+ *   stops at max d <= tol or rank n.  The rank cap is 256: a column that needs more fails with
+ *   MIDAGMA_E_ARG and a message that names the column, its rank and its residual.  A zero-range
+ *   column has rank 1 and a centred factor that is exactly 0.
+ * get_factor (tests, diagnostics): the centred factor of a column that factor factored, n x r_pad
+ *   row-major (r_pad = the rank rounded up to a multiple of 16, zero padded), and the r_pad column
+ *   means that were subtracted (nullable).
+ * run: stat[q], ge[q] = #{p < P : value_p >= value_0} and null_out (nullable, m x P) of the m pairs as
+ *   midagma_indep_run's hsic (a pair with a zero-range column: 0, ge = P).  perms: m x P x n int32 host
+ *   array, every row a permutation of [0, n) (checked on the device before any row is gathered), or
+ *   NULL for midagma_dcor_run's device permutations (the same keys, q the pair's index in the call).
+ *   chunk: rows per partial product, 0 for the rule (2048) or a multiple of 16 in [16, 2^20] (tests);
+ *   the result depends on it by rounding only.  budget_bytes (<= 0: 2 GiB): half bounds the factors
+ *   held at once (pairs are taken in consecutive groups whose columns' factors fit, at least one
+ *   pair; a column is refactored when it returns), half the scratch of a batch of evaluations
+ *   (partials, permutations, the sort's buffers; at least 4 evaluations).  Columns that were not
+ *   factored at this tol are factored first.  MIDAGMA_E_ARG before any device call: null pointers,
+ *   P outside [0, 65535], tol or chunk out of range, a pair index outside [0, d), no data, no
+ *   bandwidths.
+ * perms (tests, diagnostics): the P device permutations of pair q of a call with this seed.
+ * profile (diagnostics): ms_out holds 4 doubles: the last median_bandwidths' time, and of the last
+ *   run (or factor) the factorisation (host clock, synchronised), the permutations and the
+ *   evaluation kernels (device events, summed over the batches). */
+typedef struct midagma_hsic midagma_hsic;
+int midagma_hsic_create(midagma_hsic** out, int device);
+void midagma_hsic_destroy(midagma_hsic* h);
+const char* midagma_hsic_last_error(const midagma_hsic* h);
+int midagma_hsic_set_data(midagma_hsic* h, const double* X, int64_t n, int64_t d, int64_t budget_bytes);
+int midagma_hsic_set_data_dev(midagma_hsic* h, const double* X_dev, int64_t n, int64_t d, int64_t ld,
+                              int64_t budget_bytes, void* hip_stream);
+int midagma_hsic_set_bandwidths(midagma_hsic* h, const double* sigma2, int64_t d);
+int midagma_hsic_median_bandwidths(midagma_hsic* h, const int64_t* cols, int64_t ncols, double* sigma2_out);
+int midagma_hsic_factor(midagma_hsic* h, const int64_t* cols, int64_t ncols, double tol, int32_t* rank_out,
+                        double* resid_out);
+int midagma_hsic_get_factor(midagma_hsic* h, int64_t col, double* fc_out, double* mean_out);
+int midagma_hsic_run(midagma_hsic* h, const int64_t* pairs, int64_t m, int64_t P, const int32_t* perms,
+                     uint64_t seed, double tol, int64_t chunk, int64_t budget_bytes, double* stat, int64_t* ge,
+                     double* null_out);
+int midagma_hsic_perms(midagma_hsic* h, int64_t q, int64_t P, uint64_t seed, int32_t* perms_out);
+int midagma_hsic_profile(const midagma_hsic* h, double* ms_out);
 #ifdef __cplusplus
 }
 #endif

@@ -179,6 +179,19 @@ EXPORTED = {
     "midagma_dcor_run": (_int, [_vp, _vp, _i64, _i64, _vp, C.c_uint64, _int, _int, _i64, _dp, _vp, _dp]),
     "midagma_dcor_perms": (_int, [_vp, _i64, _i64, C.c_uint64, _vp, _vp]),
     "midagma_dcor_block": (_int, [_i64]),
+    # additive to ABI 11: HSIC tests from low-rank RBF factors at any n (solver.HipHsic, csrc/hsic.hip)
+    "midagma_hsic_create": (_int, [C.POINTER(_vp), _int]),
+    "midagma_hsic_destroy": (None, [_vp]),
+    "midagma_hsic_last_error": (C.c_char_p, [_vp]),
+    "midagma_hsic_set_data": (_int, [_vp, _dp, _i64, _i64, _i64]),
+    "midagma_hsic_set_data_dev": (_int, [_vp, _vp, _i64, _i64, _i64, _i64, _vp]),
+    "midagma_hsic_set_bandwidths": (_int, [_vp, _dp, _i64]),
+    "midagma_hsic_median_bandwidths": (_int, [_vp, _vp, _i64, _dp]),
+    "midagma_hsic_factor": (_int, [_vp, _vp, _i64, _d, _vp, _dp]),
+    "midagma_hsic_get_factor": (_int, [_vp, _i64, _dp, _dp]),
+    "midagma_hsic_run": (_int, [_vp, _vp, _i64, _i64, _vp, C.c_uint64, _d, _i64, _i64, _dp, _vp, _dp]),
+    "midagma_hsic_perms": (_int, [_vp, _i64, _i64, C.c_uint64, _vp]),
+    "midagma_hsic_profile": (_int, [_vp, _dp]),
 }
 
 GROUP_EMULATE = 1

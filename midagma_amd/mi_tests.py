@@ -23,6 +23,14 @@ statistic, exact, from a sort, block sums and cell tables in O(n sqrt(n)) work a
 the permutation p-value or the analytic chi-square p-value of the bias-corrected statistic
 ("dCor without the n^2 sum").  They change nothing of the functions above.
 
+The 'hsic' test of those functions has the same n^2 sum and the same cap.  `hsic_null`, `hsic_tests`
+and `get_I_from_hsic_tests` (csrc/hsic.hip through `midagma_amd.solver.HipHsic`) lift it: each
+column's RBF Gram matrix is replaced by a pivoted incomplete Cholesky factor with elementwise error
+<= tol, and an evaluation becomes a small FP64 MFMA GEMM over gathered factor rows.  The statistic is
+the reference's to within 4 tol (1 + tol) plus rounding ("HSIC from low-rank factors"),
+the median bandwidths are the reference's bit for bit, at any n < 2^31.  They too change nothing of
+the functions above.
+
 One keyword is added, ``perms``:
   * ``"numpy"`` (default): the host draws ``rng = np.random.default_rng(seed)`` once and calls
     ``rng.permutation(n)`` num_perm times per pair, in pair order -- the reference's stream, so the
@@ -54,11 +62,12 @@ from typing import Iterable, List, Literal, Optional, Tuple
 
 import numpy as np
 
-from .solver import HipDcor, HipIndep, _device_x, _host_x, is_device_tensor
+from .solver import HipDcor, HipHsic, HipIndep, _device_x, _host_x, is_device_tensor
 
 __all__ = ["IndepTestResult", "hsic_stat", "dcor_stat", "permutation_null", "test_pairwise_independence",
            "get_I_from_full_pairwise_tests", "summarize_I", "median_sigma2", "correlation_tests",
-           "get_I_from_correlation_tests", "dcor_null", "dcor_tests", "get_I_from_dcor_tests"]
+           "get_I_from_correlation_tests", "dcor_null", "dcor_tests", "get_I_from_dcor_tests", "hsic_null",
+           "hsic_tests", "get_I_from_hsic_tests"]
 
 TestName = Literal["hsic", "dcor", "pearson", "spearman"]
 
@@ -517,6 +526,121 @@ def get_I_from_dcor_tests(X, *, alpha: float = 0.05, pvalue: str = "permutation"
     (alpha_eff = alpha / #pairs under Bonferroni; the same dtype and shape, the empty case included).
     With perms="numpy" and undirected=True the p-values are `permutation_null`'s."""
     _, p = dcor_tests(X, pvalue=pvalue, num_perm=num_perm, seed=seed, perms=perms, device=device)
+    return _I_from_pvalues(p, alpha, bonferroni, undirected, exclude_diagonal)
+
+
+def _hsic_null(eng: HipHsic, pairs: np.ndarray, P: int, seed: int, perms, tol: float, budget_bytes: int,
+               return_null: bool, chunk: int):
+    n, m = eng.n, len(pairs)
+    kw = dict(tol=tol, chunk=chunk, budget_bytes=budget_bytes, return_null=True)
+    if isinstance(perms, str) and perms == "device":
+        stat, ge, null = eng.run(pairs, P, None, seed, **kw)
+    elif isinstance(perms, str):
+        rng = np.random.default_rng(seed)
+        stat, ge, null = np.zeros(m), np.zeros(m, dtype=np.int64), np.zeros((m, P))
+        step = max(1, _HOST_CHUNK_BYTES // max(1, 4 * P * n))
+        for q0 in range(0, m, step):
+            q1 = min(m, q0 + step)
+            pm = _numpy_perms(rng, q1 - q0, P, n)
+            stat[q0:q1], ge[q0:q1], null[q0:q1] = eng.run(pairs[q0:q1], P, pm, 0, **kw)
+    else:
+        stat, ge, null = eng.run(pairs, P, perms, 0, **kw)
+    return stat, ge, (null if return_null else None)
+
+
+def _hsic_engine(X, device: int, budget_bytes: int, cols, sigma2) -> HipHsic:
+    """An engine on X with its bandwidths: the medians of the listed columns (sigma2 None) or the
+    given squared bandwidths (d values)."""
+    eng = HipHsic(X, device, budget_bytes)
+    try:
+        if sigma2 is None:
+            eng.median_bandwidths(cols)
+        else:
+            eng.set_bandwidths(sigma2)
+    except Exception:
+        eng.close()
+        raise
+    return eng
+
+
+def _check_hsic_args(perms, num_perm, tol, chunk):
+    if isinstance(perms, str) and perms not in ("numpy", "device"):
+        raise ValueError("perms must be 'numpy', 'device' or an int32 array (m, num_perm, n)")
+    if int(num_perm) < 0:
+        raise ValueError("num_perm must be >= 0")
+    if not 1e-14 <= float(tol) <= 1e-3:
+        raise ValueError("tol must be in [1e-14, 1e-3]")
+    if not (chunk == 0 or (16 <= int(chunk) <= 2**20 and int(chunk) % 16 == 0)):
+        raise ValueError("chunk must be 0 or a multiple of 16 in [16, 2^20]")
+
+
+def hsic_null(X, pairs, *, num_perm: int = 200, seed: int = 0, perms="numpy", tol: float = 1e-13, device: int = 0,
+              budget_bytes: int = 0, return_null: bool = True, sigma2=None, chunk: int = 0):
+    """`permutation_null(test="hsic")` without the n^2 sum and without its cap on n (csrc/hsic.hip:
+    low-rank factors of the RBF Gram matrices, an FP64 MFMA GEMM an evaluation): (stat, ge, null)
+    with the same conventions; every value is within 4 tol (1 + tol) plus rounding of the n^2 sum's.
+    perms: ``"numpy"`` draws one ``default_rng(seed)`` exactly as `permutation_null` does;
+    ``"device"`` makes them on the GPU by `dcor_null`'s rule; an int32 array (m, num_perm, n) is taken
+    as given (every row must be a permutation).  tol: the largest residual diagonal entry at which a
+    column's factorisation stops (1e-14 .. 1e-3); a column that needs a rank above 256 raises
+    ValueError.  sigma2: d squared bandwidths instead of the median heuristic.  budget_bytes: the
+    device bytes for factors and scratch (0: 2 GiB); chunk: rows per partial product (0: the rule;
+    tests); results do not depend on the budget."""
+    _check_hsic_args(perms, num_perm, tol, chunk)
+    X = _as_data(X, max_n=None)
+    n, d = int(X.shape[0]), int(X.shape[1])
+    pairs = _as_pairs(pairs, d)
+    P = int(num_perm)
+    if not isinstance(perms, str):
+        perms = np.ascontiguousarray(perms, dtype=np.int32)
+        if perms.shape != (len(pairs), P, n):
+            raise ValueError(f"perms must be {(len(pairs), P, n)}, got {perms.shape}")
+    if sigma2 is not None:
+        sigma2 = np.ascontiguousarray(sigma2, dtype=np.float64).ravel()
+        if sigma2.size != d or not (np.isfinite(sigma2).all() and (sigma2 > 0).all()):
+            raise ValueError("sigma2 must hold d finite squared bandwidths > 0")
+    eng = _hsic_engine(X, device, budget_bytes, np.unique(pairs), sigma2)
+    try:
+        return _hsic_null(eng, pairs, P, seed, perms, float(tol), budget_bytes, return_null, int(chunk))
+    finally:
+        eng.close()
+
+
+def hsic_tests(X, *, num_perm: int = 200, seed: int = 0, perms="device", tol: float = 1e-13, device: int = 0,
+               budget_bytes: int = 0, sigma2=None):
+    """(stat, p), two d x d host arrays: the HSIC permutation test (`hsic_null`) of every pair i < j
+    of X's columns, in the reference's pair order, mirrored to (j, i), p = (ge + 1) / (num_perm + 1).
+    A pair with a zero-range column is (0, 1).  The diagonal is (nan, 0) by rule: the reference
+    tests no column against itself."""
+    if isinstance(perms, str) and perms not in ("numpy", "device"):
+        raise ValueError("perms must be 'numpy' or 'device'")
+    _check_hsic_args(perms, num_perm, tol, 0)
+    X = _as_data(X, max_n=None)
+    d = int(X.shape[1])
+    P = int(num_perm)
+    iu = np.triu_indices(d, 1)
+    pairs = np.stack(iu, axis=1).astype(np.int64)
+    stat, p = np.full((d, d), np.nan), np.zeros((d, d))
+    if len(pairs):
+        eng = _hsic_engine(X, device, budget_bytes, None, sigma2)
+        try:
+            s, ge, _ = _hsic_null(eng, pairs, P, seed, perms, float(tol), budget_bytes, False, 0)
+        finally:
+            eng.close()
+        pv = (ge + 1.0) / (P + 1.0)
+        stat[iu], p[iu] = s, pv
+        stat.T[iu], p.T[iu] = s, pv
+    return stat, p
+
+
+def get_I_from_hsic_tests(X, *, alpha: float = 0.05, num_perm: int = 200, seed: int = 0, perms="device",
+                          bonferroni: bool = True, undirected: bool = True, exclude_diagonal: bool = True,
+                          tol: float = 1e-13, device: int = 0) -> np.ndarray:
+    """`get_I_from_full_pairwise_tests(test="hsic")` through `hsic_tests`: I = {(i, j): p > alpha_eff}
+    in the reference's pair order (alpha_eff = alpha / #pairs under Bonferroni; the same dtype and
+    shape, the empty case included).  With perms="numpy" and undirected=True the p-values are
+    `permutation_null`'s wherever no permuted value is within 4 tol (1 + tol) of the observed one."""
+    _, p = hsic_tests(X, num_perm=num_perm, seed=seed, perms=perms, tol=tol, device=device)
     return _I_from_pvalues(p, alpha, bonferroni, undirected, exclude_diagonal)
 
 

@@ -935,6 +935,141 @@ class HipDcor(_Handle):
         return (out, inv) if inverse else out
 
 
+class HipHsic(_Handle):
+    """HSIC permutation tests of pairs of columns from low-rank factors of the RBF Gram matrices, on
+    one GPU (`midagma_hsic_*`, csrc/hsic.hip): the engine under `mi_tests.hsic_null` / `hsic_tests`,
+    for 2 <= n < 2^31.  Holds the columns of X by row and sorted (16 bytes a value) and the centred
+    factors of the columns in use (8 n r_pad bytes each).
+
+    X is a host array (copied to `device`), or a 2-d float64 torch CUDA tensor: the engine then
+    lives on the tensor's device (`device` is ignored), reads X there on torch's current stream
+    without a host copy and never writes it.  No synchronise is needed around the call."""
+
+    TOL = 1e-13
+    _destroy, _last_error = "midagma_hsic_destroy", "midagma_hsic_last_error"
+
+    def __init__(self, X, device: int = 0, budget_bytes: int = 0):
+        self.L = _lib.lib()
+        self.h = None
+        self.n = self.d = 0
+        on_device = is_device_tensor(X)
+        if on_device:
+            X = _device_x(X, "HipHsic")
+            device = X.device.index
+        else:
+            X = _host_x(X, "HipHsic")  # (the library copies it to the device and never writes it)
+        h = C.c_void_p()
+        self._check(self.L.midagma_hsic_create(C.byref(h), int(device)), None, "hsic_create")
+        self.h = h
+        try:
+            self.set_data(X, budget_bytes)
+        except Exception:
+            self.close()
+            raise
+
+    def set_data(self, X, budget_bytes: int = 0):
+        """Replace the engine's data (bandwidths and factors are dropped).  When the library rejects
+        a device X (inf or nan), the engine holds no data."""
+        self.n = self.d = 0
+        if is_device_tensor(X):
+            X = _device_x(X, "HipHsic")
+            n, d, ld = _rows(X)
+            rc = self.L.midagma_hsic_set_data_dev(self.h, C.c_void_p(X.data_ptr()), n, d, ld, int(budget_bytes),
+                                                  _cur_stream(X.device))
+            self._check(rc, self.h, "hsic_set_data_dev")
+        else:
+            X = _host_x(X, "HipHsic")
+            n, d = int(X.shape[0]), int(X.shape[1])
+            self._check(self.L.midagma_hsic_set_data(self.h, dptr(X), n, d, int(budget_bytes)), self.h,
+                        "hsic_set_data")
+        self.n, self.d = n, d
+
+    def set_bandwidths(self, sigma2):
+        """The RBF kernels' sigma^2 per variable (factors are dropped)."""
+        s2 = _as_f64(sigma2).ravel()
+        self._check(self.L.midagma_hsic_set_bandwidths(self.h, dptr(s2), s2.size), self.h, "hsic_set_bandwidths")
+
+    def median_bandwidths(self, cols=None) -> np.ndarray:
+        """sigma^2 per variable by the reference's median heuristic at any n, on the device (bit for
+        bit `mi_tests.median_sigma2` of the column) for the listed columns (None: all) and 1.0 for
+        the others; installed as `set_bandwidths` would.  Returns all d values."""
+        if not self.d:
+            raise ValueError("hsic_median_bandwidths: set the data first")
+        s2 = np.zeros(self.d)
+        if cols is None:
+            cp, nc = None, 0
+        else:
+            cols = np.ascontiguousarray(cols, dtype=np.int64).ravel()
+            if cols.size == 0:  # (an empty array has no usable address)
+                s2[:] = 1.0
+                self.set_bandwidths(s2)
+                return s2
+            cp, nc = C.c_void_p(cols.ctypes.data), int(cols.size)
+        self._check(self.L.midagma_hsic_median_bandwidths(self.h, cp, nc, dptr(s2)), self.h,
+                    "hsic_median_bandwidths")
+        return s2
+
+    def factor(self, cols, tol: float = TOL):
+        """(rank, resid) of the listed columns' pivoted incomplete Cholesky factors at `tol`: int32
+        ranks and the largest residual diagonal entries reached.  The factors stay on the engine."""
+        cols = np.ascontiguousarray(cols, dtype=np.int64).ravel()
+        rank = np.zeros(cols.size, dtype=np.int32)
+        resid = np.zeros(cols.size)
+        if cols.size == 0:
+            return rank, resid
+        rc = self.L.midagma_hsic_factor(self.h, C.c_void_p(cols.ctypes.data), int(cols.size), float(tol),
+                                        C.c_void_p(rank.ctypes.data), dptr(resid))
+        self._check(rc, self.h, "hsic_factor")
+        return rank, resid
+
+    def get_factor(self, col: int, rank: int):
+        """(Fc, mean): the centred factor of a factored column (n x r_pad, r_pad the rank rounded up
+        to a multiple of 16) and the column means that were subtracted (diagnostics)."""
+        rp = (int(rank) + 15) // 16 * 16
+        Fc, mean = np.zeros((self.n, rp)), np.zeros(rp)
+        self._check(self.L.midagma_hsic_get_factor(self.h, int(col), dptr(Fc), dptr(mean)), self.h, "hsic_get_factor")
+        return Fc, mean
+
+    def run(self, pairs, P: int, perms=None, seed: int = 0, *, tol: float = TOL, chunk: int = 0,
+            budget_bytes: int = 0, return_null: bool = False):
+        """(stat, ge[, null]) per pair, as `HipIndep.run("hsic", ...)` to within 4 tol (1 + tol) plus
+        rounding.  perms: explicit m x P x n int32 permutations, or None for device permutations from
+        `seed` (csrc/dcor.hip's rule).  chunk: rows per partial product (0: the rule)."""
+        pairs = np.ascontiguousarray(pairs, dtype=np.int64).reshape(-1, 2)
+        m, P = int(pairs.shape[0]), int(P)
+        if perms is not None:
+            perms = np.ascontiguousarray(perms, dtype=np.int32)
+            if perms.shape != (m, P, self.n):
+                raise ValueError(f"perms must be {(m, P, self.n)}, got {perms.shape}")
+        stat = np.zeros(m)
+        ge = np.zeros(m, dtype=np.int64)
+        null = np.zeros((m, max(P, 0))) if return_null else None
+
+        def vp(a):
+            return None if a is None or a.size == 0 else C.c_void_p(a.ctypes.data)
+
+        rc = self.L.midagma_hsic_run(self.h, vp(pairs), m, P, vp(perms), C.c_uint64(int(seed) & (2**64 - 1)),
+                                     float(tol), int(chunk), int(budget_bytes), dptr(stat), vp(ge),
+                                     dptr(null) if (return_null and null.size) else None)
+        self._check(rc, self.h, "hsic_run")
+        return (stat, ge, null) if return_null else (stat, ge)
+
+    def device_perms(self, q: int, P: int, seed: int = 0):
+        """The P device permutations (P x n int32) of pair q of a call with this seed."""
+        out = np.zeros((int(P), self.n), dtype=np.int32)
+        rc = self.L.midagma_hsic_perms(self.h, int(q), int(P), C.c_uint64(int(seed) & (2**64 - 1)),
+                                       C.c_void_p(out.ctypes.data))
+        self._check(rc, self.h, "hsic_perms")
+        return out
+
+    def profile(self) -> dict:
+        """Times in ms: the last `median_bandwidths`, and the last run's factorisation, permutations
+        and evaluation kernels (diagnostics)."""
+        ms = np.zeros(4)
+        self._check(self.L.midagma_hsic_profile(self.h, dptr(ms)), self.h, "hsic_profile")
+        return dict(zip(("median_ms", "factor_ms", "perm_ms", "eval_ms"), ms.tolist()))
+
+
 class HipBatch(_Handle):
     """B independent small-d problems (d <= 64, l2, cov mode, float64) on one GPU, one persistent
     workgroup each (`midagma_batch_*`, csrc/batch.hip).  The problems share d and the loop
