@@ -625,7 +625,29 @@ int midagma_dcor_block(int64_t n);
  * perms (tests, diagnostics): the P device permutations of pair q of a call with this seed.
  * profile (diagnostics): ms_out holds 4 doubles: the last median_bandwidths' time, and of the last
  *   run (or factor) the factorisation (host clock, synchronised), the permutations and the
- *   evaluation kernels (device events, summed over the batches). */
+ *   evaluation kernels (device events, summed over the batches).
+ * all_pairs (additive, ABI 11): the chi-square test's statistic of every pair of the listed columns
+ *   (cols NULL: all d, ncols ignored) from one evaluation a pair, no permutations.  With D = 1 - K
+ *   off the diagonal (hyppo's Hsic convention) and A~, B~ the U-centred D of two columns,
+ *   cov_u_out (ncols x ncols, required) receives cov_U = <A~, B~> / (n (n - 3)), the variances on
+ *   the diagonal; the caller forms R_U = cov_U(x, y) / sqrt(cov_U(x, x) cov_U(y, y)) and
+ *   p = chi2.sf(n R_U + 1, 1).  biased_out (nullable, ncols x ncols) receives run's statistic
+ *   || Fc_i^T Fc_j ||_F^2 / n^2.  Both are symmetric; a pair with a zero-range column is 0 in both.
+ *   Computed from the centred factors and O(n) vectors a column as
+ *   <A~_x, A~_y> = || Fc_x^T Fc_y ||_F^2 + 2 n v~_x.v~_y + n^2 c_x c_y - a_x.a_y: the block norms by a
+ *   tiled FP64 MFMA pass over the factors side by side (128 x 128 tiles on and above the diagonal,
+ *   row slabs staged in LDS, rows in chunks as run's), the two vector Grams by the same pass.  Within
+ *   (n - 1) / (n - 3) c_n^2 tol (2 + tol), c_n = (4 n - 4) / (n - 2), plus rounding, of the n^2
+ *   definition.  No floating-point atomics: the same bits run to run, whatever budget_bytes, the
+ *   column list around a pair and the launch geometry.  budget_bytes (<= 0: 2 GiB): half bounds the
+ *   factors and vectors held (all listed columns at once if they fit, else column groups of a
+ *   quarter each, two held at a time, refactored when they return), half the chunk partials of a
+ *   batch of tiles (at least one tile).  MIDAGMA_E_ARG before any device call: null handle or
+ *   output, ncols < 0, tol or chunk out of range, no data, n < 4, no bandwidths, a column outside
+ *   [0, d).
+ * all_pairs_profile (diagnostics): ms_out holds 3 doubles of the last all_pairs: the factorisation
+ *   (host clock), the tiled pass over the factors, and the vectors with their Grams (device
+ *   events).  A call of its own: profile's 4 doubles stay 4 for the callers that sized a buffer. */
 typedef struct midagma_hsic midagma_hsic;
 int midagma_hsic_create(midagma_hsic** out, int device);
 void midagma_hsic_destroy(midagma_hsic* h);
@@ -643,6 +665,9 @@ int midagma_hsic_run(midagma_hsic* h, const int64_t* pairs, int64_t m, int64_t P
                      double* null_out);
 int midagma_hsic_perms(midagma_hsic* h, int64_t q, int64_t P, uint64_t seed, int32_t* perms_out);
 int midagma_hsic_profile(const midagma_hsic* h, double* ms_out);
+int midagma_hsic_all_pairs(midagma_hsic* h, const int64_t* cols, int64_t ncols, double tol, int64_t chunk,
+                           int64_t budget_bytes, double* cov_u_out, double* biased_out);
+int midagma_hsic_all_pairs_profile(const midagma_hsic* h, double* ms_out);
 #ifdef __cplusplus
 }
 #endif

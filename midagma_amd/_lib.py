@@ -192,6 +192,8 @@ EXPORTED = {
     "midagma_hsic_run": (_int, [_vp, _vp, _i64, _i64, _vp, C.c_uint64, _d, _i64, _i64, _dp, _vp, _dp]),
     "midagma_hsic_perms": (_int, [_vp, _i64, _i64, C.c_uint64, _vp]),
     "midagma_hsic_profile": (_int, [_vp, _dp]),
+    "midagma_hsic_all_pairs": (_int, [_vp, _vp, _i64, _d, _i64, _i64, _dp, _dp]),
+    "midagma_hsic_all_pairs_profile": (_int, [_vp, _dp]),
 }
 
 GROUP_EMULATE = 1

@@ -35,6 +35,29 @@
 // No floating-point atomics: every sum has one order that depends on n, the ranks and the chunk size
 // alone, so results are the same bits run to run and do not depend on how pairs and permutations
 // are batched or how columns are grouped for factorisation.
+//
+// Every pair at once (midagma_hsic_all_pairs): the chi-square test of the bias-corrected correlation
+// (Shen, Panda, Vogelstein) needs one evaluation a pair and no permutation, and for every pair the
+// evaluations are one symmetric GEMM.  With D = 1 - K off the diagonal (hyppo's Hsic convention) and
+// A~ its U-centred matrix, from the centred factor Fc, the means m and O(n) vectors a column,
+//   <A~_x, A~_y> = || Fc_x^T Fc_y ||_F^2 + 2 n v~_x.v~_y + n^2 c_x c_y - a_x.a_y,
+//   rho_i = (n - 1) - (n F_i.m - |F_i|^2),  T = sum rho_i,  v = -Fc m - rho / (n - 2),
+//   g = 1 - m.m + T / ((n - 1)(n - 2)),  a_i = -|Fc_i|^2 + 2 v_i + g,  v~ = v - mean(v),  c = g + 2 mean(v)
+// (the cross terms vanish because Fc^T 1 = 0; the centred form cancels nothing of size n^2).
+//   vectors        16 lanes a row of Fc: v and -q + 2 v into a panel (n x 2 columns a column of X,
+//                  row-major, padded to 16), chunk sums of rho and Fc m; a thread a column for the
+//                  scalars; a shift of the panel by mean(v) and g
+//   tiled pass     Phi = [Fc_1 | ... | Fc_k] side by side; a workgroup owns a 128 x 128 tile of
+//                  Phi_A^T Phi_B on or above the diagonal and a chunk of rows, stages 16-row slabs of
+//                  the two operand panels in LDS (a table maps a 16-column slab of Phi to its factor)
+//                  and runs v_mfma_f64_16x16x4_f64, a wave a 64 x 64 quadrant over every row of the
+//                  chunk; the same kernel over the vector panels gives the two vector Grams
+//   reduce         a sub-tile's entries from the chunk partials in ascending chunk order, squared and
+//                  summed in a fixed order (the factors) or kept (the vectors)
+//   combine        a thread a pair: its sub-tiles' squared norms in ascending order, plus the rest
+// A 16 x 16 sub-tile belongs to one pair and a wave takes all rows of a chunk, so a pair's value
+// depends on n, the two ranks, the chunk and nothing else: not on the budget, the column groups, the
+// other columns listed or where the pair's sub-tiles fall in a tile.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -440,6 +463,247 @@ __global__ __launch_bounds__(HT) void hsic_value_kernel(const double* __restrict
   if (threadIdx.x == 0) vals[slot] = s / ((double)n * (double)n);
 }
 
+// --- every pair at once: the tiled cross-Gram ------------------------------------------------------
+// Phi = [Fc_1 | ... | Fc_k], the centred factors of a column group side by side, is n x R.  A slab
+// is 16 columns of Phi: 16 columns of one factor (r_pad is a multiple of 16), so a 16 x 16 sub-tile
+// of Phi_A^T Phi_B belongs to one pair of columns.
+struct Slab {
+  const double* p;  // row 0 of the slab's 16 columns (nullptr: past the panel's end)
+  int64_t ld;       // doubles from a row to the next (the factor's r_pad)
+};
+
+constexpr int TS = 8;                // slabs a tile edge: tiles are 128 x 128
+constexpr int KS = 16;               // rows staged in LDS at a time
+constexpr int LS = 16 * TS + 16;     // LDS row stride in doubles: 144 (rows kq and kq + 1 of an operand read 32 banks apart)
+constexpr int TSUB = TS * TS;        // sub-tiles a tile
+constexpr int TILE_E = TSUB * 256;   // doubles a tile
+
+// The share of rows [c chunk, (c + 1) chunk) of tile (ta, tb) of Phi_A^T Phi_B; 1-d grid, block
+// c ntiles + tile.  Wave w owns the 64 x 64 quadrant (w >> 1, w & 1) as 4 x 4 accumulators and
+// takes every row of the chunk in ascending order, so an entry's value depends on n and the chunk
+// alone, not on where its sub-tile lies in a tile.  Rows past the chunk's or n's end are staged as
+// zeros.  partial: [(c ntiles + tile) 64 + sub-tile i 8 + j][reg 64 + lane]; sub-tiles past the
+// panels' ends are not written.
+__global__ __launch_bounds__(HT) void hsic_tile_kernel(const Slab* __restrict__ slabA, const Slab* __restrict__ slabB,
+                                                       const int2* __restrict__ tiles, int ntiles, int nsA, int nsB,
+                                                       int64_t n, int64_t chunk, double* __restrict__ partial) {
+  __shared__ double As[KS * LS], Bs[KS * LS];
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, r = lane & 15, kq = lane >> 4;
+  const int64_t c = blockIdx.x / ntiles;
+  const int tile = (int)(blockIdx.x % ntiles);
+  const int2 tt = tiles[tile];
+  // staging: pass q moves rows 4 q + (tid >> 6); a thread moves 2 doubles of slab (tid & 63) >> 3
+  const int ls = lane >> 3, lc = (lane & 7) * 2;
+  const int sa = tt.x * TS + ls, sb = tt.y * TS + ls;
+  const Slab SA = sa < nsA ? slabA[sa] : Slab{nullptr, 0};
+  const Slab SB = sb < nsB ? slabB[sb] : Slab{nullptr, 0};
+  const int64_t r0 = c * chunk, r1 = std::min<int64_t>(n, r0 + chunk);
+  // this wave's quadrant: sub-tiles [4 wm, 4 wm + ni) x [4 wn, 4 wn + nj)
+  const int wm = w >> 1, wn = w & 1;
+  const int ni = std::max(0, std::min(4, nsA - (tt.x * TS + 4 * wm)));
+  const int nj = std::max(0, std::min(4, nsB - (tt.y * TS + 4 * wn)));
+  dbl4 acc[4][4];
+#pragma unroll
+  for (int i = 0; i < 4; ++i)
+#pragma unroll
+    for (int j = 0; j < 4; ++j) acc[i][j] = dbl4{0.0, 0.0, 0.0, 0.0};
+  double2 pa[4], pb[4];
+  auto fetch = [&](int64_t base) {
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      const int64_t row = base + 4 * q + w;
+      const bool ok = row < r1;
+      pa[q] = (ok && SA.p) ? *reinterpret_cast<const double2*>(SA.p + row * SA.ld + lc) : double2{0.0, 0.0};
+      pb[q] = (ok && SB.p) ? *reinterpret_cast<const double2*>(SB.p + row * SB.ld + lc) : double2{0.0, 0.0};
+    }
+  };
+  fetch(r0);
+  for (int64_t base = r0; base < r1; base += KS) {
+    __syncthreads();  // (the rows of the step before are no longer read)
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      *reinterpret_cast<double2*>(&As[(4 * q + w) * LS + ls * 16 + lc]) = pa[q];
+      *reinterpret_cast<double2*>(&Bs[(4 * q + w) * LS + ls * 16 + lc]) = pb[q];
+    }
+    __syncthreads();
+    if (base + KS < r1) fetch(base + KS);  // (in flight under the MFMAs)
+    if (ni > 0 && nj > 0) {
+#pragma unroll
+      for (int k0 = 0; k0 < KS; k0 += 4) {
+        const double* ar = &As[(k0 + kq) * LS + wm * 64 + r];
+        const double* br = &Bs[(k0 + kq) * LS + wn * 64 + r];
+        double a[4], b[4];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) a[i] = ar[16 * i], b[i] = br[16 * i];
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+          if (i < ni) {
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+              if (j < nj) acc[i][j] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[i], b[j], acc[i][j], 0, 0, 0);
+          }
+      }
+    }
+  }
+  double* dst = partial + (int64_t)blockIdx.x * TILE_E;
+#pragma unroll
+  for (int i = 0; i < 4; ++i)
+    if (i < ni) {
+#pragma unroll
+      for (int j = 0; j < 4; ++j)
+        if (j < nj) {
+          double* d = dst + ((4 * wm + i) * TS + 4 * wn + j) * 256 + lane;
+#pragma unroll
+          for (int t = 0; t < 4; ++t) d[t * 64] = acc[i][j][t];
+        }
+    }
+}
+
+// Every entry of a sub-tile from its chunk partials in ascending chunk order; grid (64, tiles of
+// the batch).  SQ: out[sa nsB + sb] = the sum of the squared entries in a fixed order (a wave's
+// butterfly, then wave 0 + 1 + 2 + 3); else out[(sa nsB + sb) 256 + e] = the entries.
+template <bool SQ>
+__global__ __launch_bounds__(HT) void hsic_tile_reduce_kernel(const double* __restrict__ partial,
+                                                              const int2* __restrict__ tiles, int ntiles, int nsA,
+                                                              int nsB, int64_t nchunk, double* __restrict__ out) {
+  __shared__ double ws[4];
+  const int tile = blockIdx.y, sub = blockIdx.x;
+  const int2 tt = tiles[tile];
+  const int sa = tt.x * TS + sub / TS, sb = tt.y * TS + sub % TS;
+  if (sa >= nsA || sb >= nsB) return;
+  double m = 0.0;
+  for (int64_t c = 0; c < nchunk; ++c) m += partial[((c * ntiles + tile) * TSUB + sub) * 256 + threadIdx.x];
+  if (SQ) {
+    const double s = wg_sum(m * m, ws);
+    if (threadIdx.x == 0) out[(int64_t)sa * nsB + sb] = s;
+  } else {
+    out[((int64_t)sa * nsB + sb) * 256 + threadIdx.x] = m;
+  }
+}
+
+// --- every pair at once: the O(n) vectors of the U-centred form -----------------------------------
+// With K^ = F F^T, m the column means of F and Fc = F - 1 m^T:  k^_i = |F_i|^2,
+// rho_i = (n - 1) - (n F_i . m - k^_i) (row i's sum of D = 1 - K^ off the diagonal), w_i = Fc_i . m,
+// q_i = |Fc_i|^2, T = sum rho_i, g = 1 - m.m + T / ((n - 1)(n - 2)).
+
+// a column of the group: its factor and where its means start in the group's list
+struct UCol {
+  const double* Fc;
+  int32_t rp, moff;
+};
+
+// The chunk's FCH rows of one column, 16 lanes a row (a 16-lane load is one 128-byte segment of the
+// row): lane s sums the entries s, s + 16, ... of its row, then the 16 lanes a butterfly, so a row's
+// sums depend on r_pad alone.  panel[a][2 col] = v_a = -w_a - rho_a / (n - 2) and
+// panel[a][2 col + 1] = -q_a + 2 v_a (hsic_u_shift_kernel finishes both); part[(col nch + ch) 2 +
+// {0, 1}] = the chunk's sums of rho and w.  panel is n x W row-major; grid (nch, columns)
+__global__ __launch_bounds__(HT) void hsic_u_rows_kernel(const UCol* __restrict__ cols, const double* __restrict__ means,
+                                                         int64_t n, int64_t nch, int W, double* __restrict__ panel,
+                                                         double* __restrict__ part) {
+  __shared__ double ws[4];
+  const int col = blockIdx.y, sub = threadIdx.x & 15, grp = threadIdx.x >> 4;
+  const UCol uc = cols[col];
+  const double* mean = means + uc.moff;
+  const double nr = (double)n;
+  double sr = 0.0, sw = 0.0;
+  for (int it = 0; it < FCH / 16; ++it) {
+    const int64_t a = (int64_t)blockIdx.x * FCH + it * 16 + grp;
+    double kh = 0.0, fm = 0.0, w = 0.0, q = 0.0;
+    if (a < n) {
+      const double* fr = uc.Fc + a * uc.rp;
+      for (int t = sub; t < uc.rp; t += 16) {
+        const double fc = fr[t], m = mean[t], f = fc + m;
+        kh += f * f, fm += f * m, w += fc * m, q += fc * fc;
+      }
+    }
+#pragma unroll
+    for (int off = 8; off >= 1; off >>= 1) {
+      kh += __shfl_xor(kh, off), fm += __shfl_xor(fm, off);
+      w += __shfl_xor(w, off), q += __shfl_xor(q, off);
+    }
+    if (a < n && sub == 0) {
+      const double rho = (nr - 1.0) - (nr * fm - kh);
+      const double v = -w - rho / (nr - 2.0);
+      panel[a * W + 2 * col] = v;
+      panel[a * W + 2 * col + 1] = -q + 2.0 * v;
+      sr += rho, sw += w;
+    }
+  }
+  sr = wg_sum(sr, ws);
+  sw = wg_sum(sw, ws);
+  if (threadIdx.x == 0) {
+    part[((int64_t)col * nch + blockIdx.x) * 2] = sr;
+    part[((int64_t)col * nch + blockIdx.x) * 2 + 1] = sw;
+  }
+}
+
+// scal[col 4 + ..] = g, mean(v), c = g + 2 mean(v), T from the chunk sums in ascending order; one thread a column
+__global__ __launch_bounds__(HT) void hsic_u_scalars_kernel(const UCol* __restrict__ cols, const double* __restrict__ means,
+                                                            const double* __restrict__ part, int64_t n, int64_t nch,
+                                                            int ncols, double* __restrict__ scal) {
+  const int col = blockIdx.x * HT + threadIdx.x;
+  if (col >= ncols) return;
+  const UCol uc = cols[col];
+  double T = 0.0, sw = 0.0, mm = 0.0;
+  for (int64_t c = 0; c < nch; ++c) T += part[((int64_t)col * nch + c) * 2], sw += part[((int64_t)col * nch + c) * 2 + 1];
+  for (int t = 0; t < uc.rp; ++t) mm += means[uc.moff + t] * means[uc.moff + t];
+  const double nr = (double)n;
+  const double g = (1.0 - mm) + T / ((nr - 1.0) * (nr - 2.0));
+  const double vbar = (-sw - T / (nr - 2.0)) / nr;
+  scal[col * 4] = g, scal[col * 4 + 1] = vbar, scal[col * 4 + 2] = g + 2.0 * vbar, scal[col * 4 + 3] = T;
+}
+
+// panel[a][2 col] = v~_a = v_a - mean(v) and panel[a][2 col + 1] = a_a = (-q_a + 2 v_a) + g; one thread a pair of entries
+__global__ __launch_bounds__(HT) void hsic_u_shift_kernel(const double* __restrict__ scal, int64_t n, int ncols, int W,
+                                                          double* __restrict__ panel) {
+  const int64_t e = (int64_t)blockIdx.x * HT + threadIdx.x;
+  if (e >= n * ncols) return;
+  const int64_t a = e / ncols;
+  const int col = (int)(e % ncols);
+  panel[a * W + 2 * col] -= scal[col * 4 + 1];
+  panel[a * W + 2 * col + 1] += scal[col * 4];
+}
+
+// a column's slabs of Phi: [s0, s0 + ns)
+struct ColSlabs {
+  int32_t s0, ns;
+};
+
+// cov[pa nB + pb] = <A~_a, A~_b> / (n (n - 3)) and bia[..] = |Fc_a^T Fc_b|_F^2 / n^2 of every pair of
+// the group pair (same: pb >= pa only): the sub-tiles' squared norms in ascending (sa, sb) order
+// (a column with itself: sa <= sb, the sub-tiles above the diagonal twice), then
+// + 2 n v~_a.v~_b + n^2 c_a c_b - a_a.a_b.  One thread a pair.
+__global__ __launch_bounds__(HT) void hsic_u_combine_kernel(const double* __restrict__ S, const double* __restrict__ E,
+                                                            const ColSlabs* __restrict__ csA,
+                                                            const ColSlabs* __restrict__ csB,
+                                                            const double* __restrict__ scalA,
+                                                            const double* __restrict__ scalB, int nA, int nB, int nsB,
+                                                            int nvB, int same, int64_t n, double* __restrict__ cov,
+                                                            double* __restrict__ bia) {
+  const int64_t e = (int64_t)blockIdx.x * HT + threadIdx.x;
+  if (e >= (int64_t)nA * nB) return;
+  const int pa = (int)(e / nB), pb = (int)(e % nB);
+  if (same && pb < pa) return;
+  const ColSlabs a = csA[pa], b = csB[pb];
+  const bool self = same && pa == pb;
+  double sq = 0.0;
+  for (int i = 0; i < a.ns; ++i)
+    for (int j = self ? i : 0; j < b.ns; ++j) {
+      const double s = S[(int64_t)(a.s0 + i) * nsB + b.s0 + j];
+      sq += (self && j > i) ? 2.0 * s : s;
+    }
+  // entry (row, col) of a sub-tile is register row >> 2 of lane (row & 3) 16 + col (mfma64.h, acc_row)
+  const int ma = 2 * pa, mb = 2 * pb;
+  const double* sub = E + ((int64_t)(ma >> 4) * nvB + (mb >> 4)) * 256;
+  const int ra = ma & 15, rb = mb & 15;
+  const double vv = sub[(ra >> 2) * 64 + (ra & 3) * 16 + rb];
+  const double aa = sub[((ra + 1) >> 2) * 64 + ((ra + 1) & 3) * 16 + rb + 1];
+  const double nr = (double)n;
+  const double u = ((sq + 2.0 * nr * vv) + nr * nr * (scalA[pa * 4 + 2] * scalB[pb * 4 + 2])) - aa;
+  cov[e] = u / (nr * (nr - 3.0));
+  bia[e] = sq / (nr * nr);
+}
+
 constexpr int64_t kMaxD = 65535, kMaxP = 65535, kMaxGroups = 16383;  // (EG permutations a group in a sort of <= 65535 segments)
 constexpr int64_t kMaxN = (int64_t(1) << 31) - 1;
 constexpr int64_t kDefaultBudget = int64_t(2) << 30;
@@ -485,6 +749,11 @@ struct midagma_hsic {
   PinBuf<double> hvals;
   Event ev[3];
   double prof[4] = {0, 0, 0, 0};  // ms: medians, factorisation, permutations, evaluation
+  // all_pairs' scratch (grow-only) and times
+  DevBuf<double> usq, uent, ucov, ubia;
+  DevBuf<int2> utiles;
+  PinBuf<double> hcov, hbia;
+  double uprof[2] = {0, 0};  // ms: the tiled pass over the factors, the vectors and their Grams
 };
 
 // abi.h's hook: an entry's device work runs on the handle's device once a set_data* has opened it
@@ -964,6 +1233,256 @@ extern "C" int midagma_hsic_run(midagma_hsic* h, const int64_t* pairs, int64_t m
   });
   if (rc != MIDAGMA_OK) (void)hipStreamSynchronize(h->comp);  // leave nothing in flight that reads the scratch
   return rc;
+}
+
+namespace {
+
+// a column group of all_pairs with what the passes read of it (valid while its factors are held)
+struct UGroup {
+  std::vector<int64_t> cols;
+  int ns = 0, nv = 0;  // slabs of Phi, slabs of the vector panel
+  DevBuf<double> panel, scal, means;
+  DevBuf<UCol> ucols;
+  DevBuf<Slab> slabs, vslabs;
+  DevBuf<ColSlabs> cs;
+};
+
+float ms_between(hipEvent_t a, hipEvent_t b) {
+  float ms = 0.f;
+  HIP_TRY(hipEventElapsedTime(&ms, a, b));
+  return ms;
+}
+
+// the group's slab tables, the O(n) vectors of its columns (panel: n x 16 nv, column 2 k and
+// 2 k + 1 the vectors v~ and a of the group's column k) and their scalars; synchronises
+void build_group(midagma_hsic* h, UGroup& g) {
+  const int64_t n = h->n, nch = (n + FCH - 1) / FCH;
+  const int nc = (int)g.cols.size();
+  std::vector<Slab> slabs, vslabs;
+  std::vector<ColSlabs> cs;
+  std::vector<UCol> uc;
+  std::vector<double> means;
+  for (int64_t v : g.cols) {
+    const Factor& f = h->fac[v];
+    cs.push_back(ColSlabs{(int32_t)slabs.size(), f.rpad / 16});
+    uc.push_back(UCol{f.Fc.p, f.rpad, (int32_t)means.size()});
+    for (int s = 0; s < f.rpad / 16; ++s) slabs.push_back(Slab{f.Fc.p + 16 * s, f.rpad});
+    means.insert(means.end(), f.mean.begin(), f.mean.end());
+  }
+  g.ns = (int)slabs.size(), g.nv = (2 * nc + 15) / 16;
+  const int W = 16 * g.nv;
+  g.panel.alloc((size_t)(n * W)), g.scal.alloc((size_t)nc * 4), g.means.alloc(means.size());
+  g.ucols.alloc((size_t)nc), g.slabs.alloc(slabs.size()), g.vslabs.alloc((size_t)g.nv), g.cs.alloc((size_t)nc);
+  for (int s = 0; s < g.nv; ++s) vslabs.push_back(Slab{g.panel.p + 16 * s, W});
+  DevBuf<double> part;
+  part.alloc((size_t)(nc * nch * 2));
+  hipStream_t st = h->comp;
+  HIP_TRY(hipEventRecord(h->ev[0], st));
+  HIP_TRY(hipMemcpyAsync(g.means.p, means.data(), means.size() * sizeof(double), hipMemcpyHostToDevice, st));
+  HIP_TRY(hipMemcpyAsync(g.ucols.p, uc.data(), uc.size() * sizeof(UCol), hipMemcpyHostToDevice, st));
+  HIP_TRY(hipMemcpyAsync(g.slabs.p, slabs.data(), slabs.size() * sizeof(Slab), hipMemcpyHostToDevice, st));
+  HIP_TRY(hipMemcpyAsync(g.vslabs.p, vslabs.data(), vslabs.size() * sizeof(Slab), hipMemcpyHostToDevice, st));
+  HIP_TRY(hipMemcpyAsync(g.cs.p, cs.data(), cs.size() * sizeof(ColSlabs), hipMemcpyHostToDevice, st));
+  HIP_TRY(hipMemsetAsync(g.panel.p, 0, (size_t)(n * W) * sizeof(double), st));  // (the padding columns)
+  hipLaunchKernelGGL(hsic_u_rows_kernel, dim3((unsigned)nch, (unsigned)nc), dim3(HT), 0, st, g.ucols.p, g.means.p, n, nch,
+                     W, g.panel.p, part.p);
+  hipLaunchKernelGGL(hsic_u_scalars_kernel, dim3((unsigned)((nc + HT - 1) / HT)), dim3(HT), 0, st, g.ucols.p, g.means.p,
+                     part.p, n, nch, nc, g.scal.p);
+  hipLaunchKernelGGL(hsic_u_shift_kernel, dim3((unsigned)((n * nc + HT - 1) / HT)), dim3(HT), 0, st, g.scal.p, n, nc, W,
+                     g.panel.p);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipEventRecord(h->ev[1], st));
+  HIP_TRY(hipStreamSynchronize(st));  // (the host vectors and `part` end here)
+  h->uprof[1] += ms_between(h->ev[0], h->ev[1]);
+}
+
+// out = the chunk-summed sub-tiles of PA^T PB (squared and summed when sq) for the panels' slab
+// tables, the tiles on and above the diagonal only when `same`, in batches of tiles whose chunk
+// partials stay within ebudget (at least one tile)
+void tiled_gram(midagma_hsic* h, const Slab* sa, int nsA, const Slab* sb, int nsB, bool same, bool sq, int64_t ch,
+                int64_t ebudget, double* out) {
+  const int64_t n = h->n, nchunk = (n + ch - 1) / ch;
+  const int TA = (nsA + TS - 1) / TS, TB = (nsB + TS - 1) / TS;
+  std::vector<int2> tiles;
+  for (int a = 0; a < TA; ++a)
+    for (int b = same ? a : 0; b < TB; ++b) tiles.push_back(int2{a, b});
+  const int64_t nt = (int64_t)tiles.size();
+  h->utiles.alloc((size_t)nt);
+  HIP_TRY(hipMemcpyAsync(h->utiles.p, tiles.data(), nt * sizeof(int2), hipMemcpyHostToDevice, h->comp));
+  int64_t tmax = std::max<int64_t>(1, ebudget / (nchunk * TILE_E * 8));
+  tmax = std::min<int64_t>(std::min<int64_t>(tmax, 65535), std::max<int64_t>(1, kMaxN / nchunk));
+  for (int64_t t0 = 0; t0 < nt; t0 += tmax) {
+    const int nb = (int)std::min(tmax, nt - t0);
+    h->partial.alloc((size_t)(nchunk * nb * TILE_E));
+    hipLaunchKernelGGL(hsic_tile_kernel, dim3((unsigned)(nchunk * nb)), dim3(HT), 0, h->comp, sa, sb, h->utiles.p + t0, nb,
+                       nsA, nsB, n, ch, h->partial.p);
+    if (sq)
+      hipLaunchKernelGGL(hsic_tile_reduce_kernel<true>, dim3(TSUB, (unsigned)nb), dim3(HT), 0, h->comp, h->partial.p,
+                         h->utiles.p + t0, nb, nsA, nsB, nchunk, out);
+    else
+      hipLaunchKernelGGL(hsic_tile_reduce_kernel<false>, dim3(TSUB, (unsigned)nb), dim3(HT), 0, h->comp, h->partial.p,
+                         h->utiles.p + t0, nb, nsA, nsB, nchunk, out);
+    HIP_TRY(hipGetLastError());
+  }
+  HIP_TRY(hipStreamSynchronize(h->comp));  // (`tiles` ends here; h->partial may be regrown by the next call)
+}
+
+// cov_U and the biased statistic of every pair (a in A, b in B; A == B: b >= a) into the host
+// matrices (nu x nu, by the columns' places ua / ub in the call's list), mirrored
+void group_pair(midagma_hsic* h, const UGroup& A, const UGroup& B, const std::vector<int>& placeA,
+                const std::vector<int>& placeB, int64_t ch, int64_t ebudget, int64_t nu, double* cov, double* bia) {
+  const bool same = &A == &B;
+  const int nA = (int)A.cols.size(), nB = (int)B.cols.size();
+  const size_t np = (size_t)nA * nB;
+  h->usq.alloc((size_t)A.ns * B.ns), h->uent.alloc((size_t)A.nv * B.nv * 256);
+  h->ucov.alloc(np), h->ubia.alloc(np), h->hcov.alloc(np), h->hbia.alloc(np);
+  HIP_TRY(hipEventRecord(h->ev[0], h->comp));
+  tiled_gram(h, A.slabs.p, A.ns, B.slabs.p, B.ns, same, true, ch, ebudget, h->usq.p);
+  HIP_TRY(hipEventRecord(h->ev[1], h->comp));
+  tiled_gram(h, A.vslabs.p, A.nv, B.vslabs.p, B.nv, same, false, ch, ebudget, h->uent.p);
+  hipLaunchKernelGGL(hsic_u_combine_kernel, dim3((unsigned)((np + HT - 1) / HT)), dim3(HT), 0, h->comp, h->usq.p,
+                     h->uent.p, A.cs.p, B.cs.p, A.scal.p, B.scal.p, nA, nB, B.ns, B.nv, same ? 1 : 0, h->n, h->ucov.p,
+                     h->ubia.p);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipEventRecord(h->ev[2], h->comp));
+  HIP_TRY(hipMemcpyAsync(h->hcov.p, h->ucov.p, np * sizeof(double), hipMemcpyDeviceToHost, h->comp));
+  HIP_TRY(hipMemcpyAsync(h->hbia.p, h->ubia.p, np * sizeof(double), hipMemcpyDeviceToHost, h->comp));
+  HIP_TRY(hipStreamSynchronize(h->comp));
+  h->uprof[0] += ms_between(h->ev[0], h->ev[1]);
+  h->uprof[1] += ms_between(h->ev[1], h->ev[2]);
+  for (int a = 0; a < nA; ++a)
+    for (int b = same ? a : 0; b < nB; ++b) {
+      // a zero-range column: the centred matrix is exactly 0 (as midagma_hsic_run decides it)
+      const bool zero = h->hzr[A.cols[a]] || h->hzr[B.cols[b]];
+      const double c = zero ? 0.0 : h->hcov.p[(size_t)a * nB + b], s = zero ? 0.0 : h->hbia.p[(size_t)a * nB + b];
+      const int64_t ua = placeA[a], ub = placeB[b];
+      cov[ua * nu + ub] = cov[ub * nu + ua] = c;
+      bia[ua * nu + ub] = bia[ub * nu + ua] = s;
+    }
+}
+
+}  // namespace
+
+extern "C" int midagma_hsic_all_pairs(midagma_hsic* h, const int64_t* cols, int64_t ncols, double tol, int64_t chunk,
+                                      int64_t budget_bytes, double* cov_u_out, double* biased_out) {
+  if (!h) return abi_fail(no_handle<midagma_hsic>, MIDAGMA_E_ARG, "hsic_all_pairs: null handle");
+  if (!cov_u_out) return abi_fail(h, MIDAGMA_E_ARG, "hsic_all_pairs: null pointer");
+  if (cols && ncols < 0) return abi_fail(h, MIDAGMA_E_ARG, "hsic_all_pairs: ncols < 0");
+  if (const char* why = bad_tol(tol)) return abi_fail(h, MIDAGMA_E_ARG, std::string("hsic_all_pairs: ") + why);
+  if (chunk != 0 && (chunk < 16 || chunk > kMaxChunk || chunk % 16))
+    return abi_fail(h, MIDAGMA_E_ARG, "hsic_all_pairs: chunk must be 0 or a multiple of 16 in [16, 2^20]");
+  if (h->n == 0) return abi_fail(h, MIDAGMA_E_ARG, "hsic_all_pairs: set the data first");
+  if (h->n < 4) return abi_fail(h, MIDAGMA_E_ARG, "hsic_all_pairs: the U-centred statistic needs n >= 4");
+  if (!h->have_bw) return abi_fail(h, MIDAGMA_E_ARG, "hsic_all_pairs: set the bandwidths first");
+  const int64_t n = h->n, d = h->d, nout = cols ? ncols : d;
+  // the listed columns, each once, ascending (a pair's smaller column is always the A side, so its
+  // value does not depend on the list); place[k]: where entry k's column is
+  std::vector<int64_t> uniq;
+  std::vector<int64_t> place((size_t)nout), seen((size_t)d, -1);
+  for (int64_t k = 0; k < nout; ++k) {
+    const int64_t v = cols ? cols[k] : k;
+    if (v < 0 || v >= d) return abi_fail(h, MIDAGMA_E_ARG, "hsic_all_pairs: column index outside [0, d)");
+    seen[v] = 0;
+  }
+  for (int64_t v = 0; v < d; ++v)
+    if (seen[v] == 0) seen[v] = (int64_t)uniq.size(), uniq.push_back(v);
+  for (int64_t k = 0; k < nout; ++k) place[k] = seen[cols ? cols[k] : k];
+  h->prof[1] = h->uprof[0] = h->uprof[1] = 0.0;
+  if (nout == 0) return MIDAGMA_OK;
+  const int64_t nu = (int64_t)uniq.size();
+  const int64_t budget = budget_of(budget_bytes), fbudget = budget / 2, ebudget = budget - fbudget;
+  const int64_t ch = chunk ? chunk : chunk_rule(n);
+  std::vector<double> cov((size_t)(nu * nu), 0.0), bia((size_t)(nu * nu), 0.0);
+
+  const int rc = abi_guarded(h, [&] {
+    if (h->ftol != tol) {
+      drop_factors(h);
+      h->ftol = tol;
+    }
+    // column groups: every column at once if the factors and vectors fit half the budget (at the
+    // padded rank a column had before, 64 for one not factored yet), else consecutive groups of a
+    // quarter of it each, two of which are held at a time
+    auto bytes_of = [&](int64_t v) { return n * 8 * ((h->est_rpad[v] ? h->est_rpad[v] : 64) + 2); };
+    auto total_bytes = [&] {
+      int64_t t = 0;
+      for (int64_t v : uniq) t += bytes_of(v);
+      return t;
+    };
+    int64_t total = total_bytes();
+    if (total > fbudget) {
+      // groups are needed: size them by the ranks, not by the estimate (half as many columns a group,
+      // so twice the groups and four times the group pairs).  The columns not factored at this tol
+      // yet are factored once for their ranks, a budget's worth at a time, the others making room.
+      std::vector<int64_t> unknown;
+      for (int64_t v : uniq)
+        if (!h->est_rpad[v]) unknown.push_back(v);
+      for (size_t k0 = 0; k0 < unknown.size();) {
+        size_t k1 = k0;
+        for (int64_t b = 0; k1 < unknown.size() && (k1 == k0 || b + bytes_of(unknown[k1]) <= fbudget); ++k1)
+          b += bytes_of(unknown[k1]);
+        HIP_TRY(hipStreamSynchronize(h->comp));
+        for (int64_t v = 0; v < d; ++v)
+          if (h->fac[v].have) h->fac[v] = Factor{};
+        ensure_factors(h, std::vector<int64_t>(unknown.begin() + k0, unknown.begin() + k1), tol, fbudget);
+        k0 = k1;
+      }
+      total = total_bytes();
+    }
+    const int64_t cap = total <= fbudget ? total : fbudget / 2;
+    std::vector<std::vector<int>> groups(1);  // places in uniq
+    int64_t bytes = 0;
+    for (int64_t u = 0; u < nu; ++u) {
+      const int64_t add = bytes_of(uniq[u]);
+      if (!groups.back().empty() && bytes + add > cap) groups.emplace_back(), bytes = 0;
+      groups.back().push_back((int)u), bytes += add;
+    }
+    std::vector<uint8_t> keep((size_t)d);
+    // hold the factors of the marked columns (the others make room when one is missing), then the group's tables
+    auto load = [&](UGroup& g, const std::vector<int>& places) {
+      g.cols.clear();
+      for (int u : places) g.cols.push_back(uniq[u]);
+      bool all = true;
+      for (int64_t v : g.cols) all = all && h->fac[v].have;
+      if (!all) {
+        HIP_TRY(hipStreamSynchronize(h->comp));
+        for (int64_t v = 0; v < d; ++v)
+          if (!keep[v] && h->fac[v].have) h->fac[v] = Factor{};
+        ensure_factors(h, g.cols, tol, fbudget);
+      }
+      build_group(h, g);
+    };
+    for (size_t ga = 0; ga < groups.size(); ++ga) {
+      UGroup A;
+      std::fill(keep.begin(), keep.end(), 0);
+      for (int u : groups[ga]) keep[uniq[u]] = 1;
+      load(A, groups[ga]);
+      group_pair(h, A, A, groups[ga], groups[ga], ch, ebudget, nu, cov.data(), bia.data());
+      for (size_t gb = ga + 1; gb < groups.size(); ++gb) {
+        UGroup B;
+        std::fill(keep.begin(), keep.end(), 0);
+        for (int u : groups[ga]) keep[uniq[u]] = 1;
+        for (int u : groups[gb]) keep[uniq[u]] = 1;
+        load(B, groups[gb]);
+        group_pair(h, A, B, groups[ga], groups[gb], ch, ebudget, nu, cov.data(), bia.data());
+      }
+    }
+  });
+  if (rc != MIDAGMA_OK) {
+    (void)hipStreamSynchronize(h->comp);  // leave nothing in flight that reads the scratch
+    return rc;
+  }
+  for (int64_t k = 0; k < nout; ++k)
+    for (int64_t l = 0; l < nout; ++l) {
+      cov_u_out[k * nout + l] = cov[(size_t)(place[k] * nu + place[l])];
+      if (biased_out) biased_out[k * nout + l] = bia[(size_t)(place[k] * nu + place[l])];
+    }
+  return MIDAGMA_OK;
+}
+
+extern "C" int midagma_hsic_all_pairs_profile(const midagma_hsic* h, double* ms_out) {
+  if (!h || !ms_out) return abi_fail(no_handle<midagma_hsic>, MIDAGMA_E_ARG, "hsic_all_pairs_profile: bad arguments");
+  ms_out[0] = h->prof[1], ms_out[1] = h->uprof[0], ms_out[2] = h->uprof[1];
+  return MIDAGMA_OK;
 }
 
 extern "C" int midagma_hsic_perms(midagma_hsic* h, int64_t q, int64_t P, uint64_t seed, int32_t* perms_out) {

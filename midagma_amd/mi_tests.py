@@ -29,7 +29,9 @@ column's RBF Gram matrix is replaced by a pivoted incomplete Cholesky factor wit
 <= tol, and an evaluation becomes a small FP64 MFMA GEMM over gathered factor rows.  The statistic is
 the reference's to within 4 tol (1 + tol) plus rounding ("HSIC from low-rank factors"),
 the median bandwidths are the reference's bit for bit, at any n < 2^31.  They too change nothing of
-the functions above.
+the functions above.  `hsic_tests(pvalue="chi2")` tests every pair with one evaluation and no
+permutations: the chi-square test of `dcor_tests(pvalue="chi2")` on the U-centred RBF kernel, from
+one tiled FP64 MFMA pass over all the factors ("HSIC chi-square test for every pair").
 
 One keyword is added, ``perms``:
   * ``"numpy"`` (default): the host draws ``rng = np.random.default_rng(seed)`` once and calls
@@ -606,17 +608,26 @@ def hsic_null(X, pairs, *, num_perm: int = 200, seed: int = 0, perms="numpy", to
         eng.close()
 
 
-def hsic_tests(X, *, num_perm: int = 200, seed: int = 0, perms="device", tol: float = 1e-13, device: int = 0,
-               budget_bytes: int = 0, sigma2=None):
-    """(stat, p), two d x d host arrays: the HSIC permutation test (`hsic_null`) of every pair i < j
-    of X's columns, in the reference's pair order, mirrored to (j, i), p = (ge + 1) / (num_perm + 1).
-    A pair with a zero-range column is (0, 1).  The diagonal is (nan, 0) by rule: the reference
-    tests no column against itself."""
+def hsic_tests(X, *, pvalue: str = "permutation", num_perm: int = 200, seed: int = 0, perms="device",
+               tol: float = 1e-13, device: int = 0, budget_bytes: int = 0, sigma2=None):
+    """(stat, p), two d x d host arrays: the HSIC test of every pair i < j of X's columns, in the
+    reference's pair order, mirrored to (j, i).  A pair with a zero-range column is (0, 1).  The
+    diagonal is (nan, 0) by rule: the reference tests no column against itself.
+    pvalue="permutation": the permutation test (`hsic_null`), p = (ge + 1) / (num_perm + 1).
+    pvalue="chi2": one evaluation a pair, no permutations (`HipHsic.all_pairs`, one tiled pass over
+    all the factors): stat is the bias-corrected correlation R_U of the distances D = 1 - K (hyppo's
+    Hsic convention) and p = chi2.sf(n R_U + 1, 1), the chi-square test of Shen, Panda and
+    Vogelstein that `dcor_tests(pvalue="chi2")` uses, which holds for any characteristic kernel.  It
+    is not in the reference, which has only the permutation test.  n < 4 raises ValueError."""
+    if pvalue not in ("permutation", "chi2"):
+        raise ValueError("pvalue must be 'permutation' or 'chi2'")
     if isinstance(perms, str) and perms not in ("numpy", "device"):
         raise ValueError("perms must be 'numpy' or 'device'")
     _check_hsic_args(perms, num_perm, tol, 0)
     X = _as_data(X, max_n=None)
-    d = int(X.shape[1])
+    n, d = int(X.shape[0]), int(X.shape[1])
+    if pvalue == "chi2" and n < 4:
+        raise ValueError("the chi-square test needs n >= 4")
     P = int(num_perm)
     iu = np.triu_indices(d, 1)
     pairs = np.stack(iu, axis=1).astype(np.int64)
@@ -624,23 +635,42 @@ def hsic_tests(X, *, num_perm: int = 200, seed: int = 0, perms="device", tol: fl
     if len(pairs):
         eng = _hsic_engine(X, device, budget_bytes, None, sigma2)
         try:
-            s, ge, _ = _hsic_null(eng, pairs, P, seed, perms, float(tol), budget_bytes, False, 0)
+            if pvalue == "chi2":
+                cov, _ = eng.all_pairs(None, tol=float(tol), budget_bytes=budget_bytes)
+            else:
+                s, ge, _ = _hsic_null(eng, pairs, P, seed, perms, float(tol), budget_bytes, False, 0)
         finally:
             eng.close()
-        pv = (ge + 1.0) / (P + 1.0)
+        if pvalue == "chi2":
+            from scipy import stats
+            s = _r_u(cov)[iu]
+            zero = _zero_range(X)  # (their R_U is 0 by rule, and the rule's p is 1, not chi2.sf(1))
+            pv = np.where(zero[iu[0]] | zero[iu[1]], 1.0, stats.chi2.sf(n * s + 1.0, 1))
+        else:
+            pv = (ge + 1.0) / (P + 1.0)
         stat[iu], p[iu] = s, pv
         stat.T[iu], p.T[iu] = s, pv
     return stat, p
 
 
-def get_I_from_hsic_tests(X, *, alpha: float = 0.05, num_perm: int = 200, seed: int = 0, perms="device",
-                          bonferroni: bool = True, undirected: bool = True, exclude_diagonal: bool = True,
-                          tol: float = 1e-13, device: int = 0) -> np.ndarray:
+def _r_u(cov: np.ndarray) -> np.ndarray:
+    """R_U = cov_U(x, y) / sqrt(cov_U(x, x) cov_U(y, y)) from the matrix of U-centred covariances;
+    0 where either variance is <= 0."""
+    var = np.diag(cov)
+    den = var[:, None] * var[None, :]
+    ok = (var[:, None] > 0) & (var[None, :] > 0)
+    return np.where(ok, cov / np.sqrt(np.where(ok, den, 1.0)), 0.0)
+
+
+def get_I_from_hsic_tests(X, *, alpha: float = 0.05, pvalue: str = "permutation", num_perm: int = 200,
+                          seed: int = 0, perms="device", bonferroni: bool = True, undirected: bool = True,
+                          exclude_diagonal: bool = True, tol: float = 1e-13, device: int = 0) -> np.ndarray:
     """`get_I_from_full_pairwise_tests(test="hsic")` through `hsic_tests`: I = {(i, j): p > alpha_eff}
     in the reference's pair order (alpha_eff = alpha / #pairs under Bonferroni; the same dtype and
     shape, the empty case included).  With perms="numpy" and undirected=True the p-values are
-    `permutation_null`'s wherever no permuted value is within 4 tol (1 + tol) of the observed one."""
-    _, p = hsic_tests(X, num_perm=num_perm, seed=seed, perms=perms, tol=tol, device=device)
+    `permutation_null`'s wherever no permuted value is within 4 tol (1 + tol) of the observed one.
+    pvalue="chi2": the chi-square test's p-values, one evaluation a pair."""
+    _, p = hsic_tests(X, pvalue=pvalue, num_perm=num_perm, seed=seed, perms=perms, tol=tol, device=device)
     return _I_from_pvalues(p, alpha, bonferroni, undirected, exclude_diagonal)
 
 

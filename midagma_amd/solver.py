@@ -938,7 +938,7 @@ class HipDcor(_Handle):
 class HipHsic(_Handle):
     """HSIC permutation tests of pairs of columns from low-rank factors of the RBF Gram matrices, on
     one GPU (`midagma_hsic_*`, csrc/hsic.hip): the engine under `mi_tests.hsic_null` / `hsic_tests`,
-    for 2 <= n < 2^31.  Holds the columns of X by row and sorted (16 bytes a value) and the centred
+    for 2 <= n < 2^31, and the chi-square test's statistic of every pair at once (`all_pairs`).  Holds the columns of X by row and sorted (16 bytes a value) and the centred
     factors of the columns in use (8 n r_pad bytes each).
 
     X is a host array (copied to `device`), or a 2-d float64 torch CUDA tensor: the engine then
@@ -1054,6 +1054,27 @@ class HipHsic(_Handle):
         self._check(rc, self.h, "hsic_run")
         return (stat, ge, null) if return_null else (stat, ge)
 
+    def all_pairs(self, cols=None, *, tol: float = TOL, chunk: int = 0, budget_bytes: int = 0):
+        """(cov_u, biased), two k x k host arrays over the listed columns (None: all d): cov_u is
+        the U-centred covariance <A~_i, A~_j> / (n (n - 3)) of the distances D = 1 - K (the
+        variances on the diagonal), the statistic of the chi-square test; biased is `run`'s
+        statistic || Fc_i^T Fc_j ||_F^2 / n^2.  One tiled FP64 MFMA pass over the centred factors
+        side by side, one evaluation a pair; needs n >= 4.  chunk: rows per partial product (0:
+        the rule).  The bits do not depend on budget_bytes or on the other columns listed."""
+        if cols is None:
+            cp, k = None, self.d
+        else:
+            cols = np.ascontiguousarray(cols, dtype=np.int64).ravel()
+            k = int(cols.size)
+            if k == 0:
+                return np.zeros((0, 0)), np.zeros((0, 0))
+            cp = C.c_void_p(cols.ctypes.data)
+        cov, bia = np.zeros((k, k)), np.zeros((k, k))
+        rc = self.L.midagma_hsic_all_pairs(self.h, cp, k, float(tol), int(chunk), int(budget_bytes), dptr(cov),
+                                           dptr(bia))
+        self._check(rc, self.h, "hsic_all_pairs")
+        return cov, bia
+
     def device_perms(self, q: int, P: int, seed: int = 0):
         """The P device permutations (P x n int32) of pair q of a call with this seed."""
         out = np.zeros((int(P), self.n), dtype=np.int32)
@@ -1068,6 +1089,13 @@ class HipHsic(_Handle):
         ms = np.zeros(4)
         self._check(self.L.midagma_hsic_profile(self.h, dptr(ms)), self.h, "hsic_profile")
         return dict(zip(("median_ms", "factor_ms", "perm_ms", "eval_ms"), ms.tolist()))
+
+    def all_pairs_profile(self) -> dict:
+        """Times in ms of the last `all_pairs`: the factorisation, the tiled pass over the factors,
+        and the O(n) vectors with their Grams (diagnostics)."""
+        ms = np.zeros(3)
+        self._check(self.L.midagma_hsic_all_pairs_profile(self.h, dptr(ms)), self.h, "hsic_all_pairs_profile")
+        return dict(zip(("factor_ms", "tile_ms", "vector_ms"), ms.tolist()))
 
 
 class HipBatch(_Handle):
