@@ -495,15 +495,26 @@ __global__ __launch_bounds__(64 * NW) void small_minimize_kernel(
       double x0[E], r[E];
       // ||R||: d max|R_ij| against 1e-2 (the series converges in the passes below) and 1e-4
       // (a third pass); rounding of d x is monotone, so max_ij(d |R_ij|) = d max_ij |R_ij| and
-      // the two tests are lane tests, reduced by ballots (a wave max took 6 dependent shuffles)
-      bool big2 = false, big4 = false;
+      // the two tests are lane tests, reduced by ballots (a wave max took 6 dependent shuffles).
+      // max|X0| > 512 falls back as well, a guard against extreme conditioning: the series is
+      // one-sided, S Y = I - R^(2^p) up to the rounding dR of R (~u |S||X0|), but Y S - I =
+      // inv(S) dR S is that amplified by |inv(S)||S|.  Measured (tests/test_gpu_small_inverse.py):
+      // two-sided residual <= 6x LAPACK's wherever max|inv| <= 100, 8.05 - 13.3x on some slots at
+      // 546 - 1213 (cond_1 1.8e4 - 8e4); the forward error stays under LAPACK's throughout.  max|inv|
+      // is no sharp predictor (long weighted paths make it large at rho = 0 too), so the bound sits
+      // above what the measured default fits at d = 20 .. 64 reach (batched fits): a
+      // Gauss-Jordan slot costs 5x a series slot, and at 128 a default fit at d = 32 took 23 % longer.
+      // (One compare on the lane's max, taken off the products' path; a NaN in X0 is one in R.)
+      double xmax = 0.0;
 #pragma unroll
       for (int e = 0; e < E; ++e) {
         const int i = rows[e], j = cols[e];
         x0[e] = real[e] ? (warm >= 2 ? 2.0 * p1[e] - p2[e] : p1[e]) : ((i == j) ? 1.0 : 0.0);
         PA[1][i * SW + j] = a[e];
         PB[1][i * SB + j] = x0[e];
+        xmax = fmax(xmax, fabs(x0[e]));
       }
+      bool big2 = !(xmax <= 512.0), big4 = false;
       __syncthreads();
 #pragma unroll
       for (int u = 0; u < TPW; ++u) {

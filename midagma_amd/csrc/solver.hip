@@ -622,10 +622,13 @@ extern "C" int midagma_debug_at_fold(midagma_solver* s, int on) {
 // (every inverse path ends in Mt: launch_blocked_inverse's ping-pong starts in
 // binv_build_target, so its K2 flips land there, also when outer step 0 read A0; the updates
 // only read it) and W the slot's updated W, the next slot's input.  Enqueues no kernel and
-// changes no state.  -1: no handle, no slot run since the last begin (Mt would be stale), or
-// the one-workgroup loop (small.hip), which keeps its inverse in LDS.
+// changes no state.  The one-workgroup loop (small.hip) keeps its inverse in registers and has no
+// Mt: there Mt is the d x d corner of the first DS x DS image of sprev (row stride DS =
+// small_block(d)), the kernel's p1, which every launch writes at its end: the inverse of the W
+// its last slot started from, also when that slot halved or reverted.  -1: no handle, or no slot
+// run since the last begin (Mt would be stale).
 extern "C" int midagma_debug_slot_matrices(midagma_solver* s, double* W_out, double* Mt_out) {
-  if (!s || s->bc_len == 0 || s->small_on()) return -1;  // (bc_len: set by the first begin)
+  if (!s || s->bc_len == 0) return -1;  // (bc_len: set by the first begin)
   if (hipSetDevice(s->device) != hipSuccess) return -1;
   if (hipStreamSynchronize(s->stream) != hipSuccess) return -1;
   if (s->side && hipStreamSynchronize(s->side) != hipSuccess) return -1;
@@ -634,7 +637,11 @@ extern "C" int midagma_debug_slot_matrices(midagma_solver* s, double* W_out, dou
   if (st.slots < 1) return -1;
   const size_t row = (size_t)s->d * sizeof(double), pitch = (size_t)s->D * sizeof(double);
   if (W_out && hipMemcpy2D(W_out, row, s->W.p, pitch, row, s->d, hipMemcpyDeviceToHost) != hipSuccess) return -1;
-  if (Mt_out && hipMemcpy2D(Mt_out, row, s->Mt.p, pitch, row, s->d, hipMemcpyDeviceToHost) != hipSuccess) return -1;
+  const bool small = s->small_on();
+  if (small && !s->sprev.p) return -1;
+  const double* const Mt = small ? s->sprev.p : s->Mt.p;
+  const size_t mpitch = small ? (size_t)small_block(s->d) * sizeof(double) : pitch;
+  if (Mt_out && hipMemcpy2D(Mt_out, row, Mt, mpitch, row, s->d, hipMemcpyDeviceToHost) != hipSuccess) return -1;
   return 0;
 }
 

@@ -401,7 +401,9 @@ class HipSolver(_Handle):
     def debug_slot_matrices(self):
         """Test hook (read-only): (W, Mt) as the last slot left them on the device, d x d each.  Mt is
         inv(sI - W∘W)^T for the W that slot started from, W the slot's updated W (the next slot's
-        input).  Waits for the solver's streams; raises when no slot has run since begin."""
+        input).  On the one-workgroup small-d loop Mt is the inverse the last launch stored for the
+        next launch's warm start (of the W its last slot started from, also after a halving).
+        Waits for the solver's streams; raises when no slot has run since begin."""
         W, Mt = np.empty((self.d, self.d)), np.empty((self.d, self.d))
         if self.L.midagma_debug_slot_matrices(self.h, dptr(W), dptr(Mt)) != 0:
             raise _lib.HipSolverError("debug_slot_matrices: no slot has run since begin (or no Mt buffer)")
