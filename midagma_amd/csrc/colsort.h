@@ -1,5 +1,5 @@
 // The segmented stable LSD radix sort of corr.hip, for the other files that sort on the device
-// (dcor.hip: the columns' argsort and the Philox keys of its permutations).
+// (dcor.hip and hsic.hip: the columns' argsort; coltest.h: the Philox keys of their permutations).
 //
 // nseg segments of n (64-bit key, 32-bit payload) records each, segment c at offset c n of every
 // buffer.  The records start in K0 / I0; a pass that moves a segment writes it to the other side,

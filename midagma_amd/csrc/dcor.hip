@@ -42,10 +42,7 @@
 #include <vector>
 
 #include "../../include/midagma_hip.h"
-#include "colsort.h"
-#include "devmem.h"
-#include "launch.h"
-#include "philox.h"
+#include "coltest.h"
 
 namespace midagma {
 namespace {
@@ -54,19 +51,6 @@ constexpr int DT = 256;      // threads of the pre-pass kernels
 constexpr int MAXB = 1024;   // the largest block edge
 constexpr int PCH = 4 * DT;  // sorted elements per pre-pass chunk, 4 consecutive ones a thread
 constexpr int PT = 64;       // tile edge of the prefix along the bins
-
-// the sum of v over the workgroup (any multiple of 64 threads up to 256) in a fixed order: the
-// butterfly within a wave, then the waves ascending; valid in every thread; w: 4 doubles of LDS
-__device__ __forceinline__ double wg_sum(double v, double* w) {
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off);
-  __syncthreads();  // (w may still be read from a previous call)
-  if ((threadIdx.x & 63) == 0) w[threadIdx.x >> 6] = v;
-  __syncthreads();
-  double s = w[0];
-  for (int k = 1, nw = blockDim.x >> 6; k < nw; ++k) s += w[k];
-  return s;
-}
 
 // --- the per-column pre-pass --------------------------------------------------------------------
 // part[v nch + chunk] = the sum of the chunk's sorted values of column v; CENTRED: of the values
@@ -202,18 +186,7 @@ __global__ __launch_bounds__(DT) void dcor_colstat_kernel(const double* __restri
   zr[v] = X[(int64_t)order[v * n] * ld + v] == X[(int64_t)order[v * n + n - 1] * ld + v] ? 1 : 0;
 }
 
-// --- permutations -------------------------------------------------------------------------------
-// the sort records of permutations f0 .. f0 + nseg - 1 (f = q P + p): K0[seg n + a] = (o.x << 32) | o.y,
-// o = Philox4x32-10(counter (q, p, a, 0), key (k0, k1)), I0[seg n + a] = a.  grid (ceil(n / DT), nseg)
-__global__ __launch_bounds__(DT) void dcor_keys_kernel(uint32_t k0, uint32_t k1, int64_t f0, int64_t n, int64_t P,
-                                                       uint64_t* __restrict__ K0, uint32_t* __restrict__ I0) {
-  const int64_t a = (int64_t)blockIdx.x * DT + threadIdx.x, f = f0 + blockIdx.y;
-  if (a >= n) return;
-  const U4 o = philox4x32_10(U4{(uint32_t)(f / P), (uint32_t)(f % P), (uint32_t)a, 0u}, k0, k1);
-  K0[(int64_t)blockIdx.y * n + a] = ((uint64_t)o.x << 32) | o.y;
-  I0[(int64_t)blockIdx.y * n + a] = (uint32_t)a;
-}
-
+// --- permutations (coltest.h makes the device's) --------------------------------------------------
 // inv[seg n + perm[seg n + a]] = a (the host checked that every row is a permutation of [0, n))
 __global__ __launch_bounds__(DT) void dcor_invert_kernel(const int32_t* __restrict__ perm, int64_t n,
                                                          int32_t* __restrict__ inv) {
@@ -471,38 +444,52 @@ __global__ __launch_bounds__(DT) void dcor_value_kernel(const double* __restrict
   }
 }
 
-constexpr int64_t kMaxD = 65535, kMaxP = 65535, kMaxChunk = 16383;  // (4 tables an evaluation in a grid dimension of 65535)
-constexpr int64_t kMaxN = (int64_t(1) << 31) - 1;
-constexpr int64_t kDefaultBudget = int64_t(2) << 30;
+constexpr int64_t kMaxChunk = 16383;  // (4 tables an evaluation in a grid dimension of 65535)
 
 }  // namespace
 }  // namespace midagma
 
 using namespace midagma;
 
-struct midagma_dcor {
-  int device = 0;
-  int64_t n = 0, d = 0;
-  std::string err;
-  hipStream_t comp = nullptr;
+struct midagma_dcor : ColHandle {
   DevBuf<double> xc, rs, cs;       // d x n centred values and row sums (by row), 4 scalars a column
   DevBuf<int32_t> order, pos, zr;  // d x n argsort and positions, the zero-range marks
-  std::vector<double> hcs;         // host copies of cs and zr
-  std::vector<int32_t> hzr;
+  std::vector<double> hcs;         // the host copy of cs
   // a run's scratch (kept between runs, grow-only)
   DevBuf<int64_t> dpairs;
-  DevBuf<int32_t> perm, inv;
+  DevBuf<int32_t> inv;
   DevBuf<double> tab, part, vals;
-  DevBuf<uint64_t> skeys;
-  DevBuf<uint32_t> sidx, shist;
-  DevBuf<unsigned long long> soa;
   PinBuf<double> hvals;
+  void prepare(const double* X, int64_t n, int64_t d, int64_t ld, int64_t budget, hipStream_t st);
 };
 
-// abi.h's hook: an entry's device work runs on the handle's device once a set_data* has opened it
-// (before that the handle's index may name no device, and no entry has device work)
-static void abi_select_device(const midagma_dcor* h) {
-  if (h->comp) HIP_TRY(hipSetDevice(h->device));
+// the per-column pre-pass from X_dev (n x d, ld) on stream st; the stream is synchronised
+void midagma_dcor::prepare(const double* X, int64_t n, int64_t d, int64_t ld, int64_t budget, hipStream_t st) {
+  const size_t nd = (size_t)n * d;
+  const int64_t nch = (n + PCH - 1) / PCH;
+  order.alloc(nd);
+  colargsort_run(X, n, d, ld, order.p, budget, st);  // (throws on inf / nan)
+  xc.alloc(nd), rs.alloc(nd), pos.alloc(nd);
+  cs.alloc(4 * d), zr.alloc(d);
+  DevBuf<double> part, part3, mean, tot;
+  part.alloc((size_t)(nch * d)), part3.alloc((size_t)(3 * nch * d)), mean.alloc(d), tot.alloc(d);
+  const dim3 chunks((unsigned)nch, (unsigned)d), cols((unsigned)((d + DT - 1) / DT));
+  hipLaunchKernelGGL(dcor_chunksum_kernel<false>, chunks, dim3(DT), 0, st, X, ld, order.p, n, nch, nullptr, nullptr,
+                     part.p);
+  hipLaunchKernelGGL(dcor_mean_kernel, cols, dim3(DT), 0, st, part.p, nch, d, (double)n, mean.p);
+  hipLaunchKernelGGL(dcor_chunksum_kernel<true>, chunks, dim3(DT), 0, st, X, ld, order.p, n, nch, mean.p, xc.p,
+                     part.p);
+  hipLaunchKernelGGL(dcor_scan_kernel, cols, dim3(DT), 0, st, part.p, nch, d, tot.p);
+  hipLaunchKernelGGL(dcor_rowsum_kernel, chunks, dim3(DT), 0, st, xc.p, order.p, n, nch, part.p, tot.p, rs.p,
+                     pos.p, part3.p);
+  hipLaunchKernelGGL(dcor_colstat_kernel, cols, dim3(DT), 0, st, part3.p, tot.p, X, ld, order.p, n, nch, d, cs.p,
+                     zr.p);
+  HIP_TRY(hipGetLastError());
+  hcs.resize(4 * d), hzr.resize(d);
+  HIP_TRY(hipMemcpyAsync(hcs.data(), cs.p, 4 * d * sizeof(double), hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipMemcpyAsync(hzr.data(), zr.p, d * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));  // (the scratch is freed on return)
+  this->n = n, this->d = d;
 }
 
 namespace {
@@ -512,43 +499,6 @@ int block_edge(int64_t n) {
   int64_t m = 64;
   while (m < MAXB && m * m < n) m <<= 1;
   return (int)m;
-}
-
-const char* bad_shape(const void* X, int64_t n, int64_t d, int64_t ld) {
-  if (!X) return "null pointer";
-  if (n < 2 || n > kMaxN) return "need 2 <= n < 2^31 rows";
-  if (d < 1 || d > kMaxD) return "need 1 <= d <= 65535 columns";
-  if (ld < d) return "the leading dimension is below d";
-  return nullptr;
-}
-
-// the per-column pre-pass from X_dev (n x d, ld) on stream st; the stream is synchronised
-void prepare(midagma_dcor* h, const double* X, int64_t n, int64_t d, int64_t ld, int64_t budget, hipStream_t st) {
-  const size_t nd = (size_t)n * d;
-  const int64_t nch = (n + PCH - 1) / PCH;
-  h->order.alloc(nd);
-  colargsort_run(X, n, d, ld, h->order.p, budget, st);  // (throws on inf / nan)
-  h->xc.alloc(nd), h->rs.alloc(nd), h->pos.alloc(nd);
-  h->cs.alloc(4 * d), h->zr.alloc(d);
-  DevBuf<double> part, part3, mean, tot;
-  part.alloc((size_t)(nch * d)), part3.alloc((size_t)(3 * nch * d)), mean.alloc(d), tot.alloc(d);
-  const dim3 chunks((unsigned)nch, (unsigned)d), cols((unsigned)((d + DT - 1) / DT));
-  hipLaunchKernelGGL(dcor_chunksum_kernel<false>, chunks, dim3(DT), 0, st, X, ld, h->order.p, n, nch, nullptr, nullptr,
-                     part.p);
-  hipLaunchKernelGGL(dcor_mean_kernel, cols, dim3(DT), 0, st, part.p, nch, d, (double)n, mean.p);
-  hipLaunchKernelGGL(dcor_chunksum_kernel<true>, chunks, dim3(DT), 0, st, X, ld, h->order.p, n, nch, mean.p, h->xc.p,
-                     part.p);
-  hipLaunchKernelGGL(dcor_scan_kernel, cols, dim3(DT), 0, st, part.p, nch, d, tot.p);
-  hipLaunchKernelGGL(dcor_rowsum_kernel, chunks, dim3(DT), 0, st, h->xc.p, h->order.p, n, nch, part.p, tot.p, h->rs.p,
-                     h->pos.p, part3.p);
-  hipLaunchKernelGGL(dcor_colstat_kernel, cols, dim3(DT), 0, st, part3.p, tot.p, X, ld, h->order.p, n, nch, d, h->cs.p,
-                     h->zr.p);
-  HIP_TRY(hipGetLastError());
-  h->hcs.resize(4 * d), h->hzr.resize(d);
-  HIP_TRY(hipMemcpyAsync(h->hcs.data(), h->cs.p, 4 * d * sizeof(double), hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipMemcpyAsync(h->hzr.data(), h->zr.p, d * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipStreamSynchronize(st));  // (the scratch is freed on return)
-  h->n = n, h->d = d;
 }
 
 struct RunPlan {
@@ -562,7 +512,7 @@ RunPlan run_plan(int64_t n, int64_t P, int block, bool device_perms, int64_t bud
   if (budget <= 0) budget = kDefaultBudget;
   p.m = block ? block : block_edge(n);
   p.K = (n + p.m - 1) / p.m;
-  p.sort_bytes = (P > 0 && device_perms) ? 2 * n * 8 + 2 * n * 4 + segsort_hist_per_segment(n) * 4 + 16 : 0;
+  p.sort_bytes = (P > 0 && device_perms) ? perm_sort_bytes(n) : 0;
   const int64_t per = 4 * p.K * p.K * 8 + 4 * p.K * 8 + 16 + (P > 0 ? 2 * n * 4 : 0) + p.sort_bytes;
   p.evals = std::max<int64_t>(1, std::min<int64_t>(kMaxChunk, budget / per));
   return p;
@@ -583,79 +533,21 @@ void launch_passes(midagma_dcor* h, const RunPlan& pl, int threads, int64_t e0, 
   HIP_TRY(hipGetLastError());
 }
 
-// permutations f0 .. f0 + nf - 1 of (seed) into h->perm and h->inv, on the handle's stream
-void device_perms(midagma_dcor* h, uint64_t seed, int64_t f0, int64_t nf, int64_t P) {
-  const int64_t n = h->n, hs = segsort_hist_per_segment(n);
-  h->skeys.alloc((size_t)(2 * nf * n)), h->sidx.alloc((size_t)(2 * nf * n));
-  h->shist.alloc((size_t)(nf * hs)), h->soa.alloc((size_t)(2 * nf));
-  const SegSort s{h->skeys.p, h->skeys.p + nf * n, h->sidx.p, h->sidx.p + nf * n, h->soa.p, h->soa.p + nf, h->shist.p};
-  // (every pass live: random keys share no digit, and a pass that moves nothing is still a stable pass)
-  HIP_TRY(hipMemsetAsync(s.key_or, 0xff, (size_t)nf * 8, h->comp));
-  HIP_TRY(hipMemsetAsync(s.key_and, 0, (size_t)nf * 8, h->comp));
-  hipLaunchKernelGGL(dcor_keys_kernel, dim3((unsigned)((n + DT - 1) / DT), (unsigned)nf), dim3(DT), 0, h->comp,
-                     (uint32_t)seed, (uint32_t)(seed >> 32), f0, n, P, s.K0, s.I0);
-  HIP_TRY(hipGetLastError());
-  launch_segsort(s, n, nf, h->comp);
-  launch_segsort_payload(s, n, nf, h->perm.p, h->inv.p, h->comp);
-}
-
-// the first set_data* opens the handle's device and makes its stream
-void open_handle(midagma_dcor* h) {
-  open_device(h->device, "");
-  if (!h->comp) HIP_TRY(hipStreamCreateWithFlags(&h->comp, hipStreamNonBlocking));
-}
-
 }  // namespace
 
 extern "C" const char* midagma_dcor_last_error(const midagma_dcor* h) { return abi_last_error(h); }
 
-extern "C" void midagma_dcor_destroy(midagma_dcor* h) {
-  if (!h) return;
-  if (h->comp) {  // (a handle that never opened its device owns nothing there, and its index may name none)
-    (void)hipSetDevice(h->device);
-    (void)hipStreamSynchronize(h->comp);
-    (void)hipStreamDestroy(h->comp);
-  }
-  delete h;
-}
+extern "C" void midagma_dcor_destroy(midagma_dcor* h) { col_destroy(h); }
 
-// (no device call: the device is opened by the first set_data*, so the argument checks of every
-// entry can be exercised on a machine without one)
-extern "C" int midagma_dcor_create(midagma_dcor** out, int device) {
-  if (!out || device < 0) return abi_fail(no_handle<midagma_dcor>, MIDAGMA_E_ARG, "dcor_create: bad arguments");
-  *out = new midagma_dcor;
-  (*out)->device = device;
-  return MIDAGMA_OK;
-}
+extern "C" int midagma_dcor_create(midagma_dcor** out, int device) { return col_create(out, device, "dcor_create"); }
 
 extern "C" int midagma_dcor_set_data(midagma_dcor* h, const double* X, int64_t n, int64_t d, int64_t budget_bytes) {
-  if (!h) return abi_fail(no_handle<midagma_dcor>, MIDAGMA_E_ARG, "dcor_set_data: null handle");
-  if (const char* why = bad_shape(X, n, d, d)) return abi_fail(h, MIDAGMA_E_ARG, std::string("dcor_set_data: ") + why);
-  h->n = h->d = 0;
-  return abi_guarded(h, [&] {
-    open_handle(h);
-    HIP_TRY(hipStreamSynchronize(h->comp));
-    DevBuf<double> Xd;
-    Xd.alloc((size_t)n * d);
-    HIP_TRY(hipMemcpyAsync(Xd.p, X, (size_t)n * d * sizeof(double), hipMemcpyHostToDevice, h->comp));
-    prepare(h, Xd.p, n, d, d, budget_bytes, h->comp);
-  });
+  return col_set_data(h, "dcor_set_data", X, n, d, budget_bytes);
 }
 
 extern "C" int midagma_dcor_set_data_dev(midagma_dcor* h, const double* X_dev, int64_t n, int64_t d, int64_t ld,
                                          int64_t budget_bytes, void* hip_stream) {
-  if (!h) return abi_fail(no_handle<midagma_dcor>, MIDAGMA_E_ARG, "dcor_set_data_dev: null handle");
-  if (const char* why = bad_shape(X_dev, n, d, ld))
-    return abi_fail(h, MIDAGMA_E_ARG, std::string("dcor_set_data_dev: ") + why);
-  h->n = h->d = 0;  // the handle holds no data until the new one is checked
-  return abi_guarded(h, [&] {
-    open_handle(h);
-    require_device_memory(X_dev, h->device, "dcor_set_data_dev");
-    HIP_TRY(hipStreamSynchronize(h->comp));  // nothing of an earlier run still reads the columns' arrays
-    // on the caller's stream, behind X's producer; prepare's synchronise (the marks are read on the
-    // host) also orders the arrays before everything the handle's own stream runs later
-    prepare(h, X_dev, n, d, ld, budget_bytes, static_cast<hipStream_t>(hip_stream));
-  });
+  return col_set_data_dev(h, "dcor_set_data_dev", X_dev, n, d, ld, budget_bytes, hip_stream);
 }
 
 namespace {
@@ -703,7 +595,7 @@ extern "C" int midagma_dcor_run(midagma_dcor* h, const int64_t* pairs, int64_t m
   const int rc = abi_guarded(h, [&] {
     h->dpairs.alloc((size_t)(2 * m));
     HIP_TRY(hipMemcpyAsync(h->dpairs.p, pairs, 2 * m * sizeof(int64_t), hipMemcpyHostToDevice, h->comp));
-    double obs = 0.0;  // the observed value of the pair whose permutations are being counted
+    NullCount count{stat, ge, null_out, P};
     for (int64_t e0 = 0; e0 < total; e0 += pl.evals) {
       const int64_t ne = std::min(pl.evals, total - e0), e1 = e0 + ne;
       // the chunk's permutations: f = e - q - 1 for p >= 1, ascending with e
@@ -715,7 +607,7 @@ extern "C" int midagma_dcor_run(midagma_dcor* h, const int64_t* pairs, int64_t m
       if (nf > 0) {
         h->perm.alloc((size_t)(nf * n)), h->inv.alloc((size_t)(nf * n));
         if (dev_perms) {
-          device_perms(h, seed, f0, nf, P);
+          h->sort.run(seed, f0, nf, P, n, h->perm.p, h->inv.p, h->comp);
         } else {
           HIP_TRY(hipMemcpyAsync(h->perm.p, perms + f0 * n, (size_t)(nf * n) * sizeof(int32_t), hipMemcpyHostToDevice,
                                  h->comp));
@@ -739,20 +631,12 @@ extern "C" int midagma_dcor_run(midagma_dcor* h, const int64_t* pairs, int64_t m
       for (int64_t e = e0; e < e1; ++e) {
         const int64_t q = e / P1, p = e % P1, vi = pairs[2 * q], vj = pairs[2 * q + 1];
         const double v = h->hvals.p[e - e0];
-        // a zero-range column: the reference's centred matrix is exactly 0 (mi_tests.py:21-27, 99-100)
         const bool zero = h->hzr[vi] || h->hzr[vj];
         const double vx = h->hcs[vi * 4 + (unbiased ? 2 : 1)], vy = h->hcs[vj * 4 + (unbiased ? 2 : 1)];
         double s = 0.0;
         if (!zero && vx > 0.0 && vy > 0.0)
           s = unbiased ? v / std::sqrt(vx * vy) : std::sqrt(std::max(v, 0.0)) / std::sqrt(std::sqrt(vx * vy));
-        if (p == 0) {
-          obs = v;
-          stat[q] = s;
-          ge[q] = zero ? P : 0;
-        } else {
-          if (!zero && v >= obs) ++ge[q];
-          if (null_out) null_out[q * P + p - 1] = s;
-        }
+        count.add(q, p, v, s, zero);  // (counted by dcov^2, reported as the correlation)
       }
     }
   });
@@ -762,21 +646,7 @@ extern "C" int midagma_dcor_run(midagma_dcor* h, const int64_t* pairs, int64_t m
 
 extern "C" int midagma_dcor_perms(midagma_dcor* h, int64_t q, int64_t P, uint64_t seed, int32_t* perms_out,
                                   int32_t* inverse_out) {
-  if (!h) return abi_fail(no_handle<midagma_dcor>, MIDAGMA_E_ARG, "dcor_perms: null handle");
-  if (h->n == 0) return abi_fail(h, MIDAGMA_E_ARG, "dcor_perms: set the data first");
-  if (q < 0 || q > 0xffffffffll || P < 1 || P > kMaxP || !perms_out)
-    return abi_fail(h, MIDAGMA_E_ARG, "dcor_perms: need 0 <= q < 2^32, 1 <= P <= 65535 and an output");
-  const int64_t n = h->n;
-  return abi_guarded(h, [&] {
-    for (int64_t p = 0; p < P; ++p) {  // (one at a time: the scratch of one evaluation)
-      h->perm.alloc((size_t)n), h->inv.alloc((size_t)n);
-      device_perms(h, seed, q * P + p, 1, P);
-      HIP_TRY(hipMemcpyAsync(perms_out + p * n, h->perm.p, n * sizeof(int32_t), hipMemcpyDeviceToHost, h->comp));
-      if (inverse_out)
-        HIP_TRY(hipMemcpyAsync(inverse_out + p * n, h->inv.p, n * sizeof(int32_t), hipMemcpyDeviceToHost, h->comp));
-      HIP_TRY(hipStreamSynchronize(h->comp));
-    }
-  });
+  return col_perms(h, "dcor_perms", q, P, seed, perms_out, h ? &h->inv : nullptr, inverse_out);
 }
 
 extern "C" int midagma_dcor_block(int64_t n) { return n < 1 ? 0 : block_edge(n); }

@@ -24,7 +24,7 @@
 //                  c_a^2, 0) (the pivot's own: 0).  The working factor is column-major (a step reads
 //                  and writes whole columns); the finished one is centred and stored row-major
 //                  n x r_pad, r_pad the next multiple of 16, zero padded: a gathered row is contiguous
-//   permutations   dcor.hip's: Philox keys and the segmented radix sort (any n), or the host's,
+//   permutations   coltest.h's: Philox keys and the segmented radix sort (any n), or the host's,
 //                  checked on the device (every index in range, every row marked once)
 //   evaluation     grid (row chunk, group of 4 permutations of a pair, 32 x 32 block of M): the A
 //                  operand of v_mfma_f64_16x16x4_f64 comes from Fc's rows, loaded once for the
@@ -70,11 +70,8 @@
 #include <vector>
 
 #include "../../include/midagma_hip.h"
-#include "colsort.h"
-#include "devmem.h"
-#include "launch.h"
+#include "coltest.h"
 #include "mfma64.h"
-#include "philox.h"
 
 namespace midagma {
 namespace {
@@ -86,33 +83,6 @@ constexpr int RFIRST = 64;   // columns of the working factor in the first attem
 constexpr int EG = 4;        // permutations that share one load of the Fc chunk
 constexpr int MG = 64;       // most workgroups a column of a median round
 constexpr int64_t kNoRow = INT64_MAX;
-
-__device__ __forceinline__ double wg_sum(double v, double* w) {
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off);
-  __syncthreads();  // (w may still be read from a previous call)
-  if ((threadIdx.x & 63) == 0) w[threadIdx.x >> 6] = v;
-  __syncthreads();
-  return ((w[0] + w[1]) + w[2]) + w[3];
-}
-
-__device__ __forceinline__ long long wg_sum_ll(long long v, long long* w) {
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) w[threadIdx.x >> 6] = v;
-  __syncthreads();
-  return w[0] + w[1] + w[2] + w[3];
-}
-
-__device__ __forceinline__ double wg_min(double v, double* w) {
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) v = fmin(v, __shfl_xor(v, off));
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) w[threadIdx.x >> 6] = v;
-  __syncthreads();
-  return fmin(fmin(w[0], w[1]), fmin(w[2], w[3]));
-}
 
 __device__ __forceinline__ bool better(double v, long long i, double ov, long long oi) {
   return ov > v || (ov == v && oi < i);
@@ -206,8 +176,8 @@ __global__ __launch_bounds__(HT) void hsic_median_round_kernel(const double* __r
     c += l - (a + 1);
     if (l < n) m = fmin(m, xs[l] - xa);
   }
-  c = wg_sum_ll(c, ws);
-  m = wg_min(m, wm);
+  c = wg_sum_ll<HT / 64>(c, ws);
+  m = wg_min<HT / 64>(m, wm);
   if (threadIdx.x == 0) {
     cnt[(cur * ncols + col) * G + blockIdx.x] = c;
     mn[(cur * ncols + col) * G + blockIdx.x] = m;
@@ -311,7 +281,7 @@ __global__ __launch_bounds__(HT) void hsic_colsum_kernel(const double* __restric
     const int64_t a = (int64_t)blockIdx.x * FCH + threadIdx.x + k * HT;
     if (a < n) s += Wc[t * n + a];
   }
-  s = wg_sum(s, w);
+  s = wg_sum<HT / 64>(s, w);
   if (threadIdx.x == 0) part[t * nch + blockIdx.x] = s;
 }
 
@@ -336,17 +306,7 @@ __global__ __launch_bounds__(HT) void hsic_centre_kernel(const double* __restric
   Fc[e] = t < r ? Wc[(int64_t)t * n + a] - mean[t] : 0.0;
 }
 
-// --- permutations --------------------------------------------------------------------------------
-// the sort records of permutations f0 .. f0 + nseg - 1 (f = q P + p): dcor.hip's key layout
-__global__ __launch_bounds__(HT) void hsic_keys_kernel(uint32_t k0, uint32_t k1, int64_t f0, int64_t n, int64_t P,
-                                                       uint64_t* __restrict__ K0, uint32_t* __restrict__ I0) {
-  const int64_t a = (int64_t)blockIdx.x * HT + threadIdx.x, f = f0 + blockIdx.y;
-  if (a >= n) return;
-  const U4 o = philox4x32_10(U4{(uint32_t)(f / P), (uint32_t)(f % P), (uint32_t)a, 0u}, k0, k1);
-  K0[(int64_t)blockIdx.y * n + a] = ((uint64_t)o.x << 32) | o.y;
-  I0[(int64_t)blockIdx.y * n + a] = (uint32_t)a;
-}
-
+// --- permutations (coltest.h makes the device's) ---------------------------------------------------
 // host permutations: flag[0] for an index outside [0, n), else its row is marked ...
 __global__ __launch_bounds__(HT) void hsic_perm_mark_kernel(const int32_t* __restrict__ perm, int64_t n,
                                                             uint8_t* __restrict__ mark, int* __restrict__ flag) {
@@ -459,7 +419,7 @@ __global__ __launch_bounds__(HT) void hsic_value_kernel(const double* __restrict
       for (int64_t c = 0; c < nchunk; ++c) m += partial[((slot * nchunk + c) * nbmax + bz) * 1024 + e];
       s += m * m;
     }
-  s = wg_sum(s, w);
+  s = wg_sum<HT / 64>(s, w);
   if (threadIdx.x == 0) vals[slot] = s / ((double)n * (double)n);
 }
 
@@ -574,7 +534,7 @@ __global__ __launch_bounds__(HT) void hsic_tile_reduce_kernel(const double* __re
   double m = 0.0;
   for (int64_t c = 0; c < nchunk; ++c) m += partial[((c * ntiles + tile) * TSUB + sub) * 256 + threadIdx.x];
   if (SQ) {
-    const double s = wg_sum(m * m, ws);
+    const double s = wg_sum<HT / 64>(m * m, ws);
     if (threadIdx.x == 0) out[(int64_t)sa * nsB + sb] = s;
   } else {
     out[((int64_t)sa * nsB + sb) * 256 + threadIdx.x] = m;
@@ -629,8 +589,8 @@ __global__ __launch_bounds__(HT) void hsic_u_rows_kernel(const UCol* __restrict_
       sr += rho, sw += w;
     }
   }
-  sr = wg_sum(sr, ws);
-  sw = wg_sum(sw, ws);
+  sr = wg_sum<HT / 64>(sr, ws);
+  sw = wg_sum<HT / 64>(sw, ws);
   if (threadIdx.x == 0) {
     part[((int64_t)col * nch + blockIdx.x) * 2] = sr;
     part[((int64_t)col * nch + blockIdx.x) * 2 + 1] = sw;
@@ -704,9 +664,7 @@ __global__ __launch_bounds__(HT) void hsic_u_combine_kernel(const double* __rest
   bia[e] = sq / (nr * nr);
 }
 
-constexpr int64_t kMaxD = 65535, kMaxP = 65535, kMaxGroups = 16383;  // (EG permutations a group in a sort of <= 65535 segments)
-constexpr int64_t kMaxN = (int64_t(1) << 31) - 1;
-constexpr int64_t kDefaultBudget = int64_t(2) << 30;
+constexpr int64_t kMaxGroups = 16383;  // (EG permutations a group in a sort of <= 65535 segments)
 constexpr int64_t kMaxChunk = int64_t(1) << 20;
 constexpr double kTolMin = 1e-14, kTolMax = 1e-3;
 
@@ -724,13 +682,8 @@ struct Factor {
 
 using namespace midagma;
 
-struct midagma_hsic {
-  int device = 0;
-  int64_t n = 0, d = 0;
-  std::string err;
-  hipStream_t comp = nullptr;
+struct midagma_hsic : ColHandle {
   DevBuf<double> XT, XS, c;  // d x n by row and sorted, 1 / (2 sigma^2) a column
-  std::vector<int32_t> hzr;  // the zero-range marks
   bool have_bw = false;
   double ftol = 0.0;           // the tolerance of the factors held
   std::vector<Factor> fac;     // d
@@ -739,13 +692,9 @@ struct midagma_hsic {
   DevBuf<int32_t> drpad;       // d
   // a run's scratch (kept between runs, grow-only)
   DevBuf<int64_t> dpairs;
-  DevBuf<int32_t> perm;
   DevBuf<uint8_t> mark;
   DevBuf<int> flag;
   DevBuf<double> partial, vals;
-  DevBuf<uint64_t> skeys;
-  DevBuf<uint32_t> sidx, shist;
-  DevBuf<unsigned long long> soa;
   PinBuf<double> hvals;
   Event ev[3];
   double prof[4] = {0, 0, 0, 0};  // ms: medians, factorisation, permutations, evaluation
@@ -754,25 +703,13 @@ struct midagma_hsic {
   DevBuf<int2> utiles;
   PinBuf<double> hcov, hbia;
   double uprof[2] = {0, 0};  // ms: the tiled pass over the factors, the vectors and their Grams
+  void prepare(const double* X, int64_t n, int64_t d, int64_t ld, int64_t budget, hipStream_t st);
 };
-
-// abi.h's hook: an entry's device work runs on the handle's device once a set_data* has opened it
-static void abi_select_device(const midagma_hsic* h) {
-  if (h->comp) HIP_TRY(hipSetDevice(h->device));
-}
 
 namespace {
 
 using clk = std::chrono::steady_clock;
 double ms_since(clk::time_point t0) { return std::chrono::duration<double, std::milli>(clk::now() - t0).count(); }
-
-const char* bad_shape(const void* X, int64_t n, int64_t d, int64_t ld) {
-  if (!X) return "null pointer";
-  if (n < 2 || n > kMaxN) return "need 2 <= n < 2^31 rows";
-  if (d < 1 || d > kMaxD) return "need 1 <= d <= 65535 columns";
-  if (ld < d) return "the leading dimension is below d";
-  return nullptr;
-}
 
 void drop_factors(midagma_hsic* h) {
   h->fac.clear();
@@ -781,50 +718,29 @@ void drop_factors(midagma_hsic* h) {
   h->ftol = 0.0;
 }
 
-void open_handle(midagma_hsic* h) {
-  open_device(h->device, "");
-  if (!h->comp) {
-    HIP_TRY(hipStreamCreateWithFlags(&h->comp, hipStreamNonBlocking));
-    for (Event& e : h->ev) e.create();
-  }
-}
+}  // namespace
 
 // XT, the sorted columns and the zero-range marks from X_dev (n x d, ld) on stream st; st is synchronised
-void prepare(midagma_hsic* h, const double* X, int64_t n, int64_t d, int64_t ld, int64_t budget, hipStream_t st) {
+void midagma_hsic::prepare(const double* X, int64_t n, int64_t d, int64_t ld, int64_t budget, hipStream_t st) {
+  for (Event& e : ev) e.create();  // (the first call makes them: the device is open by now)
   const size_t nd = (size_t)n * d;
   DevBuf<int32_t> order, zr;
   order.alloc(nd), zr.alloc(d);
   colargsort_run(X, n, d, ld, order.p, budget, st);  // (throws on inf / nan)
-  h->XT.alloc(nd), h->XS.alloc(nd);
+  XT.alloc(nd), XS.alloc(nd);
   hipLaunchKernelGGL(hsic_cols_kernel, dim3((unsigned)((n + HT - 1) / HT), (unsigned)d), dim3(HT), 0, st, X, ld, order.p,
-                     n, h->XT.p, h->XS.p);
-  hipLaunchKernelGGL(hsic_zero_range_kernel, dim3((unsigned)((d + HT - 1) / HT)), dim3(HT), 0, st, h->XS.p, n, d, zr.p);
+                     n, XT.p, XS.p);
+  hipLaunchKernelGGL(hsic_zero_range_kernel, dim3((unsigned)((d + HT - 1) / HT)), dim3(HT), 0, st, XS.p, n, d, zr.p);
   HIP_TRY(hipGetLastError());
-  h->hzr.resize(d);
-  HIP_TRY(hipMemcpyAsync(h->hzr.data(), zr.p, d * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+  hzr.resize(d);
+  HIP_TRY(hipMemcpyAsync(hzr.data(), zr.p, d * sizeof(int32_t), hipMemcpyDeviceToHost, st));
   HIP_TRY(hipStreamSynchronize(st));  // (the scratch is freed on return)
-  h->n = n, h->d = d;
-  h->have_bw = false;
-  drop_factors(h);
+  this->n = n, this->d = d;
+  have_bw = false;
+  drop_factors(this);
 }
 
-// c = 1 / (2 sigma^2) per column on the device; the factors are dropped
-int install_bandwidths(midagma_hsic* h, const double* sigma2, const char* who) {
-  const int64_t d = h->d;
-  std::vector<double> c(d);
-  for (int64_t v = 0; v < d; ++v) {
-    if (!(sigma2[v] > 0.0) || !std::isfinite(sigma2[v]))
-      return abi_fail(h, MIDAGMA_E_ARG, std::string(who) + ": squared bandwidths must be finite and > 0");
-    c[v] = 1.0 / (2.0 * sigma2[v]);
-  }
-  return abi_guarded(h, [&] {
-    HIP_TRY(hipStreamSynchronize(h->comp));
-    h->c.alloc(d);
-    HIP_TRY(hipMemcpy(h->c.p, c.data(), d * sizeof(double), hipMemcpyHostToDevice));
-    h->have_bw = true;
-    drop_factors(h);
-  });
-}
+namespace {
 
 int64_t budget_of(int64_t budget) { return budget > 0 ? budget : kDefaultBudget; }
 
@@ -925,22 +841,6 @@ void upload_factor_table(midagma_hsic* h) {
   HIP_TRY(hipStreamSynchronize(h->comp));  // (the host vectors end here)
 }
 
-// permutations f0 .. f0 + nf - 1 of (seed) into h->perm, on the handle's stream
-void device_perms(midagma_hsic* h, uint64_t seed, int64_t f0, int64_t nf, int64_t P) {
-  const int64_t n = h->n, hs = segsort_hist_per_segment(n);
-  h->skeys.alloc((size_t)(2 * nf * n)), h->sidx.alloc((size_t)(2 * nf * n));
-  h->shist.alloc((size_t)(nf * hs)), h->soa.alloc((size_t)(2 * nf));
-  const SegSort s{h->skeys.p, h->skeys.p + nf * n, h->sidx.p, h->sidx.p + nf * n, h->soa.p, h->soa.p + nf, h->shist.p};
-  // (every pass live: random keys share no digit, and a pass that moves nothing is still a stable pass)
-  HIP_TRY(hipMemsetAsync(s.key_or, 0xff, (size_t)nf * 8, h->comp));
-  HIP_TRY(hipMemsetAsync(s.key_and, 0, (size_t)nf * 8, h->comp));
-  hipLaunchKernelGGL(hsic_keys_kernel, dim3((unsigned)((n + HT - 1) / HT), (unsigned)nf), dim3(HT), 0, h->comp,
-                     (uint32_t)seed, (uint32_t)(seed >> 32), f0, n, P, s.K0, s.I0);
-  HIP_TRY(hipGetLastError());
-  launch_segsort(s, n, nf, h->comp);
-  launch_segsort_payload(s, n, nf, h->perm.p, nullptr, h->comp);
-}
-
 // the host's permutations f0 .. f0 + nf - 1 into h->perm, checked on the device; synchronises
 void host_perms(midagma_hsic* h, const int32_t* perms, int64_t f0, int64_t nf) {
   const int64_t n = h->n;
@@ -966,77 +866,33 @@ int64_t chunk_rule(int64_t) { return 2048; }
 
 extern "C" const char* midagma_hsic_last_error(const midagma_hsic* h) { return abi_last_error(h); }
 
-extern "C" void midagma_hsic_destroy(midagma_hsic* h) {
-  if (!h) return;
-  if (h->comp) {  // (a handle that never opened its device owns nothing there, and its index may name none)
-    (void)hipSetDevice(h->device);
-    (void)hipStreamSynchronize(h->comp);
-    (void)hipStreamDestroy(h->comp);
-  }
-  delete h;
-}
+extern "C" void midagma_hsic_destroy(midagma_hsic* h) { col_destroy(h); }
 
-// (no device call: the device is opened by the first set_data*, so the argument checks of every
-// entry can be exercised on a machine without one)
-extern "C" int midagma_hsic_create(midagma_hsic** out, int device) {
-  if (!out || device < 0) return abi_fail(no_handle<midagma_hsic>, MIDAGMA_E_ARG, "hsic_create: bad arguments");
-  *out = new midagma_hsic;
-  (*out)->device = device;
-  return MIDAGMA_OK;
-}
+extern "C" int midagma_hsic_create(midagma_hsic** out, int device) { return col_create(out, device, "hsic_create"); }
 
 extern "C" int midagma_hsic_set_data(midagma_hsic* h, const double* X, int64_t n, int64_t d, int64_t budget_bytes) {
-  if (!h) return abi_fail(no_handle<midagma_hsic>, MIDAGMA_E_ARG, "hsic_set_data: null handle");
-  if (const char* why = bad_shape(X, n, d, d)) return abi_fail(h, MIDAGMA_E_ARG, std::string("hsic_set_data: ") + why);
-  h->n = h->d = 0;
-  return abi_guarded(h, [&] {
-    open_handle(h);
-    HIP_TRY(hipStreamSynchronize(h->comp));
-    DevBuf<double> Xd;
-    Xd.alloc((size_t)n * d);
-    HIP_TRY(hipMemcpyAsync(Xd.p, X, (size_t)n * d * sizeof(double), hipMemcpyHostToDevice, h->comp));
-    prepare(h, Xd.p, n, d, d, budget_bytes, h->comp);
-  });
+  return col_set_data(h, "hsic_set_data", X, n, d, budget_bytes);
 }
 
 extern "C" int midagma_hsic_set_data_dev(midagma_hsic* h, const double* X_dev, int64_t n, int64_t d, int64_t ld,
                                          int64_t budget_bytes, void* hip_stream) {
-  if (!h) return abi_fail(no_handle<midagma_hsic>, MIDAGMA_E_ARG, "hsic_set_data_dev: null handle");
-  if (const char* why = bad_shape(X_dev, n, d, ld))
-    return abi_fail(h, MIDAGMA_E_ARG, std::string("hsic_set_data_dev: ") + why);
-  h->n = h->d = 0;  // the handle holds no data until the new one is checked
-  return abi_guarded(h, [&] {
-    open_handle(h);
-    require_device_memory(X_dev, h->device, "hsic_set_data_dev");
-    HIP_TRY(hipStreamSynchronize(h->comp));  // nothing of an earlier run still reads the columns' arrays
-    // on the caller's stream, behind X's producer; prepare's synchronise (the marks are read on the
-    // host) also orders the arrays before everything the handle's own stream runs later
-    prepare(h, X_dev, n, d, ld, budget_bytes, static_cast<hipStream_t>(hip_stream));
-  });
+  return col_set_data_dev(h, "hsic_set_data_dev", X_dev, n, d, ld, budget_bytes, hip_stream);
 }
 
 extern "C" int midagma_hsic_set_bandwidths(midagma_hsic* h, const double* sigma2, int64_t d) {
   if (!h) return abi_fail(no_handle<midagma_hsic>, MIDAGMA_E_ARG, "hsic_set_bandwidths: null handle");
   if (h->n == 0) return abi_fail(h, MIDAGMA_E_ARG, "hsic_set_bandwidths: set the data first");
   if (!sigma2 || d != h->d) return abi_fail(h, MIDAGMA_E_ARG, "hsic_set_bandwidths: need d squared bandwidths");
-  return install_bandwidths(h, sigma2, "hsic_set_bandwidths");
+  return install_bandwidths(h, sigma2, "hsic_set_bandwidths", [h] { drop_factors(h); });
 }
 
 extern "C" int midagma_hsic_median_bandwidths(midagma_hsic* h, const int64_t* cols, int64_t ncols, double* sigma2_out) {
   if (!h) return abi_fail(no_handle<midagma_hsic>, MIDAGMA_E_ARG, "hsic_median_bandwidths: null handle");
   if (h->n == 0) return abi_fail(h, MIDAGMA_E_ARG, "hsic_median_bandwidths: set the data first");
-  if (cols && ncols < 0) return abi_fail(h, MIDAGMA_E_ARG, "hsic_median_bandwidths: ncols < 0");
   const int64_t n = h->n, d = h->d;
-  // the listed columns, each once, ascending (a column's value does not depend on the list)
-  std::vector<int64_t> list;
-  std::vector<uint8_t> mark(d, cols ? 0 : 1);
-  for (int64_t k = 0; cols && k < ncols; ++k) {
-    if (cols[k] < 0 || cols[k] >= d)
-      return abi_fail(h, MIDAGMA_E_ARG, "hsic_median_bandwidths: column index outside [0, d)");
-    mark[cols[k]] = 1;
-  }
-  for (int64_t v = 0; v < d; ++v)
-    if (mark[v]) list.push_back(v);
+  std::vector<int64_t> list;  // (a column's value does not depend on the list)
+  if (const char* why = listed_columns(cols, ncols, d, list))
+    return abi_fail(h, MIDAGMA_E_ARG, says("hsic_median_bandwidths", why));
   const int64_t m = (int64_t)list.size();
   std::vector<double> med(m), s2(d, 1.0);
   h->prof[0] = 0.0;
@@ -1064,7 +920,7 @@ extern "C" int midagma_hsic_median_bandwidths(midagma_hsic* h, const int64_t* co
     h->prof[0] = ms_since(t0);
     for (int64_t k = 0; k < m; ++k) s2[list[k]] = med[k];
   }
-  const int rc = install_bandwidths(h, s2.data(), "hsic_median_bandwidths");
+  const int rc = install_bandwidths(h, s2.data(), "hsic_median_bandwidths", [h] { drop_factors(h); });
   if (rc != MIDAGMA_OK) return rc;
   if (sigma2_out) std::copy(s2.begin(), s2.end(), sigma2_out);
   return MIDAGMA_OK;
@@ -1085,12 +941,9 @@ extern "C" int midagma_hsic_factor(midagma_hsic* h, const int64_t* cols, int64_t
   if (ncols < 0 || (ncols > 0 && !cols)) return abi_fail(h, MIDAGMA_E_ARG, "hsic_factor: need ncols >= 0 columns");
   if (h->n == 0) return abi_fail(h, MIDAGMA_E_ARG, "hsic_factor: set the data first");
   if (!h->have_bw) return abi_fail(h, MIDAGMA_E_ARG, "hsic_factor: set the bandwidths first");
-  std::vector<uint8_t> mark(h->d, 0);
-  std::vector<int64_t> list;
-  for (int64_t k = 0; k < ncols; ++k) {
-    if (cols[k] < 0 || cols[k] >= h->d) return abi_fail(h, MIDAGMA_E_ARG, "hsic_factor: column index outside [0, d)");
-    if (!mark[cols[k]]) mark[cols[k]] = 1, list.push_back(cols[k]);
-  }
+  std::vector<int64_t> list;  // (a column's factor does not depend on the list or on its order)
+  if (const char* why = ncols ? listed_columns(cols, ncols, h->d, list) : nullptr)
+    return abi_fail(h, MIDAGMA_E_ARG, says("hsic_factor", why));
   h->prof[1] = 0.0;
   const int rc = abi_guarded(h, [&] { ensure_factors(h, list, tol, kDefaultBudget / 2); });
   if (rc != MIDAGMA_OK) {
@@ -1135,7 +988,7 @@ extern "C" int midagma_hsic_run(midagma_hsic* h, const int64_t* pairs, int64_t m
   const int64_t budget = budget_of(budget_bytes), fbudget = budget / 2, ebudget = budget - fbudget;
   const int64_t ch = chunk ? chunk : chunk_rule(n), nchunk = (n + ch - 1) / ch;
   const bool dev_perms = perms == nullptr;
-  const int64_t sort_bytes = (P > 0 && dev_perms) ? 2 * n * 8 + 2 * n * 4 + segsort_hist_per_segment(n) * 4 + 16 : 0;
+  const int64_t sort_bytes = (P > 0 && dev_perms) ? perm_sort_bytes(n) : 0;
 
   const int rc = abi_guarded(h, [&] {
     if (h->ftol != tol) {
@@ -1145,6 +998,7 @@ extern "C" int midagma_hsic_run(midagma_hsic* h, const int64_t* pairs, int64_t m
     h->dpairs.alloc((size_t)(2 * m));
     HIP_TRY(hipMemcpyAsync(h->dpairs.p, pairs, 2 * m * sizeof(int64_t), hipMemcpyHostToDevice, h->comp));
     std::vector<uint8_t> in_group(d);
+    NullCount count{stat, ge, null_out, P};
     for (int64_t qs = 0; qs < m;) {
       // the next column group: consecutive pairs while the factors of their columns (at the padded
       // rank a column had before, 64 for one not factored yet) stay within half the budget
@@ -1179,7 +1033,6 @@ extern "C" int midagma_hsic_run(midagma_hsic* h, const int64_t* pairs, int64_t m
       // bytes of scratch one group of EG evaluations takes
       const int64_t per = EG * (nchunk * nbmax * 1024 * 8 + 16 + (P > 0 ? n * 4 + (dev_perms ? 0 : n) : 0) + sort_bytes);
       const int64_t ngmax = std::max<int64_t>(1, std::min<int64_t>(kMaxGroups, ebudget / per));
-      double obs = 0.0;  // the observed value of the pair whose permutations are being counted
       for (int64_t g0 = qs * NG; g0 < qe * NG; g0 += ngmax) {
         const int64_t ng = std::min(ngmax, qe * NG - g0), g1 = g0 + ng;
         // the chunk's permutations: f = q P + p - 1 for p >= 1, ascending with the evaluations
@@ -1192,7 +1045,7 @@ extern "C" int midagma_hsic_run(midagma_hsic* h, const int64_t* pairs, int64_t m
         if (nf > 0) {
           h->perm.alloc((size_t)(nf * n));
           if (dev_perms)
-            device_perms(h, seed, f0, nf, P);
+            h->sort.run(seed, f0, nf, P, n, h->perm.p, nullptr, h->comp);
           else
             host_perms(h, perms, f0, nf);
         }
@@ -1215,17 +1068,9 @@ extern "C" int midagma_hsic_run(midagma_hsic* h, const int64_t* pairs, int64_t m
           for (int64_t s = 0; s < EG; ++s) {
             const int64_t q = g / NG, p = (g % NG) * EG + s;
             if (p > P) continue;
-            // a zero-range column: the reference's centred matrix is exactly 0 (mi_tests.py:21-27)
             const bool zero = h->hzr[pairs[2 * q]] || h->hzr[pairs[2 * q + 1]];
             const double v = zero ? 0.0 : h->hvals.p[(g - g0) * EG + s];
-            if (p == 0) {
-              obs = v;
-              stat[q] = v;
-              ge[q] = zero ? P : 0;
-            } else {
-              if (!zero && v >= obs) ++ge[q];
-              if (null_out) null_out[q * P + p - 1] = v;
-            }
+            count.add(q, p, v, v, zero);
           }
       }
       qs = qe;
@@ -1378,14 +1223,9 @@ extern "C" int midagma_hsic_all_pairs(midagma_hsic* h, const int64_t* cols, int6
   // the listed columns, each once, ascending (a pair's smaller column is always the A side, so its
   // value does not depend on the list); place[k]: where entry k's column is
   std::vector<int64_t> uniq;
+  if (const char* why = listed_columns(cols, ncols, d, uniq)) return abi_fail(h, MIDAGMA_E_ARG, says("hsic_all_pairs", why));
   std::vector<int64_t> place((size_t)nout), seen((size_t)d, -1);
-  for (int64_t k = 0; k < nout; ++k) {
-    const int64_t v = cols ? cols[k] : k;
-    if (v < 0 || v >= d) return abi_fail(h, MIDAGMA_E_ARG, "hsic_all_pairs: column index outside [0, d)");
-    seen[v] = 0;
-  }
-  for (int64_t v = 0; v < d; ++v)
-    if (seen[v] == 0) seen[v] = (int64_t)uniq.size(), uniq.push_back(v);
+  for (size_t u = 0; u < uniq.size(); ++u) seen[uniq[u]] = (int64_t)u;
   for (int64_t k = 0; k < nout; ++k) place[k] = seen[cols ? cols[k] : k];
   h->prof[1] = h->uprof[0] = h->uprof[1] = 0.0;
   if (nout == 0) return MIDAGMA_OK;
@@ -1486,19 +1326,7 @@ extern "C" int midagma_hsic_all_pairs_profile(const midagma_hsic* h, double* ms_
 }
 
 extern "C" int midagma_hsic_perms(midagma_hsic* h, int64_t q, int64_t P, uint64_t seed, int32_t* perms_out) {
-  if (!h) return abi_fail(no_handle<midagma_hsic>, MIDAGMA_E_ARG, "hsic_perms: null handle");
-  if (h->n == 0) return abi_fail(h, MIDAGMA_E_ARG, "hsic_perms: set the data first");
-  if (q < 0 || q > 0xffffffffll || P < 1 || P > kMaxP || !perms_out)
-    return abi_fail(h, MIDAGMA_E_ARG, "hsic_perms: need 0 <= q < 2^32, 1 <= P <= 65535 and an output");
-  const int64_t n = h->n;
-  return abi_guarded(h, [&] {
-    for (int64_t p = 0; p < P; ++p) {  // (one at a time: the scratch of one evaluation)
-      h->perm.alloc((size_t)n);
-      device_perms(h, seed, q * P + p, 1, P);
-      HIP_TRY(hipMemcpyAsync(perms_out + p * n, h->perm.p, n * sizeof(int32_t), hipMemcpyDeviceToHost, h->comp));
-      HIP_TRY(hipStreamSynchronize(h->comp));
-    }
-  });
+  return col_perms(h, "hsic_perms", q, P, seed, perms_out, nullptr, nullptr);
 }
 
 extern "C" int midagma_hsic_profile(const midagma_hsic* h, double* ms_out) {

@@ -48,9 +48,7 @@
 #include <vector>
 
 #include "../../include/midagma_hip.h"
-#include "devmem.h"
-#include "launch.h"
-#include "philox.h"
+#include "coltest.h"
 
 namespace midagma {
 namespace {
@@ -58,17 +56,6 @@ namespace {
 constexpr int IT = 64;  // tile edge
 constexpr int IG = 8;   // permutations per LDS round
 constexpr int KIND_HSIC = 0, KIND_DCOR = 1;
-
-// the sum of v over the workgroup's 256 threads in a fixed order (butterfly within a wave, then
-// wave 0 + 1 + 2 + 3); the result is valid in every thread; w: 4 doubles of LDS
-__device__ __forceinline__ double block_sum(double v, double* w) {
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off);
-  __syncthreads();  // (w may still be read from a previous call)
-  if ((threadIdx.x & 63) == 0) w[threadIdx.x >> 6] = v;
-  __syncthreads();
-  return ((w[0] + w[1]) + w[2]) + w[3];
-}
 
 template <int KIND>
 __device__ __forceinline__ double kern(double dlt, double c) {
@@ -100,7 +87,7 @@ __global__ __launch_bounds__(256) void indep_row_kernel(const double* __restrict
       s += ax * ax;
     }
   }
-  s = block_sum(s, w);
+  s = wg_sum<4>(s, w);
   if (threadIdx.x == 0) out[static_cast<int64_t>(v) * n + a] = PHASE == 0 ? s / n : s;
 }
 
@@ -111,7 +98,7 @@ __global__ __launch_bounds__(256) void indep_col_kernel(const double* __restrict
   const int v = blockIdx.x;
   double s = 0.0;
   for (int a = threadIdx.x; a < n; a += 256) s += in[static_cast<int64_t>(v) * n + a];
-  s = block_sum(s, w);
+  s = wg_sum<4>(s, w);
   if (threadIdx.x == 0) out[v] = s / div;
 }
 
@@ -328,30 +315,6 @@ __global__ __launch_bounds__(256) void indep_flag_kernel(const uint8_t* __restri
   flag[i] = g;
 }
 
-// the sum / the minimum of one value per thread over the workgroup (any multiple of 64 threads up
-// to 1024; integer sums and minima do not depend on the order); valid in every thread
-__device__ __forceinline__ long long block_sum_ll(long long v, long long* w) {
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) w[threadIdx.x >> 6] = v;
-  __syncthreads();
-  long long s = 0;
-  for (int k = 0, nw = blockDim.x >> 6; k < nw; ++k) s += w[k];
-  return s;
-}
-
-__device__ __forceinline__ double block_min(double v, double* w) {
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) v = fmin(v, __shfl_xor(v, off));
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) w[threadIdx.x >> 6] = v;
-  __syncthreads();
-  double s = w[0];
-  for (int k = 1, nw = blockDim.x >> 6; k < nw; ++k) s = fmin(s, w[k]);
-  return s;
-}
-
 // rows a < b of the sorted column xs[0 .. n) with fl(xs[b] - xs[a]) <= t, for this thread's rows
 // a = tid, tid + threads, ...: per row the length of the prefix of b = a + 1 .. n - 1 (the
 // differences are non-decreasing in b), by binary search.  MINNEXT: also the smallest difference
@@ -415,7 +378,7 @@ __global__ __launch_bounds__(1024) void indep_median_kernel(const double* __rest
   unsigned long long lo = 0, hi = 0x7ff0000000000000ull;
   while (lo < hi) {
     const unsigned long long mid = lo + ((hi - lo) >> 1);
-    const long long c = block_sum_ll(median_count<false>(xs, n, __longlong_as_double(mid), nullptr), wsum);
+    const long long c = wg_sum_ll(median_count<false>(xs, n, __longlong_as_double(mid), nullptr), wsum);
     if (c >= k + 1)
       hi = mid;
     else
@@ -425,8 +388,8 @@ __global__ __launch_bounds__(1024) void indep_median_kernel(const double* __rest
   double m = vk * vk;
   if (!(M & 1)) {
     double next;
-    const long long c = block_sum_ll(median_count<true>(xs, n, vk, &next), wsum);
-    const double above = block_min(next, wmin);
+    const long long c = wg_sum_ll(median_count<true>(xs, n, vk, &next), wsum);
+    const double above = wg_min(next, wmin);
     const double vn = c > M / 2 ? vk : above;
     m = (m + vn * vn) / 2.0;
   }
@@ -440,8 +403,8 @@ using namespace midagma;
 
 namespace {
 
-constexpr int64_t kMaxN = 16384, kMaxD = 65535, kMaxP = 65535, kMaxBatchPairs = 32768;
-constexpr int64_t kDefaultBudget = int64_t(128) << 20;
+constexpr int64_t kMaxRows = 16384, kMaxBatchPairs = 32768;  // (the n^2 kernel; kMaxD and kMaxP are coltest.h's)
+constexpr int64_t kBatchBudget = int64_t(128) << 20;
 
 struct Slot {
   PinBuf<int32_t> hperm;
@@ -491,7 +454,7 @@ int64_t pair_bytes(int64_t n, int64_t P) {
 }
 
 int64_t batch_pairs(int64_t n, int64_t P, int64_t budget) {
-  if (budget <= 0) budget = kDefaultBudget;
+  if (budget <= 0) budget = kBatchBudget;
   return std::min<int64_t>(kMaxBatchPairs, std::max<int64_t>(1, budget / (2 * pair_bytes(n, P))));
 }
 
@@ -565,7 +528,7 @@ extern "C" void midagma_indep_destroy(midagma_indep* h) {
 
 extern "C" int midagma_indep_set_data(midagma_indep* h, const double* X, int64_t n, int64_t d) {
   if (!h) return abi_fail(no_handle<midagma_indep>, MIDAGMA_E_ARG, "indep_set_data: null handle");
-  if (!X || n < 2 || n > kMaxN || d < 1 || d > kMaxD)
+  if (!X || n < 2 || n > kMaxRows || d < 1 || d > kMaxD)
     return abi_fail(h, MIDAGMA_E_ARG, "indep_set_data: need X, 2 <= n <= 16384 and 1 <= d <= 65535");
   std::vector<double> xt(static_cast<size_t>(n) * d);
   std::vector<uint8_t> constant(d, 1);
@@ -590,7 +553,7 @@ extern "C" int midagma_indep_set_data(midagma_indep* h, const double* X, int64_t
 extern "C" int midagma_indep_set_data_dev(midagma_indep* h, const double* X_dev, int64_t n, int64_t d, int64_t ld,
                                           void* hip_stream) {
   if (!h) return abi_fail(no_handle<midagma_indep>, MIDAGMA_E_ARG, "indep_set_data_dev: null handle");
-  if (!X_dev || n < 2 || n > kMaxN || d < 1 || d > kMaxD || ld < d)
+  if (!X_dev || n < 2 || n > kMaxRows || d < 1 || d > kMaxD || ld < d)
     return abi_fail(h, MIDAGMA_E_ARG, "indep_set_data_dev: need X, 2 <= n <= 16384, 1 <= d <= 65535 and ld >= d");
   hipStream_t s = static_cast<hipStream_t>(hip_stream);
   std::vector<uint8_t> flags(2 * d);
@@ -623,54 +586,23 @@ extern "C" int midagma_indep_set_data_dev(midagma_indep* h, const double* X_dev,
   return MIDAGMA_OK;
 }
 
-namespace {
-
-// c = 1 / (2 sigma^2) per variable on the device; the HSIC pre-pass is redone
-int install_bandwidths(midagma_indep* h, const double* sigma2, const char* who) {
-  const int64_t d = h->d;
-  std::vector<double> c(d);
-  for (int64_t v = 0; v < d; ++v) {
-    if (!(sigma2[v] > 0.0) || !std::isfinite(sigma2[v]))
-      return abi_fail(h, MIDAGMA_E_ARG, std::string(who) + ": squared bandwidths must be finite and > 0");
-    c[v] = 1.0 / (2.0 * sigma2[v]);
-  }
-  return abi_guarded(h, [&] {
-    HIP_TRY(hipStreamSynchronize(h->comp));
-    h->c.alloc(d);
-    HIP_TRY(hipMemcpy(h->c.p, c.data(), d * sizeof(double), hipMemcpyHostToDevice));
-    h->have_bw = true;
-    h->have_stats[KIND_HSIC] = false;
-  });
-}
-
-}  // namespace
-
 extern "C" int midagma_indep_set_bandwidths(midagma_indep* h, const double* sigma2, int64_t d) {
   if (!h) return abi_fail(no_handle<midagma_indep>, MIDAGMA_E_ARG, "indep_set_bandwidths: null handle");
   if (h->n == 0) return abi_fail(h, MIDAGMA_E_ARG, "indep_set_bandwidths: set the data first");
   if (!sigma2 || d != h->d) return abi_fail(h, MIDAGMA_E_ARG, "indep_set_bandwidths: need d squared bandwidths");
-  return install_bandwidths(h, sigma2, "indep_set_bandwidths");
+  // (the HSIC pre-pass is redone)
+  return install_bandwidths(h, sigma2, "indep_set_bandwidths", [h] { h->have_stats[KIND_HSIC] = false; });
 }
 
 extern "C" int midagma_indep_median_bandwidths(midagma_indep* h, const int64_t* cols, int64_t ncols,
                                                double* sigma2_out) {
   if (!h) return abi_fail(no_handle<midagma_indep>, MIDAGMA_E_ARG, "indep_median_bandwidths: null handle");
   if (h->n == 0) return abi_fail(h, MIDAGMA_E_ARG, "indep_median_bandwidths: set the data first");
-  if (cols && ncols < 0) return abi_fail(h, MIDAGMA_E_ARG, "indep_median_bandwidths: ncols < 0");
   const int64_t n = h->n, d = h->d;
-  // the listed columns, each once, ascending (a column's value does not depend on the list)
-  std::vector<int64_t> list;
-  if (cols) {
-    std::vector<uint8_t> mark(d, 0);
-    for (int64_t k = 0; k < ncols; ++k) {
-      if (cols[k] < 0 || cols[k] >= d)
-        return abi_fail(h, MIDAGMA_E_ARG, "indep_median_bandwidths: column index outside [0, d)");
-      mark[cols[k]] = 1;
-    }
-    for (int64_t v = 0; v < d; ++v)
-      if (mark[v]) list.push_back(v);
-  }
-  const int64_t m = cols ? static_cast<int64_t>(list.size()) : d;
+  std::vector<int64_t> list;  // (a column's value does not depend on the list)
+  if (const char* why = listed_columns(cols, ncols, d, list))
+    return abi_fail(h, MIDAGMA_E_ARG, says("indep_median_bandwidths", why));
+  const int64_t m = static_cast<int64_t>(list.size());
   std::vector<double> med(d), s2(d, 1.0);
   h->bw_ms = 0.0;
   if (m > 0) {
@@ -700,12 +632,10 @@ extern "C" int midagma_indep_median_bandwidths(midagma_indep* h, const int64_t* 
       h->bw_ms = ms;
     });
     if (rc != MIDAGMA_OK) return rc;
-    if (cols)
-      for (int64_t v : list) s2[v] = med[v];
-    else
-      s2 = med;
+    for (int64_t v : list) s2[v] = med[v];
   }
-  const int rc = install_bandwidths(h, s2.data(), "indep_median_bandwidths");
+  const int rc =
+      install_bandwidths(h, s2.data(), "indep_median_bandwidths", [h] { h->have_stats[KIND_HSIC] = false; });
   if (rc != MIDAGMA_OK) return rc;
   if (sigma2_out) std::copy(s2.begin(), s2.end(), sigma2_out);
   return MIDAGMA_OK;

@@ -417,23 +417,52 @@ def _I_from_pvalues(p: np.ndarray, alpha: float, bonferroni: bool, undirected: b
     return np.stack([i[keep], j[keep]], axis=1).astype(int)
 
 
-def _dcor_null(eng: HipDcor, pairs: np.ndarray, P: int, seed: int, perms, unbiased: bool, budget_bytes: int,
-               return_null: bool, block: int):
+def _engine_null(eng, pairs: np.ndarray, P: int, seed: int, perms, return_null: bool, **kw):
+    """(stat, ge, null or None) of `eng.run` (HipDcor, HipHsic; kw: the engine's own arguments) with
+    the engine's device permutations, numpy's drawn as `permutation_null` draws them (a host chunk
+    of pairs at a time), or the given ones."""
     n, m = eng.n, len(pairs)
-    kw = dict(unbiased=unbiased, block=block, budget_bytes=budget_bytes, return_null=True)
+    kw["return_null"] = True
     if isinstance(perms, str) and perms == "device":
         stat, ge, null = eng.run(pairs, P, None, seed, **kw)
     elif isinstance(perms, str):
         rng = np.random.default_rng(seed)
         stat, ge, null = np.zeros(m), np.zeros(m, dtype=np.int64), np.zeros((m, P))
-        chunk = max(1, _HOST_CHUNK_BYTES // max(1, 4 * P * n))
-        for q0 in range(0, m, chunk):
-            q1 = min(m, q0 + chunk)
+        step = max(1, _HOST_CHUNK_BYTES // max(1, 4 * P * n))
+        for q0 in range(0, m, step):
+            q1 = min(m, q0 + step)
             pm = _numpy_perms(rng, q1 - q0, P, n)
             stat[q0:q1], ge[q0:q1], null[q0:q1] = eng.run(pairs[q0:q1], P, pm, 0, **kw)
     else:
         stat, ge, null = eng.run(pairs, P, perms, 0, **kw)
     return stat, ge, (null if return_null else None)
+
+
+def _check_perms(perms, arrays: bool = True):
+    """A string `perms` names a generator; `arrays`: the entry also takes explicit permutations."""
+    if isinstance(perms, str) and perms not in ("numpy", "device"):
+        raise ValueError("perms must be 'numpy', 'device' or an int32 array (m, num_perm, n)" if arrays
+                         else "perms must be 'numpy' or 'device'")
+
+
+def _perm_array(perms, m: int, P: int, n: int):
+    """`perms` if it names a generator, else the explicit permutations as a checked int32 array."""
+    if isinstance(perms, str):
+        return perms
+    perms = np.ascontiguousarray(perms, dtype=np.int32)
+    if perms.shape != (m, P, n):
+        raise ValueError(f"perms must be {(m, P, n)}, got {perms.shape}")
+    return perms
+
+
+def _mirrored(d: int, iu, s, pv, diagonal: float):
+    """(stat, p), d x d: s and pv of the pairs iu (i < j) at (i, j) and (j, i); the diagonal is
+    (`diagonal`, 0) by rule."""
+    stat, p = np.full((d, d), float(diagonal)), np.zeros((d, d))
+    if len(iu[0]):
+        stat[iu], p[iu] = s, pv
+        stat.T[iu], p.T[iu] = s, pv
+    return stat, p
 
 
 def dcor_null(X, pairs, *, num_perm: int = 200, seed: int = 0, perms="numpy", unbiased: bool = False,
@@ -448,8 +477,7 @@ def dcor_null(X, pairs, *, num_perm: int = 200, seed: int = 0, perms="numpy", un
     unbiased: the bias-corrected R_U = dcov^2_U / sqrt(dvar_U,x dvar_U,y) (U-centring; needs n >= 4),
     counted by dcov^2_U.  budget_bytes: the device scratch per chunk of evaluations (0: 2 GiB);
     block: the block edge (0: the rule; tests); results do not depend on the budget."""
-    if isinstance(perms, str) and perms not in ("numpy", "device"):
-        raise ValueError("perms must be 'numpy', 'device' or an int32 array (m, num_perm, n)")
+    _check_perms(perms)
     X = _as_data(X, max_n=None)
     n, d = int(X.shape[0]), int(X.shape[1])
     pairs = _as_pairs(pairs, d)
@@ -460,13 +488,11 @@ def dcor_null(X, pairs, *, num_perm: int = 200, seed: int = 0, perms="numpy", un
         raise ValueError("the bias-corrected statistic needs n >= 4")
     if not (block == 0 or 4 <= int(block) <= 1024):
         raise ValueError("block must be 0 or in [4, 1024]")
-    if not isinstance(perms, str):
-        perms = np.ascontiguousarray(perms, dtype=np.int32)
-        if perms.shape != (len(pairs), P, n):
-            raise ValueError(f"perms must be {(len(pairs), P, n)}, got {perms.shape}")
+    perms = _perm_array(perms, len(pairs), P, n)
     eng = HipDcor(X, device, budget_bytes)
     try:
-        return _dcor_null(eng, pairs, P, seed, perms, unbiased, budget_bytes, return_null, int(block))
+        return _engine_null(eng, pairs, P, seed, perms, return_null, unbiased=unbiased, block=int(block),
+                            budget_bytes=budget_bytes)
     finally:
         eng.close()
 
@@ -483,8 +509,7 @@ def dcor_tests(X, *, pvalue: str = "permutation", num_perm: int = 200, seed: int
     reference, which has only the permutation test.  n < 4 raises ValueError."""
     if pvalue not in ("permutation", "chi2"):
         raise ValueError("pvalue must be 'permutation' or 'chi2'")
-    if isinstance(perms, str) and perms not in ("numpy", "device"):
-        raise ValueError("perms must be 'numpy' or 'device'")
+    _check_perms(perms, arrays=False)
     X = _as_data(X, max_n=None)
     n, d = int(X.shape[0]), int(X.shape[1])
     if pvalue == "chi2" and n < 4:
@@ -494,23 +519,21 @@ def dcor_tests(X, *, pvalue: str = "permutation", num_perm: int = 200, seed: int
         raise ValueError("num_perm must be >= 0")
     iu = np.triu_indices(d, 1)
     pairs = np.stack(iu, axis=1).astype(np.int64)
-    stat, p = np.ones((d, d)), np.zeros((d, d))
+    s = pv = None
     if len(pairs):
         eng = HipDcor(X, device, budget_bytes)
         try:
             if pvalue == "chi2":
                 from scipy import stats
-                s, ge, _ = _dcor_null(eng, pairs, 0, 0, "device", True, budget_bytes, False, 0)
+                s, ge, _ = _engine_null(eng, pairs, 0, 0, "device", False, unbiased=True, budget_bytes=budget_bytes)
                 zero = _zero_range(X)  # (their R_U is 0 by rule, and the rule's p is 1, not chi2.sf(1))
                 pv = np.where(zero[iu[0]] | zero[iu[1]], 1.0, stats.chi2.sf(n * s + 1.0, 1))
             else:
-                s, ge, _ = _dcor_null(eng, pairs, P, seed, perms, False, budget_bytes, False, 0)
+                s, ge, _ = _engine_null(eng, pairs, P, seed, perms, False, budget_bytes=budget_bytes)
                 pv = (ge + 1.0) / (P + 1.0)
         finally:
             eng.close()
-        stat[iu], p[iu] = s, pv
-        stat.T[iu], p.T[iu] = s, pv
-    return stat, p
+    return _mirrored(d, iu, s, pv, 1.0)
 
 
 def _zero_range(X) -> np.ndarray:
@@ -531,25 +554,6 @@ def get_I_from_dcor_tests(X, *, alpha: float = 0.05, pvalue: str = "permutation"
     return _I_from_pvalues(p, alpha, bonferroni, undirected, exclude_diagonal)
 
 
-def _hsic_null(eng: HipHsic, pairs: np.ndarray, P: int, seed: int, perms, tol: float, budget_bytes: int,
-               return_null: bool, chunk: int):
-    n, m = eng.n, len(pairs)
-    kw = dict(tol=tol, chunk=chunk, budget_bytes=budget_bytes, return_null=True)
-    if isinstance(perms, str) and perms == "device":
-        stat, ge, null = eng.run(pairs, P, None, seed, **kw)
-    elif isinstance(perms, str):
-        rng = np.random.default_rng(seed)
-        stat, ge, null = np.zeros(m), np.zeros(m, dtype=np.int64), np.zeros((m, P))
-        step = max(1, _HOST_CHUNK_BYTES // max(1, 4 * P * n))
-        for q0 in range(0, m, step):
-            q1 = min(m, q0 + step)
-            pm = _numpy_perms(rng, q1 - q0, P, n)
-            stat[q0:q1], ge[q0:q1], null[q0:q1] = eng.run(pairs[q0:q1], P, pm, 0, **kw)
-    else:
-        stat, ge, null = eng.run(pairs, P, perms, 0, **kw)
-    return stat, ge, (null if return_null else None)
-
-
 def _hsic_engine(X, device: int, budget_bytes: int, cols, sigma2) -> HipHsic:
     """An engine on X with its bandwidths: the medians of the listed columns (sigma2 None) or the
     given squared bandwidths (d values)."""
@@ -566,8 +570,7 @@ def _hsic_engine(X, device: int, budget_bytes: int, cols, sigma2) -> HipHsic:
 
 
 def _check_hsic_args(perms, num_perm, tol, chunk):
-    if isinstance(perms, str) and perms not in ("numpy", "device"):
-        raise ValueError("perms must be 'numpy', 'device' or an int32 array (m, num_perm, n)")
+    _check_perms(perms)
     if int(num_perm) < 0:
         raise ValueError("num_perm must be >= 0")
     if not 1e-14 <= float(tol) <= 1e-3:
@@ -593,17 +596,15 @@ def hsic_null(X, pairs, *, num_perm: int = 200, seed: int = 0, perms="numpy", to
     n, d = int(X.shape[0]), int(X.shape[1])
     pairs = _as_pairs(pairs, d)
     P = int(num_perm)
-    if not isinstance(perms, str):
-        perms = np.ascontiguousarray(perms, dtype=np.int32)
-        if perms.shape != (len(pairs), P, n):
-            raise ValueError(f"perms must be {(len(pairs), P, n)}, got {perms.shape}")
+    perms = _perm_array(perms, len(pairs), P, n)
     if sigma2 is not None:
         sigma2 = np.ascontiguousarray(sigma2, dtype=np.float64).ravel()
         if sigma2.size != d or not (np.isfinite(sigma2).all() and (sigma2 > 0).all()):
             raise ValueError("sigma2 must hold d finite squared bandwidths > 0")
     eng = _hsic_engine(X, device, budget_bytes, np.unique(pairs), sigma2)
     try:
-        return _hsic_null(eng, pairs, P, seed, perms, float(tol), budget_bytes, return_null, int(chunk))
+        return _engine_null(eng, pairs, P, seed, perms, return_null, tol=float(tol), chunk=int(chunk),
+                            budget_bytes=budget_bytes)
     finally:
         eng.close()
 
@@ -621,8 +622,7 @@ def hsic_tests(X, *, pvalue: str = "permutation", num_perm: int = 200, seed: int
     is not in the reference, which has only the permutation test.  n < 4 raises ValueError."""
     if pvalue not in ("permutation", "chi2"):
         raise ValueError("pvalue must be 'permutation' or 'chi2'")
-    if isinstance(perms, str) and perms not in ("numpy", "device"):
-        raise ValueError("perms must be 'numpy' or 'device'")
+    _check_perms(perms, arrays=False)
     _check_hsic_args(perms, num_perm, tol, 0)
     X = _as_data(X, max_n=None)
     n, d = int(X.shape[0]), int(X.shape[1])
@@ -631,14 +631,14 @@ def hsic_tests(X, *, pvalue: str = "permutation", num_perm: int = 200, seed: int
     P = int(num_perm)
     iu = np.triu_indices(d, 1)
     pairs = np.stack(iu, axis=1).astype(np.int64)
-    stat, p = np.full((d, d), np.nan), np.zeros((d, d))
+    s = pv = None
     if len(pairs):
         eng = _hsic_engine(X, device, budget_bytes, None, sigma2)
         try:
             if pvalue == "chi2":
                 cov, _ = eng.all_pairs(None, tol=float(tol), budget_bytes=budget_bytes)
             else:
-                s, ge, _ = _hsic_null(eng, pairs, P, seed, perms, float(tol), budget_bytes, False, 0)
+                s, ge, _ = _engine_null(eng, pairs, P, seed, perms, False, tol=float(tol), budget_bytes=budget_bytes)
         finally:
             eng.close()
         if pvalue == "chi2":
@@ -648,9 +648,7 @@ def hsic_tests(X, *, pvalue: str = "permutation", num_perm: int = 200, seed: int
             pv = np.where(zero[iu[0]] | zero[iu[1]], 1.0, stats.chi2.sf(n * s + 1.0, 1))
         else:
             pv = (ge + 1.0) / (P + 1.0)
-        stat[iu], p[iu] = s, pv
-        stat.T[iu], p.T[iu] = s, pv
-    return stat, p
+    return _mirrored(d, iu, s, pv, np.nan)
 
 
 def _r_u(cov: np.ndarray) -> np.ndarray:

@@ -721,7 +721,104 @@ class HipGroup(_Handle):
         return self.score_finish()
 
 
-class HipIndep(_Handle):
+def _vp(a):
+    """void* of an array (NULL for None or an empty one, which has no usable address)."""
+    return None if a is None or a.size == 0 else C.c_void_p(a.ctypes.data)
+
+
+class _ColumnEngine(_Handle):
+    """What the test engines over the columns of one X spell alike (csrc/coltest.h), once.  A subclass
+    names its family, the `<family>` of its `midagma_<family>_*` symbols, and keeps its own
+    signatures and docstrings; MAX_N is its cap on n (None: the library's)."""
+
+    _family = ""
+    MAX_N = None
+
+    def __init_subclass__(cls):
+        cls._destroy, cls._last_error = f"midagma_{cls._family}_destroy", f"midagma_{cls._family}_last_error"
+
+    def _call(self, entry: str, *args):
+        """`midagma_<family>_<entry>(handle, *args)`, checked."""
+        rc = getattr(self.L, f"midagma_{self._family}_{entry}")(self.h, *args)
+        self._check(rc, self.h, f"{self._family}_{entry}")
+
+    def _open(self, X, device: int, *budget):
+        """Create the handle on X's device (a device tensor's own) and set the data."""
+        self.L = _lib.lib()
+        self.h = None
+        self.n = self.d = 0
+        what = type(self).__name__
+        if is_device_tensor(X):
+            X = _device_x(X, what, self.MAX_N)
+            device = X.device.index
+        else:
+            X = _host_x(X, what, self.MAX_N)  # (the library copies it to the device and never writes it)
+        h = C.c_void_p()
+        create = getattr(self.L, f"midagma_{self._family}_create")
+        self._check(create(C.byref(h), int(device)), None, f"{self._family}_create")
+        self.h = h
+        try:
+            self._set_data(X, *budget)
+        except Exception:
+            self.close()
+            raise
+
+    def _set_data(self, X, *budget):
+        self.n = self.d = 0
+        what = type(self).__name__
+        if is_device_tensor(X):
+            X = _device_x(X, what, self.MAX_N)
+            n, d, ld = _rows(X)
+            self._call("set_data_dev", C.c_void_p(X.data_ptr()), n, d, ld, *budget, _cur_stream(X.device))
+        else:
+            X = _host_x(X, what, self.MAX_N)
+            n, d = int(X.shape[0]), int(X.shape[1])
+            self._call("set_data", dptr(X), n, d, *budget)
+        self.n, self.d = n, d
+
+    def _set_bandwidths(self, sigma2):
+        s2 = _as_f64(sigma2).ravel()
+        self._call("set_bandwidths", dptr(s2), s2.size)
+
+    def _median_bandwidths(self, cols) -> np.ndarray:
+        if not self.d:
+            raise ValueError(f"{self._family}_median_bandwidths: set the data first")
+        s2 = np.zeros(self.d)
+        if cols is None:
+            cp, nc = None, 0
+        else:
+            cols = np.ascontiguousarray(cols, dtype=np.int64).ravel()
+            if cols.size == 0:  # (an empty array has no usable address)
+                s2[:] = 1.0
+                self._set_bandwidths(s2)
+                return s2
+            cp, nc = C.c_void_p(cols.ctypes.data), int(cols.size)
+        self._call("median_bandwidths", cp, nc, dptr(s2))
+        return s2
+
+    def _run(self, pairs, P: int, perms, seed: int, return_null: bool, *knobs):
+        """`midagma_<family>_run` with the family's `knobs` between the seed and the outputs."""
+        pairs = np.ascontiguousarray(pairs, dtype=np.int64).reshape(-1, 2)
+        m, P = int(pairs.shape[0]), int(P)
+        if perms is not None:
+            perms = np.ascontiguousarray(perms, dtype=np.int32)
+            if perms.shape != (m, P, self.n):
+                raise ValueError(f"perms must be {(m, P, self.n)}, got {perms.shape}")
+        stat = np.zeros(m)
+        ge = np.zeros(m, dtype=np.int64)
+        null = np.zeros((m, max(P, 0))) if return_null else None
+        self._call("run", _vp(pairs), m, P, _vp(perms), C.c_uint64(int(seed) & (2**64 - 1)), *knobs, dptr(stat),
+                   _vp(ge), dptr(null) if (return_null and null.size) else None)
+        return (stat, ge, null) if return_null else (stat, ge)
+
+    def _device_perms(self, q: int, P: int, seed: int, *inverse):
+        out = np.zeros((int(P), self.n), dtype=np.int32)
+        self._call("perms", int(q), int(P), C.c_uint64(int(seed) & (2**64 - 1)), C.c_void_p(out.ctypes.data),
+                   *[None if a is None else C.c_void_p(a.ctypes.data) for a in inverse])
+        return out
+
+
+class HipIndep(_ColumnEngine):
     """Pairwise permutation independence tests on one GPU (`midagma_indep_*`, csrc/indep.hip):
     the engine under `midagma_amd.mi_tests`.  Holds a device copy of X (n x d).
 
@@ -732,67 +829,26 @@ class HipIndep(_Handle):
 
     KINDS = {"hsic": 0, "dcor": 1}
     MAX_N = 16384
-    _destroy, _last_error = "midagma_indep_destroy", "midagma_indep_last_error"
+    _family = "indep"
 
     def __init__(self, X, device: int = 0):
-        self.L = _lib.lib()
-        self.h = None
-        self.n = self.d = 0
-        on_device = is_device_tensor(X)
-        if on_device:
-            X = _device_x(X, "HipIndep", self.MAX_N)
-            device = X.device.index
-        else:
-            X = _host_x(X, "HipIndep", self.MAX_N)  # (the library copies it to the device and never writes it)
-        h = C.c_void_p()
-        self._check(self.L.midagma_indep_create(C.byref(h), int(device)), None, "indep_create")
-        self.h = h
-        try:
-            self.set_data(X)
-        except Exception:
-            self.close()
-            raise
+        self._open(X, device)
 
     def set_data(self, X):
         """Replace the engine's data (bandwidths and pre-passes are dropped).  A device tensor must
         live on the engine's device.  When the library rejects a device X (inf or nan), the engine
         holds no data: every later call raises ValueError until a set_data succeeds."""
-        self.n = self.d = 0
-        if is_device_tensor(X):
-            X = _device_x(X, "HipIndep", self.MAX_N)
-            n, d, ld = _rows(X)
-            rc = self.L.midagma_indep_set_data_dev(self.h, C.c_void_p(X.data_ptr()), n, d, ld, _cur_stream(X.device))
-            self._check(rc, self.h, "indep_set_data_dev")
-        else:
-            X = _host_x(X, "HipIndep", self.MAX_N)
-            n, d = int(X.shape[0]), int(X.shape[1])
-            self._check(self.L.midagma_indep_set_data(self.h, dptr(X), n, d), self.h, "indep_set_data")
-        self.n, self.d = n, d
+        self._set_data(X)
 
     def set_bandwidths(self, sigma2):
         """The RBF kernels' sigma^2 per variable (hsic)."""
-        s2 = _as_f64(sigma2).ravel()
-        self._check(self.L.midagma_indep_set_bandwidths(self.h, dptr(s2), s2.size), self.h, "indep_set_bandwidths")
+        self._set_bandwidths(sigma2)
 
     def median_bandwidths(self, cols=None) -> np.ndarray:
         """sigma^2 per variable by the reference's median heuristic, computed on the device (bit for
         bit `mi_tests.median_sigma2` of the column) for the listed columns (None: all) and 1.0 for
         the others; installed as `set_bandwidths` would.  Returns all d values."""
-        if not self.d:
-            raise ValueError("indep_median_bandwidths: set the data first")
-        s2 = np.zeros(self.d)
-        if cols is None:
-            cp, nc = None, 0
-        else:
-            cols = np.ascontiguousarray(cols, dtype=np.int64).ravel()
-            if cols.size == 0:  # (an empty array has no usable address)
-                s2[:] = 1.0
-                self.set_bandwidths(s2)
-                return s2
-            cp, nc = C.c_void_p(cols.ctypes.data), int(cols.size)
-        self._check(self.L.midagma_indep_median_bandwidths(self.h, cp, nc, dptr(s2)), self.h,
-                    "indep_median_bandwidths")
-        return s2
+        return self._median_bandwidths(cols)
 
     def bandwidth_ms(self) -> float:
         """The last `median_bandwidths`' kernel time in ms (device events; diagnostics)."""
@@ -855,7 +911,7 @@ def column_argsort(X, budget_bytes: int = 0):
     return order
 
 
-class HipDcor(_Handle):
+class HipDcor(_ColumnEngine):
     """dCor permutation tests of pairs of columns without the n^2 sum, on one GPU
     (`midagma_dcor_*`, csrc/dcor.hip): the engine under `mi_tests.dcor_null` / `dcor_tests`, for
     2 <= n < 2^31.  Holds the per-column sorts, centred values and row sums of X (24 bytes a value).
@@ -864,80 +920,32 @@ class HipDcor(_Handle):
     lives on the tensor's device (`device` is ignored), reads X there on torch's current stream
     without a host copy and never writes it.  No synchronise is needed around the call."""
 
-    _destroy, _last_error = "midagma_dcor_destroy", "midagma_dcor_last_error"
+    _family = "dcor"
 
     def __init__(self, X, device: int = 0, budget_bytes: int = 0):
-        self.L = _lib.lib()
-        self.h = None
-        self.n = self.d = 0
-        on_device = is_device_tensor(X)
-        if on_device:
-            X = _device_x(X, "HipDcor")
-            device = X.device.index
-        else:
-            X = _host_x(X, "HipDcor")  # (the library copies it to the device and never writes it)
-        h = C.c_void_p()
-        self._check(self.L.midagma_dcor_create(C.byref(h), int(device)), None, "dcor_create")
-        self.h = h
-        try:
-            self.set_data(X, budget_bytes)
-        except Exception:
-            self.close()
-            raise
+        self._open(X, device, int(budget_bytes))
 
     def set_data(self, X, budget_bytes: int = 0):
         """Replace the engine's data and run the per-column pre-pass.  When the library rejects a
         device X (inf or nan), the engine holds no data."""
-        self.n = self.d = 0
-        if is_device_tensor(X):
-            X = _device_x(X, "HipDcor")
-            n, d, ld = _rows(X)
-            rc = self.L.midagma_dcor_set_data_dev(self.h, C.c_void_p(X.data_ptr()), n, d, ld, int(budget_bytes),
-                                                  _cur_stream(X.device))
-            self._check(rc, self.h, "dcor_set_data_dev")
-        else:
-            X = _host_x(X, "HipDcor")
-            n, d = int(X.shape[0]), int(X.shape[1])
-            self._check(self.L.midagma_dcor_set_data(self.h, dptr(X), n, d, int(budget_bytes)), self.h,
-                        "dcor_set_data")
-        self.n, self.d = n, d
+        self._set_data(X, int(budget_bytes))
 
     def run(self, pairs, P: int, perms=None, seed: int = 0, *, unbiased: bool = False, block: int = 0,
             budget_bytes: int = 0, return_null: bool = False):
         """(stat, ge[, null]) per pair, as `HipIndep.run("dcor", ...)`; unbiased: the bias-corrected
         R_U, counted by dcov^2_U.  perms: explicit m x P x n int32 permutations, or None for device
-        permutations from `seed` (csrc/dcor.hip's rule).  block: the block edge (0: the rule)."""
-        pairs = np.ascontiguousarray(pairs, dtype=np.int64).reshape(-1, 2)
-        m, P = int(pairs.shape[0]), int(P)
-        if perms is not None:
-            perms = np.ascontiguousarray(perms, dtype=np.int32)
-            if perms.shape != (m, P, self.n):
-                raise ValueError(f"perms must be {(m, P, self.n)}, got {perms.shape}")
-        stat = np.zeros(m)
-        ge = np.zeros(m, dtype=np.int64)
-        null = np.zeros((m, max(P, 0))) if return_null else None
-
-        def vp(a):
-            return None if a is None or a.size == 0 else C.c_void_p(a.ctypes.data)
-
-        rc = self.L.midagma_dcor_run(self.h, vp(pairs), m, P, vp(perms), C.c_uint64(int(seed) & (2**64 - 1)),
-                                     int(bool(unbiased)), int(block), int(budget_bytes), dptr(stat), vp(ge),
-                                     dptr(null) if (return_null and null.size) else None)
-        self._check(rc, self.h, "dcor_run")
-        return (stat, ge, null) if return_null else (stat, ge)
+        permutations from `seed` (csrc/coltest.h's rule).  block: the block edge (0: the rule)."""
+        return self._run(pairs, P, perms, seed, return_null, int(bool(unbiased)), int(block), int(budget_bytes))
 
     def device_perms(self, q: int, P: int, seed: int = 0, inverse: bool = False):
         """The P device permutations (P x n int32) of pair q of a call with this seed, and with
         `inverse` their inverses."""
-        out = np.zeros((int(P), self.n), dtype=np.int32)
         inv = np.zeros((int(P), self.n), dtype=np.int32) if inverse else None
-        rc = self.L.midagma_dcor_perms(self.h, int(q), int(P), C.c_uint64(int(seed) & (2**64 - 1)),
-                                       C.c_void_p(out.ctypes.data), None if inv is None else C.c_void_p(inv.ctypes.data))
-        self._check(rc, self.h, "dcor_perms")
+        out = self._device_perms(q, P, seed, inv)
         return (out, inv) if inverse else out
 
 
-class HipHsic(_Handle):
+class HipHsic(_ColumnEngine):
     """HSIC permutation tests of pairs of columns from low-rank factors of the RBF Gram matrices, on
     one GPU (`midagma_hsic_*`, csrc/hsic.hip): the engine under `mi_tests.hsic_null` / `hsic_tests`,
     for 2 <= n < 2^31, and the chi-square test's statistic of every pair at once (`all_pairs`).  Holds the columns of X by row and sorted (16 bytes a value) and the centred
@@ -948,68 +956,25 @@ class HipHsic(_Handle):
     without a host copy and never writes it.  No synchronise is needed around the call."""
 
     TOL = 1e-13
-    _destroy, _last_error = "midagma_hsic_destroy", "midagma_hsic_last_error"
+    _family = "hsic"
 
     def __init__(self, X, device: int = 0, budget_bytes: int = 0):
-        self.L = _lib.lib()
-        self.h = None
-        self.n = self.d = 0
-        on_device = is_device_tensor(X)
-        if on_device:
-            X = _device_x(X, "HipHsic")
-            device = X.device.index
-        else:
-            X = _host_x(X, "HipHsic")  # (the library copies it to the device and never writes it)
-        h = C.c_void_p()
-        self._check(self.L.midagma_hsic_create(C.byref(h), int(device)), None, "hsic_create")
-        self.h = h
-        try:
-            self.set_data(X, budget_bytes)
-        except Exception:
-            self.close()
-            raise
+        self._open(X, device, int(budget_bytes))
 
     def set_data(self, X, budget_bytes: int = 0):
         """Replace the engine's data (bandwidths and factors are dropped).  When the library rejects
         a device X (inf or nan), the engine holds no data."""
-        self.n = self.d = 0
-        if is_device_tensor(X):
-            X = _device_x(X, "HipHsic")
-            n, d, ld = _rows(X)
-            rc = self.L.midagma_hsic_set_data_dev(self.h, C.c_void_p(X.data_ptr()), n, d, ld, int(budget_bytes),
-                                                  _cur_stream(X.device))
-            self._check(rc, self.h, "hsic_set_data_dev")
-        else:
-            X = _host_x(X, "HipHsic")
-            n, d = int(X.shape[0]), int(X.shape[1])
-            self._check(self.L.midagma_hsic_set_data(self.h, dptr(X), n, d, int(budget_bytes)), self.h,
-                        "hsic_set_data")
-        self.n, self.d = n, d
+        self._set_data(X, int(budget_bytes))
 
     def set_bandwidths(self, sigma2):
         """The RBF kernels' sigma^2 per variable (factors are dropped)."""
-        s2 = _as_f64(sigma2).ravel()
-        self._check(self.L.midagma_hsic_set_bandwidths(self.h, dptr(s2), s2.size), self.h, "hsic_set_bandwidths")
+        self._set_bandwidths(sigma2)
 
     def median_bandwidths(self, cols=None) -> np.ndarray:
         """sigma^2 per variable by the reference's median heuristic at any n, on the device (bit for
         bit `mi_tests.median_sigma2` of the column) for the listed columns (None: all) and 1.0 for
         the others; installed as `set_bandwidths` would.  Returns all d values."""
-        if not self.d:
-            raise ValueError("hsic_median_bandwidths: set the data first")
-        s2 = np.zeros(self.d)
-        if cols is None:
-            cp, nc = None, 0
-        else:
-            cols = np.ascontiguousarray(cols, dtype=np.int64).ravel()
-            if cols.size == 0:  # (an empty array has no usable address)
-                s2[:] = 1.0
-                self.set_bandwidths(s2)
-                return s2
-            cp, nc = C.c_void_p(cols.ctypes.data), int(cols.size)
-        self._check(self.L.midagma_hsic_median_bandwidths(self.h, cp, nc, dptr(s2)), self.h,
-                    "hsic_median_bandwidths")
-        return s2
+        return self._median_bandwidths(cols)
 
     def factor(self, cols, tol: float = TOL):
         """(rank, resid) of the listed columns' pivoted incomplete Cholesky factors at `tol`: int32
@@ -1036,25 +1001,8 @@ class HipHsic(_Handle):
             budget_bytes: int = 0, return_null: bool = False):
         """(stat, ge[, null]) per pair, as `HipIndep.run("hsic", ...)` to within 4 tol (1 + tol) plus
         rounding.  perms: explicit m x P x n int32 permutations, or None for device permutations from
-        `seed` (csrc/dcor.hip's rule).  chunk: rows per partial product (0: the rule)."""
-        pairs = np.ascontiguousarray(pairs, dtype=np.int64).reshape(-1, 2)
-        m, P = int(pairs.shape[0]), int(P)
-        if perms is not None:
-            perms = np.ascontiguousarray(perms, dtype=np.int32)
-            if perms.shape != (m, P, self.n):
-                raise ValueError(f"perms must be {(m, P, self.n)}, got {perms.shape}")
-        stat = np.zeros(m)
-        ge = np.zeros(m, dtype=np.int64)
-        null = np.zeros((m, max(P, 0))) if return_null else None
-
-        def vp(a):
-            return None if a is None or a.size == 0 else C.c_void_p(a.ctypes.data)
-
-        rc = self.L.midagma_hsic_run(self.h, vp(pairs), m, P, vp(perms), C.c_uint64(int(seed) & (2**64 - 1)),
-                                     float(tol), int(chunk), int(budget_bytes), dptr(stat), vp(ge),
-                                     dptr(null) if (return_null and null.size) else None)
-        self._check(rc, self.h, "hsic_run")
-        return (stat, ge, null) if return_null else (stat, ge)
+        `seed` (csrc/coltest.h's rule).  chunk: rows per partial product (0: the rule)."""
+        return self._run(pairs, P, perms, seed, return_null, float(tol), int(chunk), int(budget_bytes))
 
     def all_pairs(self, cols=None, *, tol: float = TOL, chunk: int = 0, budget_bytes: int = 0):
         """(cov_u, biased), two k x k host arrays over the listed columns (None: all d): cov_u is
@@ -1079,11 +1027,7 @@ class HipHsic(_Handle):
 
     def device_perms(self, q: int, P: int, seed: int = 0):
         """The P device permutations (P x n int32) of pair q of a call with this seed."""
-        out = np.zeros((int(P), self.n), dtype=np.int32)
-        rc = self.L.midagma_hsic_perms(self.h, int(q), int(P), C.c_uint64(int(seed) & (2**64 - 1)),
-                                       C.c_void_p(out.ctypes.data))
-        self._check(rc, self.h, "hsic_perms")
-        return out
+        return self._device_perms(q, P, seed)
 
     def profile(self) -> dict:
         """Times in ms: the last `median_bandwidths`, and the last run's factorisation, permutations
