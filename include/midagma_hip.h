@@ -476,6 +476,32 @@ int midagma_btrek_set(midagma_batch* h, int seq, int agg, int mode, const double
                       const int64_t* pairs, int64_t m);
 int midagma_btrek_value(midagma_batch* h, const double* W, double* value, double* grad);
 
+/* The logistic loss in a batch (additive, ABI 11; d <= 64, float64 W): the reference's
+ * DagmaLinear("logistic") loop for B problems at once.  The loss has no covariance to fold n into,
+ * so each problem's workgroup streams its X through the score phase of every slot in row blocks
+ * (X^T expit(X W) on the FP64 matrix cores, csrc/small.hip), with fixed-order sums: a problem's W,
+ * result and checkpoint records do not depend on B, on the other problems, on whether X is shared,
+ * or on how the slots are split over launches, bit for bit.  They agree with a data-mode logistic
+ * midagma_solver, which runs the large-tile launch chain, to rounding.  Errors as the batch entries'.
+ * Not run here (MIDAGMA_E_ARG): a trek regularizer set with midagma_btrek_set, a float32 W, a
+ * different n per problem.
+ * set_data: host X, n x d row-major (shared = 1: one X for all B problems, stored once on the
+ *   device) or B x n x d (shared = 0), copied and zero-padded to the device layout.  MIDAGMA_E_ARG:
+ *   a null pointer, n < 1, n >= 2^31, inf/nan in X, or padded slabs that exceed the device's free
+ *   memory (checked before allocating).
+ * minimize: midagma_batch_minimize's arguments and semantics (per-problem mu, s, lr, lambda1;
+ *   active; results; checkpoints through midagma_batch_checkpoints, whose score is the logistic
+ *   loss / n).  Needs midagma_batch_set_cov with the uncentred X^T X / n of each problem (the
+ *   reference's cov, linear.py:428) and set_data first, else MIDAGMA_E_ARG.  Masks apply as for l2.
+ * score: the reference's _score for all B problems at given W (B x d x d host), no Adam step:
+ *   loss holds B values, sum(logaddexp(0, X W) - X o (X W)) / n; G (nullable, B x d x d) is
+ *   X^T expit(X W) / n - cov and needs set_cov. */
+int midagma_blogit_set_data(midagma_batch* h, const double* X, int64_t n, int shared);
+int midagma_blogit_minimize(midagma_batch* h, double* W, const double* mu, const double* s_dom, const double* lr,
+                            const double* lambda1, int64_t max_iter, double tol, double beta1, double beta2,
+                            int64_t checkpoint, const uint8_t* active, midagma_result* res);
+int midagma_blogit_score(midagma_batch* h, const double* W, double* loss, double* G);
+
 /* Bootstrap covariances for a batch, formed on the device from one X (additive, ABI 11).
  * Replicate b of `seed` draws n row indices with replacement:
  *   o = Philox4x32-10(counter (j, b, 0, 0), key (seed & 0xffffffff, seed >> 32)),

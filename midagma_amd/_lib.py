@@ -161,6 +161,11 @@ EXPORTED = {
     # additive to ABI 11: the PST trek regularizer in a batch (HipBatch.set_trek / trek_value, csrc/pst_blk.h)
     "midagma_btrek_set": (_int, [_vp, _int, _int, _int, _dp, _d, C.POINTER(_i64), _i64]),
     "midagma_btrek_value": (_int, [_vp, _dp, _dp, _dp]),
+    # additive to ABI 11: the logistic loss in a batch (HipBatch.set_data / minimize_logistic / score_logistic)
+    "midagma_blogit_set_data": (_int, [_vp, _dp, _i64, _int]),
+    "midagma_blogit_minimize": (_int, [_vp, _dp, _dp, _dp, _dp, _dp, _i64, _d, _d, _d, _i64, _vp,
+                                       C.POINTER(MidagmaResult)]),
+    "midagma_blogit_score": (_int, [_vp, _dp, _dp, _dp]),
     # additive to ABI 11: bootstrap covariances for a batch from one X (HipBatch.boot_cov, csrc/boot.hip)
     "midagma_boot_cov": (_int, [_vp, _vp, _i64, _i64, _int, C.c_uint64, _i64, _i64]),
     "midagma_boot_get_cov": (_int, [_vp, _dp]),
@@ -203,6 +208,7 @@ DEBUG_HOOKS = {
     "midagma_debug_slot_matrices": (_int, [_vp, _dp, _dp]),
     "midagma_debug_live_bytes": (_i64, []),
     "midagma_debug_batch_cov_slabs": (_int, [_vp, _dp]),
+    "midagma_debug_batch_w_slabs": (_int, [_vp, _dp]),
 }
 
 _lock = threading.Lock()

@@ -32,9 +32,22 @@ The device draws replicate b's row indices (`bootstrap_indices(seed, b, n)` rest
 the host) and forms its covariance from counts over one pass of X (csrc/boot.hip), straight into
 problem b of the batch; the stage and retry loop is `fit`'s.
 
+`DagmaLogisticBatch` is the same batch for the reference's other loss, `DagmaLinear("logistic")`,
+the one for binary data:
+
+    W = DagmaLogisticBatch().fit([X0, X1, ...], lambda1=0.02)                 # (B, d, d)
+    W = DagmaLogisticBatch().fit(X, lambda1=[0.005, 0.01, 0.02, 0.05])        # one X on the device, a grid
+
+The logistic loss cannot fold n into a covariance: every Adam step needs X^T expit(X W).  Each
+problem's workgroup streams its X through that step in row blocks on the FP64 matrix cores
+(csrc/small.hip, the logistic score phase); a shared X is stored once.  X is not centred
+(linear.py:410 centres for l2 only).  A problem's result does not depend on the rest of the batch,
+bit for bit, and matches `DagmaLinear("logistic").fit` (the large-tile launch chain) to rounding.
+
 Not in the batch: the TCC trek regularizer, PST with seq log or binom or at d > 32, a pair set per
-problem, float32 W, d > 64, the logistic loss and data mode, several devices, a device X in `fit`
-(`bootstrap` takes one), weighted or m-out-of-n bootstraps.
+problem, float32 W, d > 64, the l2 loss in data mode, several devices, a device X in `fit`
+(`bootstrap` takes one), weighted or m-out-of-n bootstraps.  Not in the logistic batch either: any
+trek regularizer, a different n per problem, a bootstrap.
 """
 from __future__ import annotations
 
@@ -46,7 +59,7 @@ import numpy as np
 from . import _lib
 from .solver import HipBatch, HipSolver, is_device_tensor
 
-__all__ = ["DagmaLinearBatch", "bootstrap_indices"]
+__all__ = ["DagmaLinearBatch", "DagmaLogisticBatch", "bootstrap_indices"]
 
 _M32 = np.uint64(0xFFFFFFFF)
 
@@ -91,13 +104,129 @@ def _edges(edges):
     return None
 
 
-class DagmaLinearBatch:
+class _BatchLoop:
+    """What the batch classes share: the checked problem list, the masks and the lockstep stage and
+    retry loop over a batch backend (`HipBatch`, or a test's CPU double)."""
+
+    _MINIMIZE = "minimize"  # the backend method that runs one minimize call over the batch
+
+    # ------------------------------------------------------------------ inputs
+    def _problems(self, Xs, lambda1, trek_weight=None):
+        """(list of B host X, B lambda1 values), checked; no device work."""
+        def host2d(X):
+            if is_device_tensor(X) or hasattr(X, "data_ptr"):
+                raise ValueError(f"{type(self).__name__} takes host arrays, not device tensors")
+            if not isinstance(X, np.ndarray) or X.dtype != np.float64 or X.ndim != 2:
+                raise ValueError("every X must be a 2-d float64 host array (n x d)")
+            return X
+
+        lam_seq = None if np.ndim(lambda1) == 0 else [float(x) for x in lambda1]
+        tw_len = None if trek_weight is None or np.ndim(trek_weight) == 0 else len(trek_weight)
+        if lam_seq is not None and tw_len is not None and tw_len != len(lam_seq):
+            raise ValueError(f"lambda1 holds {len(lam_seq)} values and trek_weight {tw_len}")
+        if is_device_tensor(Xs) or hasattr(Xs, "data_ptr"):
+            raise ValueError(f"{type(self).__name__} takes host arrays, not device tensors")
+        if isinstance(Xs, np.ndarray) and Xs.ndim == 2:
+            # one X: a lambda1 and / or trek_weight grid (X centred once, cov formed once, shared by
+            # the problems)
+            X = host2d(Xs)
+            xs = [X] * (len(lam_seq) if lam_seq is not None else (tw_len if tw_len is not None else 1))
+        elif isinstance(Xs, np.ndarray):
+            if Xs.ndim != 3 or Xs.dtype != np.float64:
+                raise ValueError("Xs must be a sequence of (n_b, d) float64 arrays, a (B, n, d) array or one (n, d) X")
+            xs = [Xs[b] for b in range(Xs.shape[0])]
+        else:
+            xs = [host2d(X) for X in Xs]
+        B = len(xs)
+        if B == 0:
+            raise ValueError("an empty batch")
+        if B > HipBatch.MAX_B:
+            raise ValueError(f"at most {HipBatch.MAX_B} problems in a batch, got {B}")
+        ds = {int(X.shape[1]) for X in xs}
+        if len(ds) != 1:
+            raise ValueError(f"the problems must share d, got {sorted(ds)}")
+        d = ds.pop()
+        if d < 1 or d > HipBatch.MAX_D:
+            raise ValueError(f"{type(self).__name__} needs 1 <= d <= {HipBatch.MAX_D}, got d = {d}")
+        if any(X.shape[0] < 1 for X in xs):
+            raise ValueError("every X needs at least one row")
+        if lam_seq is None:
+            lam_seq = [lambda1] * B
+        elif len(lam_seq) != B:
+            raise ValueError(f"lambda1 holds {len(lam_seq)} values for {B} problems")
+        return xs, lam_seq, d
+
+    def _masks(self, mu: float, lam, inc, exc, B: int, d: int):
+        """linear.py:217-222 per problem (mask_inc depends on the problem's lambda1)."""
+        mask_inc = mask_exc = None
+        if inc is not None:
+            mask_inc = np.zeros((B, d, d))
+            for b in range(B):
+                mask_inc[b][inc[0], inc[1]] = -2 * mu * lam[b]
+        if exc is not None:
+            mask_exc = np.ones((B, d, d))
+            mask_exc[:, exc[0], exc[1]] = 0.
+        return mask_inc, mask_exc
+
+    # ------------------------------------------------- the loop of fit and bootstrap
+    @staticmethod
+    def _s_list(s, T: int):
+        if isinstance(s, (list, tuple)):
+            return list(s) + max(0, T - len(s)) * [s[-1]]  # linear.py:431-434
+        if type(s) in (int, float):
+            return T * [s]
+        raise ValueError("s should be a list, int, or float.")
+
+    def _stages(self, batch, B, d, lam, T, s0, inc, exc, mu_init, mu_factor, warm_iter, max_iter, lr, checkpoint,
+                beta_1, beta_2):
+        """The path-following loop (linear.py:441-453) over a batch whose cov is set: the stages in
+        lockstep, within a stage every problem that has not yet succeeded re-run with its own
+        halved lr and enlarged s.  Leaves W_est (unthresholded) and minimize_log."""
+        self.W_est = np.zeros((B, d, d))
+        self.minimize_log = [[] for _ in range(B)]
+        s_of = [list(s0) for _ in range(B)]  # each problem enlarges its own s on a failure
+        mu = mu_init
+        for i in range(T):
+            self.vprint(f'\nIteration -- {i+1}:')
+            inner_iters = int(max_iter) if i == T - 1 else int(warm_iter)
+            lr_of = [lr] * B
+            todo = np.ones(B, dtype=bool)
+            batch.set_masks(*self._masks(mu, lam, inc, exc, B, d))
+            while todo.any():
+                t0 = time.time()
+                W_try = self.W_est.copy()
+                s_now = [s_of[b][i] for b in range(B)]
+                res = getattr(batch, self._MINIMIZE)(W_try, mu, s_now, lr_of, lam, inner_iters, beta_1=beta_1, beta_2=beta_2,
+                                     checkpoint=checkpoint, active=todo)
+                seconds = time.time() - t0
+                singular = [b for b in np.flatnonzero(todo) if res[b].status == _lib.ST_SINGULAR]
+                if singular:
+                    raise np.linalg.LinAlgError(
+                        f"singular matrix: inverse of sI - W*W is not finite in problems {singular}")
+                for b in np.flatnonzero(todo):
+                    r = res[b]
+                    self.minimize_log[b].append(dict(mu=mu, s=s_now[b], lr=lr_of[b], max_iter=inner_iters,
+                                                     iters=r.iters, success=r.success, early_stop=r.early_stop,
+                                                     halvings=r.halvings, seconds=seconds))
+                    if r.success:
+                        self.W_est[b] = W_try[b]
+                        todo[b] = False
+                    else:  # this problem alone: a smaller lr and a larger s (linear.py:449-452)
+                        self.vprint(f'problem {b}: W went out of domain for s={s_now[b]} at iteration '
+                                    f'{r.iters + 1}; retrying with larger s')
+                        lr_of[b] *= 0.5
+                        s_of[b][i] += 0.1
+            mu *= mu_factor
+
+
+class DagmaLinearBatch(_BatchLoop):
     """B independent `DagmaLinear('l2')` fits with a common d <= 64 on one GPU."""
 
     def __init__(self, loss_type: str = "l2", verbose: bool = False, dtype: type = np.float64, *,
                  device: int | None = None, trek_reg=None, batch_factory=None, solver_factory=None) -> None:
         if loss_type != "l2":
-            raise ValueError("DagmaLinearBatch runs the l2 loss (cov mode) only")
+            raise ValueError("DagmaLinearBatch runs the l2 loss (cov mode) only; DagmaLogisticBatch runs the "
+                             "logistic loss")
         if np.dtype(dtype).type is not np.float64:
             raise ValueError("DagmaLinearBatch runs a float64 W only")
         self._trek = self._read_trek(trek_reg)
@@ -157,114 +286,6 @@ class DagmaLinearBatch:
     def _trek_final(self, batch, B):
         """The PST value at every unthresholded W_est (zeros without a regularizer)."""
         self.trek_final = np.zeros(B) if self._trek is None else np.asarray(batch.trek_value(self.W_est, grad=False)[0])
-
-    # ------------------------------------------------------------------ inputs
-    def _problems(self, Xs, lambda1, trek_weight=None):
-        """(list of B host X, B lambda1 values), checked; no device work."""
-        def host2d(X):
-            if is_device_tensor(X) or hasattr(X, "data_ptr"):
-                raise ValueError("DagmaLinearBatch takes host arrays, not device tensors")
-            if not isinstance(X, np.ndarray) or X.dtype != np.float64 or X.ndim != 2:
-                raise ValueError("every X must be a 2-d float64 host array (n x d)")
-            return X
-
-        lam_seq = None if np.ndim(lambda1) == 0 else [float(x) for x in lambda1]
-        tw_len = None if trek_weight is None or np.ndim(trek_weight) == 0 else len(trek_weight)
-        if lam_seq is not None and tw_len is not None and tw_len != len(lam_seq):
-            raise ValueError(f"lambda1 holds {len(lam_seq)} values and trek_weight {tw_len}")
-        if is_device_tensor(Xs) or hasattr(Xs, "data_ptr"):
-            raise ValueError("DagmaLinearBatch takes host arrays, not device tensors")
-        if isinstance(Xs, np.ndarray) and Xs.ndim == 2:
-            # one X: a lambda1 and / or trek_weight grid (X centred once, cov formed once, shared by
-            # the problems)
-            X = host2d(Xs)
-            xs = [X] * (len(lam_seq) if lam_seq is not None else (tw_len if tw_len is not None else 1))
-        elif isinstance(Xs, np.ndarray):
-            if Xs.ndim != 3 or Xs.dtype != np.float64:
-                raise ValueError("Xs must be a sequence of (n_b, d) float64 arrays, a (B, n, d) array or one (n, d) X")
-            xs = [Xs[b] for b in range(Xs.shape[0])]
-        else:
-            xs = [host2d(X) for X in Xs]
-        B = len(xs)
-        if B == 0:
-            raise ValueError("an empty batch")
-        if B > HipBatch.MAX_B:
-            raise ValueError(f"at most {HipBatch.MAX_B} problems in a batch, got {B}")
-        ds = {int(X.shape[1]) for X in xs}
-        if len(ds) != 1:
-            raise ValueError(f"the problems must share d, got {sorted(ds)}")
-        d = ds.pop()
-        if d < 1 or d > HipBatch.MAX_D:
-            raise ValueError(f"DagmaLinearBatch needs 1 <= d <= {HipBatch.MAX_D}, got d = {d}")
-        if any(X.shape[0] < 1 for X in xs):
-            raise ValueError("every X needs at least one row")
-        if lam_seq is None:
-            lam_seq = [lambda1] * B
-        elif len(lam_seq) != B:
-            raise ValueError(f"lambda1 holds {len(lam_seq)} values for {B} problems")
-        return xs, lam_seq, d
-
-    def _masks(self, mu: float, lam, inc, exc, B: int, d: int):
-        """linear.py:217-222 per problem (mask_inc depends on the problem's lambda1)."""
-        mask_inc = mask_exc = None
-        if inc is not None:
-            mask_inc = np.zeros((B, d, d))
-            for b in range(B):
-                mask_inc[b][inc[0], inc[1]] = -2 * mu * lam[b]
-        if exc is not None:
-            mask_exc = np.ones((B, d, d))
-            mask_exc[:, exc[0], exc[1]] = 0.
-        return mask_inc, mask_exc
-
-    # ------------------------------------------------- the loop of fit and bootstrap
-    @staticmethod
-    def _s_list(s, T: int):
-        if isinstance(s, (list, tuple)):
-            return list(s) + max(0, T - len(s)) * [s[-1]]  # linear.py:431-434
-        if type(s) in (int, float):
-            return T * [s]
-        raise ValueError("s should be a list, int, or float.")
-
-    def _stages(self, batch, B, d, lam, T, s0, inc, exc, mu_init, mu_factor, warm_iter, max_iter, lr, checkpoint,
-                beta_1, beta_2):
-        """The path-following loop (linear.py:441-453) over a batch whose cov is set: the stages in
-        lockstep, within a stage every problem that has not yet succeeded re-run with its own
-        halved lr and enlarged s.  Leaves W_est (unthresholded) and minimize_log."""
-        self.W_est = np.zeros((B, d, d))
-        self.minimize_log = [[] for _ in range(B)]
-        s_of = [list(s0) for _ in range(B)]  # each problem enlarges its own s on a failure
-        mu = mu_init
-        for i in range(T):
-            self.vprint(f'\nIteration -- {i+1}:')
-            inner_iters = int(max_iter) if i == T - 1 else int(warm_iter)
-            lr_of = [lr] * B
-            todo = np.ones(B, dtype=bool)
-            batch.set_masks(*self._masks(mu, lam, inc, exc, B, d))
-            while todo.any():
-                t0 = time.time()
-                W_try = self.W_est.copy()
-                s_now = [s_of[b][i] for b in range(B)]
-                res = batch.minimize(W_try, mu, s_now, lr_of, lam, inner_iters, beta_1=beta_1, beta_2=beta_2,
-                                     checkpoint=checkpoint, active=todo)
-                seconds = time.time() - t0
-                singular = [b for b in np.flatnonzero(todo) if res[b].status == _lib.ST_SINGULAR]
-                if singular:
-                    raise np.linalg.LinAlgError(
-                        f"singular matrix: inverse of sI - W*W is not finite in problems {singular}")
-                for b in np.flatnonzero(todo):
-                    r = res[b]
-                    self.minimize_log[b].append(dict(mu=mu, s=s_now[b], lr=lr_of[b], max_iter=inner_iters,
-                                                     iters=r.iters, success=r.success, early_stop=r.early_stop,
-                                                     halvings=r.halvings, seconds=seconds))
-                    if r.success:
-                        self.W_est[b] = W_try[b]
-                        todo[b] = False
-                    else:  # this problem alone: a smaller lr and a larger s (linear.py:449-452)
-                        self.vprint(f'problem {b}: W went out of domain for s={s_now[b]} at iteration '
-                                    f'{r.iters + 1}; retrying with larger s')
-                        lr_of[b] *= 0.5
-                        s_of[b][i] += 0.1
-            mu *= mu_factor
 
     def _finals(self, B, d):
         """h and the score of every problem's W_est on self.cov[b], from one ordinary solver: the
@@ -404,5 +425,88 @@ class DagmaLinearBatch:
         self._finals(B, d)
         self.fit_timing = dict(prep_s=t_prep - t_start, loop_s=t_loop - t_prep,
                                final_s=time.perf_counter() - t_loop, cov_on="host")
+        self.W_est[np.abs(self.W_est) < w_threshold] = 0
+        return self.W_est
+
+
+class DagmaLogisticBatch(_BatchLoop):
+    """B independent `DagmaLinear('logistic')` fits with a common n and d <= 64 on one GPU."""
+
+    _MINIMIZE = "minimize_logistic"
+
+    def __init__(self, verbose: bool = False, dtype: type = np.float64, *, device: int | None = None,
+                 trek_reg=None, batch_factory=None, solver_factory=None) -> None:
+        if np.dtype(dtype).type is not np.float64:
+            raise ValueError("DagmaLogisticBatch runs a float64 W only")
+        if trek_reg is not None and trek_reg.enabled():
+            raise ValueError("DagmaLogisticBatch runs no trek regularizer")
+        self.loss_type = "logistic"
+        self.dtype = np.float64
+        self.vprint = print if verbose else (lambda *a, **k: None)
+        self.device = 0 if device is None else int(device)
+        # the backends (tests pass CPU doubles): the batch, and one ordinary solver for h
+        self._batch_factory = batch_factory or HipBatch
+        self._solver_factory = solver_factory or HipSolver
+        self.minimize_log: list = []
+
+    def fit(self, Xs, lambda1: typing.Union[float, typing.Sequence[float]] = 0.03, w_threshold: float = 0.3,
+            T: int = 5, mu_init: float = 1.0, mu_factor: float = 0.1,
+            s: typing.Union[typing.List[float], float] = [1.0, .9, .8, .7, .6],
+            warm_iter: int = 3e4, max_iter: int = 6e4, lr: float = 0.0003, checkpoint: int = 1000,
+            beta_1: float = 0.99, beta_2: float = 0.999,
+            exclude_edges: typing.Optional[typing.Tuple[typing.Tuple[int, int], ...]] = None,
+            include_edges: typing.Optional[typing.Tuple[typing.Tuple[int, int], ...]] = None) -> np.ndarray:
+        """Runs DAGMA with the logistic loss (linear.py:335-462) on every problem and returns the
+        thresholded weighted adjacencies, (B, d, d).
+
+        Xs: a sequence of B host float64 arrays (n, d) with a common n and d, a (B, n, d) array, or
+        one (n, d) X with `lambda1` a length-B sequence (a lambda1 grid: X is stored once on the
+        device and every problem reads it).  X is neither centred nor written.  The other
+        arguments are `DagmaLinear.fit`'s and shared by the problems; the caller's `s` list is not
+        changed.
+
+        Leaves W_est (B, d, d), W_unthresholded (its values before the threshold), h_final (B,),
+        score_final (B,; the logistic loss of the unthresholded W_est, from the batch's own
+        row-block kernel), minimize_log (B lists with
+        `DagmaLinear.minimize_log`'s fields) and fit_timing.  Raises ValueError, before any device
+        work, for Xs of different n, d > 64, a device tensor or a non-float64 X, and
+        np.linalg.LinAlgError naming the problems whose s I - W o W became singular."""
+        t_start = time.perf_counter()
+        xs, lam, d = self._problems(Xs, lambda1)
+        ns = {int(X.shape[0]) for X in xs}
+        if len(ns) != 1:
+            raise ValueError(f"DagmaLogisticBatch needs one n for all problems, got {sorted(ns)}")
+        B, T = len(xs), int(T)
+        s0 = self._s_list(s, T)
+        inc, exc = _edges(include_edges), _edges(exclude_edges)
+        self.B, self.d, self.lambda1, self.checkpoint = B, d, lam, checkpoint
+        shared = all(X is xs[0] for X in xs)
+        # cov = X^T X / n of the uncentred X, once per distinct X (linear.py:428)
+        covs: dict = {}
+        for X in xs:
+            if id(X) not in covs:
+                covs[id(X)] = X.T @ X / float(X.shape[0])
+        self.cov = [covs[id(X)] for X in xs]
+        batch = self._batch_factory(d, B, device=self.device)
+        try:
+            batch.set_cov(np.stack(self.cov))
+            batch.set_data(xs[0] if shared else np.stack(xs), shared=shared)
+            t_prep = time.perf_counter()
+            self._stages(batch, B, d, lam, T, s0, inc, exc, mu_init, mu_factor, warm_iter, max_iter, lr, checkpoint,
+                         beta_1, beta_2)
+            self.score_final = np.asarray(batch.score_logistic(self.W_est, grad=False)[0], dtype=np.float64)
+        finally:
+            batch.close()
+        t_loop = time.perf_counter()
+        self.h_final = np.empty(B)
+        solver = self._solver_factory(d, "l2", "cov", device=self.device)  # (h does not read the loss)
+        try:
+            for b in range(B):
+                self.h_final[b], _ = solver.h_value(self.W_est[b], 1.0, grad=True)
+        finally:
+            solver.close()
+        self.fit_timing = dict(prep_s=t_prep - t_start, loop_s=t_loop - t_prep,
+                               final_s=time.perf_counter() - t_loop, cov_on="host")
+        self.W_unthresholded = self.W_est.copy()
         self.W_est[np.abs(self.W_est) < w_threshold] = 0
         return self.W_est

@@ -1,12 +1,16 @@
-// A batch of B independent small-d problems (d <= 64, l2, cov mode, float64; at d <= 32 with the
-// PST trek regularizer) behind the midagma_batch_* and midagma_btrek_* entries of the C ABI: the
+// A batch of B independent small-d problems (d <= 64, float64; l2 in cov mode, at d <= 32 with the
+// PST trek regularizer, or the logistic loss on each problem's X) behind the midagma_batch_*,
+// midagma_btrek_* and midagma_blogit_* entries of the C ABI: the
 // small-d persistent loop (small.hip) with one workgroup per problem.  Without a regularizer,
 // problem b's result is bit-identical to what a midagma_solver gives for that problem alone: the
 // same kernel instantiation runs it, on Params / State / (-mu) cov / W / m / v filled as
 // midagma_solver::begin fills them (solver_impl.h's shared helpers), and the kernel's results do
 // not depend on how the host splits slots over launches.  With PST (pst_blk.h's body in the
 // slots; the single solver runs trek.hip's launch chain) a problem's result does not depend on
-// the rest of the batch, and agrees with the single solver's to rounding.
+// the rest of the batch, and agrees with the single solver's to rounding.  The logistic loss
+// (midagma_blogit_*) runs small.hip's row-block score phase over the problem's X inside the slots,
+// where the single solver runs gemm.hip's launch chain: again independent of the rest of the batch
+// bit for bit, and equal to the single solver to rounding.
 //
 // Device layout: every per-problem array of the single solver with a leading problem index
 // (D x D slabs with D = 64, as the single solver pads d <= 64).  The host relaunches only the
@@ -117,15 +121,17 @@ void midagma_batch::ensure_tables(double b1, double b2, int64_t max_iter, int64_
 
 void midagma_batch::minimize(double* Wh, const double* mu, const double* s_dom, const double* lr,
                              const double* lambda1, int64_t max_iter, double tol, double b1, double b2,
-                             int64_t checkpoint, const uint8_t* active, midagma_result* res) {
+                             int64_t checkpoint, const uint8_t* active, midagma_result* res, bool logistic) {
   ensure_tables(b1, b2, max_iter, checkpoint);
+  const SmallLogit lg = logistic ? logit_view() : SmallLogit{};
   int64_t n_run = 0;
   for (int64_t b = 0; b < B; ++b) {
     last_active[b] = !active || active[b];
     if (!last_active[b]) continue;
     h_params.p[b] = cov_l2_params(d, D, mu[b], s_dom[b], lambda1[b], tol, b1, b2, max_iter, checkpoint, bc_len,
                                   has_inc, has_exc);
-    if (trek.mode) {
+    if (logistic) logistic_data_params(h_params.p[b], mu[b], (double)x_n);
+    if (trek.mode && !logistic) {
       h_params.p[b].trek_weight = trek_weight[b];
       h_params.p[b].trek_mode = trek.mode;
     }
@@ -150,9 +156,11 @@ void midagma_batch::minimize(double* Wh, const double* mu, const double* s_dom, 
   const int64_t cap = slot_cap(max_iter, checkpoint);
   for (int64_t launched = 0; n_run > 0;) {
     const int64_t slots = small_next_batch(-1, launched, cap, midagma_solver::kSmallBatch);
-    launch_small_minimize(d_params.p, d_state.p, W.p, m.p, v.p, covs.p, has_inc ? minc.p : nullptr,
-                          has_exc ? mexc.p : nullptr, bc_table.p, d_ckpt.p, ckpt_cap, carry.p, pstore.p, d, slots,
-                          stream, nullptr, false, d_index.p, n_run, trek.mode ? &trek : nullptr);
+    // (the logistic slots read the plain cov: G_score = (zscale X)^T expit(X W) + cscale cov)
+    launch_small_minimize(d_params.p, d_state.p, W.p, m.p, v.p, logistic ? cov.p : covs.p,
+                          has_inc ? minc.p : nullptr, has_exc ? mexc.p : nullptr, bc_table.p, d_ckpt.p, ckpt_cap,
+                          carry.p, pstore.p, d, slots, stream, nullptr, false, d_index.p, n_run,
+                          trek.mode && !logistic ? &trek : nullptr, logistic ? &lg : nullptr);
     launched += slots;
     HIP_TRY(hipMemcpyAsync(h_state.p, d_state.p, B * sizeof(State), hipMemcpyDeviceToHost, stream));
     HIP_TRY(hipStreamSynchronize(stream));
@@ -205,6 +213,53 @@ void midagma_batch::trek_value(const double* Wh, double* value, double* grad) {
   HIP_TRY(hipMemcpyAsync(value, trek_val.p, (size_t)B * sizeof(double), hipMemcpyDeviceToHost, stream));
   if (grad)
     download_all(m, grad);
+  else
+    HIP_TRY(hipStreamSynchronize(stream));
+}
+
+SmallLogit midagma_batch::logit_view() const {
+  SmallLogit lg;
+  lg.X = X.p;
+  lg.n = x_n;
+  lg.n_pad = x_n_pad;
+  lg.stride = x_shared ? 0 : x_n_pad * (int64_t)small_block(d);
+  return lg;
+}
+
+// host X (n x d per problem) -> the device layout: n_pad x DS doubles per problem, zero padding
+void midagma_batch::set_data(const double* Xh, int64_t n, bool shared) {
+  const int64_t ds = small_block(d), rb = small_logit_rows(d);
+  const int64_t n_pad = (n + rb - 1) / rb * rb, count = shared ? 1 : B;
+  const size_t slab = (size_t)n_pad * ds, bytes = (size_t)count * slab * sizeof(double);
+  has_data = false;
+  X.release();  // (the last X does not count against the new one; every entry ends synchronized)
+  size_t free_b = 0, total_b = 0;
+  HIP_TRY(hipMemGetInfo(&free_b, &total_b));
+  if (bytes > free_b)
+    throw std::invalid_argument("blogit_set_data: the padded X (" + std::to_string(bytes) +
+                                " bytes) does not fit the device's free memory (" + std::to_string(free_b) + ")");
+  X.alloc((size_t)count * slab);
+  logit_loss.alloc((size_t)B);
+  std::vector<double> pad(slab, 0.0);  // (rows n.., columns d.. stay zero over the problems)
+  for (int64_t b = 0; b < count; ++b) {
+    const double* src = Xh + b * n * d;
+    for (int64_t i = 0; i < n; ++i)
+      for (int64_t j = 0; j < d; ++j) pad[(size_t)(i * ds + j)] = src[i * d + j];
+    HIP_TRY(hipMemcpy(X.p + (size_t)b * slab, pad.data(), slab * sizeof(double), hipMemcpyHostToDevice));
+  }
+  x_n = n;
+  x_n_pad = n_pad;
+  x_shared = shared;
+  has_data = true;
+}
+
+// (W and m serve as the call's scratch slabs, as in trek_value)
+void midagma_batch::logit_score(const double* Wh, double* loss, double* G) {
+  upload_all(W, Wh);
+  launch_small_logit_eval(W.p, cov.p, d, D, B, logit_view(), logit_loss.p, G ? m.p : nullptr, stream);
+  HIP_TRY(hipMemcpyAsync(loss, logit_loss.p, (size_t)B * sizeof(double), hipMemcpyDeviceToHost, stream));
+  if (G)
+    download_all(m, G);
   else
     HIP_TRY(hipStreamSynchronize(stream));
 }
@@ -331,4 +386,56 @@ extern "C" int midagma_btrek_value(midagma_batch* h, const double* W, double* va
     return MIDAGMA_OK;
   }
   return abi_guarded(h, [&] { h->trek_value(W, value, grad); });
+}
+
+extern "C" int midagma_blogit_set_data(midagma_batch* h, const double* X, int64_t n, int shared) {
+  if (!h) return abi_fail(h, MIDAGMA_E_ARG, "blogit_set_data: null handle");
+  if (!X) return abi_fail(h, MIDAGMA_E_ARG, "blogit_set_data: null argument");
+  if (n < 1 || n >= ((int64_t)1 << 31)) return abi_fail(h, MIDAGMA_E_ARG, "blogit_set_data: need 1 <= n < 2^31");
+  if (!finite_block(X, (shared ? 1 : h->B) * n * h->d))
+    return abi_fail(h, MIDAGMA_E_ARG, "blogit_set_data: array must not contain infs or NaNs");
+  return abi_guarded(h, [&] { h->set_data(X, n, shared != 0); });
+}
+
+extern "C" int midagma_blogit_minimize(midagma_batch* h, double* W, const double* mu, const double* s_dom,
+                                       const double* lr, const double* lambda1, int64_t max_iter, double tol,
+                                       double beta1, double beta2, int64_t checkpoint, const uint8_t* active,
+                                       midagma_result* res) {
+  if (!h) return abi_fail(h, MIDAGMA_E_ARG, "blogit_minimize: null handle");
+  if (!W || !mu || !s_dom || !lr || !lambda1 || !res)
+    return abi_fail(h, MIDAGMA_E_ARG, "blogit_minimize: null argument");
+  if (max_iter < 1 || checkpoint < 1)
+    return abi_fail(h, MIDAGMA_E_ARG, "blogit_minimize: max_iter and checkpoint must be >= 1");
+  if (!h->has_cov || !h->has_data)
+    return abi_fail(h, MIDAGMA_E_ARG, "blogit_minimize: set_cov and blogit_set_data before minimize");
+  if (h->trek.mode)
+    return abi_fail(h, MIDAGMA_E_ARG, "blogit_minimize: the logistic loss runs without a trek regularizer");
+  const int64_t dd = h->d * h->d;
+  for (int64_t b = 0; b < h->B; ++b)
+    if ((!active || active[b]) && !finite_block(W + b * dd, dd))
+      return abi_fail(h, MIDAGMA_E_ARG, "blogit_minimize: array must not contain infs or NaNs");
+  return abi_guarded(h, [&] {
+    h->minimize(W, mu, s_dom, lr, lambda1, max_iter, tol, beta1, beta2, checkpoint, active, res, true);
+  });
+}
+
+extern "C" int midagma_blogit_score(midagma_batch* h, const double* W, double* loss, double* G) {
+  if (!h) return abi_fail(h, MIDAGMA_E_ARG, "blogit_score: null handle");
+  if (!W || !loss) return abi_fail(h, MIDAGMA_E_ARG, "blogit_score: null argument");
+  if (!h->has_data || (G && !h->has_cov))
+    return abi_fail(h, MIDAGMA_E_ARG, "blogit_score: blogit_set_data (and set_cov for the gradient) first");
+  if (!finite_block(W, h->B * h->d * h->d))
+    return abi_fail(h, MIDAGMA_E_ARG, "blogit_score: array must not contain infs or NaNs");
+  return abi_guarded(h, [&] { h->logit_score(W, loss, G); });
+}
+
+// Test hook (not in the public header): the batch's W slabs as the last minimize call left them on
+// the device, B x D x D with D = 64, padding included.
+extern "C" int midagma_debug_batch_w_slabs(midagma_batch* h, double* out) {
+  if (!h || !out) return abi_fail(h, MIDAGMA_E_ARG, "debug_batch_w_slabs: null argument");
+  return abi_guarded(h, [&] {
+    HIP_TRY(hipMemcpyAsync(out, h->W.p, (size_t)h->B * h->D * h->D * sizeof(double), hipMemcpyDeviceToHost,
+                           h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+  });
 }

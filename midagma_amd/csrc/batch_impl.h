@@ -1,6 +1,6 @@
-// The batch of small-d problems behind the midagma_batch_* and midagma_boot_* entries: the handle
-// that batch.hip (create, set_cov, masks, minimize) and boot.hip (the bootstrap covariances written
-// into the handle's cov slabs) share.
+// The batch of small-d problems behind the midagma_batch_*, midagma_btrek_*, midagma_blogit_* and
+// midagma_boot_* entries: the handle that batch.hip (create, set_cov, masks, minimize, the logistic
+// loss's X) and boot.hip (the bootstrap covariances written into the handle's cov slabs) share.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -35,6 +35,11 @@ struct midagma_batch {
   DevBuf<> trek_N, trek_val;
   midagma::SmallPst trek{};  // (mode 0: off)
   std::vector<double> trek_weight;
+  // the logistic loss (midagma_blogit_*): X padded to n_pad x small_block(d) doubles per problem,
+  // stored once when the problems share it
+  DevBuf<> X, logit_loss;
+  int64_t x_n = 0, x_n_pad = 0;
+  bool x_shared = false, has_data = false;
   std::vector<uint8_t> last_active;  // the problems of the last minimize call (their checkpoints)
   double boot_ms[4] = {0, 0, 0, 0};  // the last boot_cov: centring, counts, Gram, finish (device events)
 
@@ -56,7 +61,10 @@ struct midagma_batch {
   void ensure_tables(double b1, double b2, int64_t max_iter, int64_t checkpoint);
   void minimize(double* Wh, const double* mu, const double* s_dom, const double* lr, const double* lambda1,
                 int64_t max_iter, double tol, double b1, double b2, int64_t checkpoint, const uint8_t* active,
-                midagma_result* res);
+                midagma_result* res, bool logistic = false);
+  midagma::SmallLogit logit_view() const;
+  void set_data(const double* Xh, int64_t n, bool shared);
+  void logit_score(const double* Wh, double* loss, double* G);
   void set_trek(int seq, int agg, int mode, const double* weight, double eps_inv, const int64_t* pairs, int64_t m);
   void trek_value(const double* Wh, double* value, double* grad);
 };

@@ -18,6 +18,7 @@
 #include "binv_tile.h"
 #include "control.h"
 #include "launch.h"
+#include "logit_math.h"
 #include "mfma64.h"
 #include "nm_series.h"
 
@@ -29,14 +30,6 @@ struct IMinus {
     return ((k0 + r) == (n0 + c) ? 1.0 : 0.0) - v;
   }
 };
-
-// numpy.logaddexp(0, x) (npy_math: log1p/exp split on the sign of the difference)
-__device__ __forceinline__ double logaddexp0(double x) {
-  if (x == 0.0) return 0.69314718055994530942;
-  const double t = -x;
-  if (t > 0) return log1p(exp(-t));
-  return x + log1p(exp(t));
-}
 
 template <bool ATRANS, int BMODE, int EPI>
 __global__ __launch_bounds__(NTHREADS) void gemm_kernel(int64_t K, int64_t kslice, const double* __restrict__ A,
@@ -80,7 +73,7 @@ __global__ __launch_bounds__(NTHREADS) void gemm_kernel(int64_t K, int64_t kslic
       const double x = A[gi * lda + gj];
       part += logaddexp0(v) - x * v;
     }
-    Ct[(int64_t)row * ldc + col] = 1.0 / (1.0 + exp(-v));
+    Ct[(int64_t)row * ldc + col] = expit(v);
   });
   if (!want_loss) return;
   __shared__ double red[NTHREADS];
@@ -570,7 +563,7 @@ __device__ __forceinline__ void gemm_pipe_tile(int t, int64_t K, int64_t kslice,
         const double v = stg[(2 * tt + j) * 64];
         if (want_loss && row < m_valid && col + j < n_valid)
           part += logaddexp0(v) - (AMODE ? A[(col + j) * lda + row] : A[row * lda + col + j]) * v;
-        (j ? o.y : o.x) = 1.0 / (1.0 + exp(-v));
+        (j ? o.y : o.x) = expit(v);
       }
       *reinterpret_cast<double2*>(Ct + row * ldc + col) = o;
     }

@@ -282,11 +282,30 @@ struct SmallPst {
   int seq = 0, agg = 0;       // TrekSeq (exp or inv), TrekAgg
   int mode = 0;               // 1 'log', 2 'opt'
 };
+// logit (nullable; a batch, float64, no tcc, no pst): the logistic loss.  The score phase streams
+// the problem's X (below) through the workgroup in row blocks, Z = (Params.zscale X)^T expit(X W)
+// (X^T scaled before the product, as linear.py:246 scales it), and the slot's gradient is
+// Z + Params.cscale * cov, so `covs` holds the plain cov (not (-mu) cov); the checkpoint
+// objective's score is Params.logit_scale * the logistic loss.
+struct SmallLogit {
+  const double* X = nullptr;  // n_pad x small_block(d) doubles per problem, row-major, zero padding
+  int64_t n = 0;              // valid rows
+  int64_t n_pad = 0;          // rows stored: a multiple of small_logit_rows(d)
+  int64_t stride = 0;         // doubles between two problems' X (0: one X shared by all)
+};
+// rows of one X block of the logistic score phase (and what n_pad is a multiple of)
+int small_logit_rows(int64_t d);
 void launch_small_minimize(const Params* pr, State* st, double* W, double* m, double* v, const double* covs,
                            const double* minc, const double* mexc, const double* bc_table, CkptRec* ckpt,
                            int64_t ckpt_cap, double* carry, double* pstore, int64_t d, int64_t n_slots,
                            hipStream_t stream, const SmallTcc* tcc = nullptr, bool w32 = false,
-                           const int32_t* index = nullptr, int64_t n_problems = 1, const SmallPst* pst = nullptr);
+                           const int32_t* index = nullptr, int64_t n_problems = 1, const SmallPst* pst = nullptr,
+                           const SmallLogit* logit = nullptr);
+// The reference's logistic _score (linear.py:89-92) of n_problems matrices (D x D slabs of W), one
+// workgroup each, on the row-block body of the slots: loss[b] = sum(logaddexp(0, X W) - X o (X W)) / n
+// and, with G (D x D slabs, nullable), (X^T / n) expit(X W) - cov on the d x d block.
+void launch_small_logit_eval(const double* W, const double* cov, int64_t d, int64_t D, int64_t n_problems,
+                             const SmallLogit& lg, double* loss, double* G, hipStream_t stream);
 // The PST penalty of n_problems matrices (D x D slabs of W, d <= 32), one workgroup each, no Adam
 // step: value[b] and, with grad (D x D slabs, nullable), d value / d W on the d x d block.
 void launch_small_pst_eval(const double* W, int64_t d, int64_t D, int64_t n_problems, const SmallPst& ps,

@@ -25,9 +25,22 @@
 // (w / (DS/16), w % (DS/16)); lane l owns column 16 tc + (l & 15), rows 16 tr + (l >> 4) + 4 t
 // for t = 0..3.  DS = 16, 32, 64 -> 1, 4, 16 waves.
 // Arithmetic per element is step.hip's, in the same order (built with -ffp-contract=off).
+//
+// The logistic loss (LOGIT; a batch, float64, no regularizer) has no covariance to fold n into:
+// its score phase streams the problem's X (n_pad x DS doubles, zero padding) through the workgroup
+// in blocks of kLogitRows rows, in ascending order.  Per block, R = X_blk W on the matrix cores
+// against the W image in LDS, S = expit(R) staged through LDS (the accumulator layout is not the
+// B-operand layout), Z += (mu / n X_blk)^T S into the owner's accumulator (X^T scaled first, as
+// the reference scales it), so Z lands where rhs lands for l2.  A block is loaded once: the wave takes its X_blk^T fragments for the second product into
+// registers while the block is current, which lets two X buffers and two S buffers run at one
+// barrier a block.  The S buffers alias the product form's operand images (the inverse and the
+// score phase never overlap), the X buffers take the place of the (-mu) cov image.  On checkpoint
+// slots the lanes also sum logaddexp(0, R) - X o R over the valid n x d entries.  Every sum has a
+// fixed order (blocks ascending, lanes, waves), so a problem's result does not depend on the batch.
 #include <type_traits>
 
 #include "launch.h"
+#include "logit_math.h"
 #include "np_sum.h"
 #include "mfma64.h"
 #include "tcc_blk.h"
@@ -110,6 +123,108 @@ __device__ __forceinline__ dbl4 tile_mma(const double* __restrict__ A, const dou
     acc = __builtin_amdgcn_mfma_f64_16x16x4f64(A[(row0 + c) * SA_ + 4 * kk + q], B[(4 * kk + q) * SB_ + col0 + c],
                                                acc, 0, 0, 0);
   return acc;
+}
+
+// Rows of one X block of the logistic score phase.  DS <= 32: DS rows, so the block's R has one
+// 16 x 16 tile per wave; DS = 64: 32 rows (8 of the 16 waves form R), which is what fits beside
+// the inverse's images in the CU's 160 KB of LDS.
+template <int DS>
+constexpr int kLogitRows = DS >= 64 ? 32 : DS;
+
+// The logistic score phase of one workgroup: z += (xscale X)^T expit(X W) over the nb = n_pad / RB
+// row blocks of X, for the 16 x 16 tile (tr, tc) this wave owns.  X^T is scaled before the product,
+// entry by entry, as the reference's `mu / n * X.T @ sigmoid(X @ W)` scales it (linear.py:246), and
+// an element's terms are added in ascending row order: with binary X an exactly cancelling entry of
+// G_score keeps the rounding the reference's own sum leaves there, whose sign picks the L1 branch.
+// With want_loss also this lane's share of sum(logaddexp(0, R) - X o R) over the rows < n and
+// columns < di.  W is read as the B operand from
+// the I - W image (off-diagonal entries are -W exactly) and the diagonal words.  Xbuf: 2 x RB x
+// (DS + 2) doubles, S0 / S1: RB x SI doubles each.  Stage s (one barrier each): the second product of
+// block s - 1 from the wave's registers and S[(s - 1) & 1]; the wave's X^T fragments of block s;
+// the first product of block s, its sigmoid into S[s & 1]; block s + 1 from registers into
+// Xbuf[(s + 1) & 1] and block s + 2 from global memory into registers.  Block 0 is stored ahead of
+// the first barrier, which also ends every wave's earlier reads of whatever S0 / S1 alias.
+template <int DS, int NW>
+__device__ __forceinline__ void logit_score_phase(const double* __restrict__ X, int64_t n, int64_t n_pad, int di,
+                                                  double* __restrict__ Xbuf, double* __restrict__ S0,
+                                                  double* __restrict__ S1, const double* __restrict__ IWimg,
+                                                  const double* __restrict__ wdiag, bool want_loss, int tr, int tc,
+                                                  double xscale, dbl4& z, double& loss) {
+  constexpr int RB = kLogitRows<DS>, NT = 64 * NW, TPR = DS / 16, SX = DS + 2;
+  constexpr int SI = ((DS + 15) / 32) * 32 + 16;
+  constexpr int XE = RB * DS / NT;  // elements of a block per thread
+  constexpr bool HOIST = DS <= 32;  // the W fragments stay in registers over the blocks
+  static_assert(XE * NT == RB * DS && RB % 16 == 0 && (RB / 16) * TPR <= NW, "block shape");
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, q = lane >> 4, c = lane & 15;
+  const int rt = w / TPR, ct = w % TPR;  // this wave's tile of the block's R
+  const bool has_r = rt < RB / 16;
+  const int64_t nb = n_pad / RB;
+  double ga[XE], gb[XE], xt[RB / 4];
+  [[maybe_unused]] double wb[HOIST ? DS / 4 : 1];
+  auto w_at = [&](int k, int nn) { return k == nn ? wdiag[k] : -IWimg[k * SI + nn]; };
+  if constexpr (HOIST) {
+#pragma unroll
+    for (int kk = 0; kk < DS / 4; ++kk) wb[kk] = w_at(4 * kk + q, 16 * ct + c);
+  }
+  // a block travels global memory -> registers -> LDS, two blocks ahead of its products: one stage
+  // is shorter than a global load's latency
+  auto load_blk = [&](double(&gr)[XE], int64_t blk) __attribute__((always_inline)) {
+    const double* __restrict__ const Xn = X + blk * (RB * DS);
+#pragma unroll
+    for (int i = 0; i < XE; ++i) gr[i] = Xn[tid + i * NT];
+  };
+  auto store_blk = [&](const double(&gr)[XE], int64_t blk) __attribute__((always_inline)) {
+    double* __restrict__ const Xw = Xbuf + (blk & 1) * (RB * SX);
+#pragma unroll
+    for (int i = 0; i < XE; ++i) {
+      const int e = tid + i * NT;
+      Xw[(e / DS) * SX + e % DS] = gr[i];
+    }
+  };
+  load_blk(ga, 0);
+  if (nb > 1) load_blk(gb, 1);
+  store_blk(ga, 0);
+  z = dbl4{0.0, 0.0, 0.0, 0.0};
+  loss = 0.0;
+  __syncthreads();
+  // stage s; gw holds block s + 1, gl (block s, stored a stage ago) takes block s + 2
+  auto stage = [&](int64_t s, const double(&gw)[XE], double(&gl)[XE]) __attribute__((always_inline)) {
+    const double* __restrict__ const Xc = Xbuf + (s & 1) * (RB * SX);
+    if (s + 2 < nb) load_blk(gl, s + 2);
+    if (s >= 1) {
+      const double* __restrict__ const Sp = ((s - 1) & 1) ? S1 : S0;
+#pragma unroll
+      for (int kk = 0; kk < RB / 4; ++kk)
+        z = __builtin_amdgcn_mfma_f64_16x16x4f64(xt[kk], Sp[(4 * kk + q) * SI + 16 * tc + c], z, 0, 0, 0);
+    }
+    if (s == nb) return;
+#pragma unroll
+    for (int kk = 0; kk < RB / 4; ++kk) xt[kk] = xscale * Xc[(4 * kk + q) * SX + 16 * tr + c];
+    if (has_r) {
+      dbl4 r = dbl4{0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+      for (int kk = 0; kk < DS / 4; ++kk)
+        if (DS < 64 || 4 * kk < di) {  // (X's columns and W's rows >= d are zero)
+          const double wop = HOIST ? wb[HOIST ? kk : 0] : w_at(4 * kk + q, 16 * ct + c);
+          r = __builtin_amdgcn_mfma_f64_16x16x4f64(Xc[(16 * rt + c) * SX + 4 * kk + q], wop, r, 0, 0, 0);
+        }
+      double* __restrict__ const Sc = (s & 1) ? S1 : S0;
+      const int col = 16 * ct + c;
+#pragma unroll
+      for (int t = 0; t < 4; ++t) {
+        const int row = 16 * rt + q + 4 * t;
+        Sc[row * SI + col] = expit(r[t]);
+        // padded rows and columns have R = 0, logaddexp = log 2: they stay out of the loss
+        if (want_loss && s * RB + row < n && col < di) loss += logaddexp0(r[t]) - Xc[row * SX + col] * r[t];
+      }
+    }
+    if (s + 1 < nb) store_blk(gw, s + 1);
+    __syncthreads();
+  };
+  for (int64_t s = 0; s <= nb; s += 2) {
+    stage(s, gb, ga);
+    if (s + 1 <= nb) stage(s + 1, ga, gb);
+  }
 }
 
 struct SmallCtl {
@@ -251,13 +366,13 @@ __device__ __noinline__ void small_control(const SmallCtlParams& pr_, State& S, 
     ctl.bc2 = S.bc2;
 }
 
-template <int DS, int NW, int TCC, bool W32 = false, bool PST = false>
+template <int DS, int NW, int TCC, bool W32 = false, bool PST = false, bool LOGIT = false>
 __global__ __launch_bounds__(64 * NW) void small_minimize_kernel(
     const Params* __restrict__ pr_, State* __restrict__ stg_, double* __restrict__ Wg_, double* __restrict__ mg_,
     double* __restrict__ vg_, const double* __restrict__ covs_, const double* __restrict__ minc_,
     const double* __restrict__ mexc_, const double* __restrict__ bc_table, CkptRec* __restrict__ ckpt_,
     int64_t ckpt_cap, double* __restrict__ carry_, double* __restrict__ pstore_, int64_t n_slots, SmallTcc tc,
-    const int32_t* __restrict__ index, SmallPst ps) {
+    const int32_t* __restrict__ index, SmallPst ps, SmallLogit lg) {
   constexpr int NT = 64 * NW, TPR = DS / 16, TPW = TPR * TPR / NW, E = 4 * TPW;
   // A batch (batch.hip): workgroup blockIdx.x works on problem index[blockIdx.x] of per-problem
   // arrays (Params, State, the D x D slabs, ckpt_cap records, the carry words, the two stored
@@ -287,6 +402,9 @@ __global__ __launch_bounds__(64 * NW) void small_minimize_kernel(
   static_assert(TPW * NW == TPR * TPR, "whole tiles per wave");
   // PST: pst_blk.h's body on this workgroup's ownership (one tile per wave), float64, never with TCC
   static_assert(!PST || (TCC == 0 && !W32 && DS <= 32 && TPW == 1), "PST in the small loop: d <= 32, float64");
+  // LOGIT: the logistic loss (logit_score_phase above), float64 without a regularizer; `covs` is the
+  // plain cov, this lane's entries in registers
+  static_assert(!LOGIT || (TCC == 0 && !W32 && !PST && TPW == 1), "logistic in the small loop: float64, no trek");
   constexpr int SW = DS + 2;                         // W, cov images: 16 rows x 4 cols per read
   constexpr int SI = ((DS + 15) / 32) * 32 + 16;     // I - W image: B operand rows, = 16 mod 32
   // DS = 64: the images are single-buffered (an extra barrier before each rewrite), R / Q serve
@@ -297,7 +415,11 @@ __global__ __launch_bounds__(64 * NW) void small_minimize_kernel(
   constexpr int SB = ONE ? SW : SI;                  // stride of the product form's B images
   __shared__ double Wimg[ONE ? 1 : DS * SW];
   __shared__ double wdiag[DS];
-  __shared__ double Cimg[DS * SW];
+  __shared__ double Cimg[LOGIT ? 1 : DS * SW];
+  // LOGIT: two X blocks in the cov image's place; the two S blocks alias PAbuf and PRbuf below
+  constexpr int LRB = kLogitRows<DS>;
+  __shared__ double Xbuf[LOGIT ? 2 * LRB * SW : 1];
+  static_assert(LRB * SI <= (ONE ? 1 : 2) * DS * SW, "an S block fits a product-form operand image");
   __shared__ double IWimg[DS * SI];
   __shared__ __attribute__((aligned(32))) double rowb[2][DS];
   __shared__ __attribute__((aligned(32))) double colb[2][DS];
@@ -343,7 +465,8 @@ __global__ __launch_bounds__(64 * NW) void small_minimize_kernel(
   __shared__ SmallCtlParams cp;  // (thread 0's)
   __shared__ int64_t next_ck;
   if (tid == 0) {
-    cp = SmallCtlParams{pr->d_log_s, pr->score_scale, pr->mu,          pr->lambda1,   pr->trek_weight,
+    // (LOGIT: the controller's score_scale * sum is step.hip's loss * logit_scale)
+    cp = SmallCtlParams{pr->d_log_s, LOGIT ? pr->logit_scale : pr->score_scale, pr->mu, pr->lambda1, pr->trek_weight,
                         pr->tol,     pr->s,           pr->max_iter,    pr->checkpoint, pr->trek_mode, W32 ? 1 : 0};
     S = *stg;
     next_ck = (S.iter / cp.checkpoint + 1) * cp.checkpoint;
@@ -365,10 +488,17 @@ __global__ __launch_bounds__(64 * NW) void small_minimize_kernel(
     vv[e] = real[e] ? vg[idx] : 0.0;
   }
   // MFMA A operand image: (-mu) cov, zero padding
-  for (int e = tid; e < DS * SW; e += NT) {
-    const int r = e / SW, k = e % SW;
-    Cimg[e] = (r < di && k < di) ? covs[(int64_t)r * D + k] : 0.0;
+  if constexpr (!LOGIT)
+    for (int e = tid; e < DS * SW; e += NT) {
+      const int r = e / SW, k = e % SW;
+      Cimg[e] = (r < di && k < di) ? covs[(int64_t)r * D + k] : 0.0;
+    }
+  [[maybe_unused]] double cv[LOGIT ? E : 1];
+  if constexpr (LOGIT) {
+#pragma unroll
+    for (int e = 0; e < E; ++e) cv[e] = real[e] ? covs[(int64_t)rows[e] * D + cols[e]] : 0.0;
   }
+  [[maybe_unused]] const double* __restrict__ const Xp = LOGIT ? lg.X + prob * lg.stride : nullptr;
   if (!ONE)
     for (int e = tid; e < DS * SW; e += NT) Wimg[e] = 0.0;
   for (int e = tid; e < DS; e += NT) wdiag[e] = 0.0;
@@ -415,6 +545,7 @@ __global__ __launch_bounds__(64 * NW) void small_minimize_kernel(
   // the update's constants in registers (read through pr in the loop, they were reloaded every
   // slot: the out-of-line controller may write memory), and the lane's mask entries, fixed for
   // the launch (linear.py:217-222)
+  [[maybe_unused]] const double c_cscale = pr->cscale;
   const double c_zscale = pr->zscale, c_mu_l1 = pr->mu_l1, c_beta1 = pr->beta1, c_c1 = pr->c1,
                c_beta2 = pr->beta2, c_c2 = pr->c2;
   [[maybe_unused]] const double c_trek_w = PST ? pr->trek_weight : 0.0;
@@ -664,16 +795,29 @@ __global__ __launch_bounds__(64 * NW) void small_minimize_kernel(
 
     // ---- rhs = ((-mu) cov) @ (I - W)  (linear.py:244) on the matrix cores
     double z[E];
+    [[maybe_unused]] double lloss = 0.0;
+    if constexpr (LOGIT) {
+      // ---- Z = X^T expit(X W) over the row blocks of X (linear.py:245-246), the loss when due
+      // (the phase's first barrier, before any S block is written, ends the inverse's reads of the
+      // operand images the S blocks alias)
+      dbl4 acc;
+      logit_score_phase<DS, NW>(Xp, lg.n, lg.n_pad, di, Xbuf, PAbuf, PRbuf, IWimg, wdiag,
+                                (RC ? r_ckpt : S.ckpt_pending) != 0, tr[0], (cols[0] - c) / 16, c_zscale, acc,
+                                lloss);
 #pragma unroll
-    for (int u = 0; u < TPW; ++u) {
-      dbl4 acc = dbl4{0.0, 0.0, 0.0, 0.0};
+      for (int t = 0; t < 4; ++t) z[t] = acc[t];
+    } else {
 #pragma unroll
-      for (int kk = 0; kk < DS / 4; ++kk)
-        if (!ONE || 4 * kk < di)  // (DS <= 32 unguarded, as tile_mma; cov's padding is zero)
-          acc = __builtin_amdgcn_mfma_f64_16x16x4f64(Cimg[(16 * tr[u] + c) * SW + 4 * kk + q],
-                                                     IWimg[(4 * kk + q) * SI + cols[4 * u]], acc, 0, 0, 0);
+      for (int u = 0; u < TPW; ++u) {
+        dbl4 acc = dbl4{0.0, 0.0, 0.0, 0.0};
 #pragma unroll
-      for (int t = 0; t < 4; ++t) z[4 * u + t] = acc[t];
+        for (int kk = 0; kk < DS / 4; ++kk)
+          if (!ONE || 4 * kk < di)  // (DS <= 32 unguarded, as tile_mma; cov's padding is zero)
+            acc = __builtin_amdgcn_mfma_f64_16x16x4f64(Cimg[(16 * tr[u] + c) * SW + 4 * kk + q],
+                                                       IWimg[(4 * kk + q) * SI + cols[4 * u]], acc, 0, 0, 0);
+#pragma unroll
+        for (int t = 0; t < 4; ++t) z[4 * u + t] = acc[t];
+      }
     }
 
     SS_MARK(2)  // the score product on the matrix cores
@@ -703,6 +847,7 @@ __global__ __launch_bounds__(64 * NW) void small_minimize_kernel(
         for (int e = 0; e < E; ++e)
           if (real[e]) l1img[rows[e] * di + cols[e]] = fabsf((float)wv[e]);
       }
+      if constexpr (LOGIT) sd = lloss;  // the controller's sum is the loss
       sd = wave_sum(sd);
       l1 = wave_sum(l1);
       const double lds = wave_sum(ld);
@@ -795,7 +940,8 @@ __global__ __launch_bounds__(64 * NW) void small_minimize_kernel(
       for (int e = 0; e < E; ++e) {
         const double wo = wv[e];
         const double mt = m_entry(a[e], w32);
-        gs[e] = c_zscale * z[e];
+        // (LOGIT: z is (zscale X)^T expit(X W) already; linear.py:246's ... - mu * cov)
+        gs[e] = LOGIT ? z[e] + c_cscale * cv[e] : c_zscale * z[e];
         const double sg = sgn(wo);
         gl1[e] = c_mu_l1 * sg;
         gh[e] = h_term(wo, mt, w32);
@@ -865,7 +1011,7 @@ __global__ __launch_bounds__(64 * NW) void small_minimize_kernel(
         const double wo = wv[e];
         if (act == ACT_STEP) {  // (DS = 64: per element, the form above spills there)
           const double mt = m_entry(a[e], w32);
-          const double gs = c_zscale * z[e];
+          const double gs = LOGIT ? z[e] + c_cscale * cv[e] : c_zscale * z[e];
           const double sg = sgn(wo);
           const double gl1 = c_mu_l1 * sg;
           const double gh = h_term(wo, mt, w32);
@@ -1008,6 +1154,66 @@ __global__ __launch_bounds__(64 * NW) void small_pst_eval_kernel(const double* _
   }
 }
 
+// The reference's logistic _score (linear.py:89-92) of B given matrices, no Adam step: workgroup b
+// runs logit_score_phase on problem b's D x D slab of W and its X; loss[b], and with G (D x D slabs)
+// X^T expit(X W) / n - cov on d x d.
+template <int DS, int NW>
+__global__ __launch_bounds__(64 * NW) void small_logit_eval_kernel(const double* __restrict__ W_,
+                                                                    const double* __restrict__ cov_, int64_t d,
+                                                                    int64_t D, SmallLogit lg,
+                                                                    double* __restrict__ loss_out,
+                                                                    double* __restrict__ G_) {
+  constexpr int NT = 64 * NW, TPR = DS / 16, SW = DS + 2, SI = ((DS + 15) / 32) * 32 + 16;
+  constexpr int RB = kLogitRows<DS>;
+  __shared__ double IWimg[DS * SI];
+  __shared__ double wdiag[DS];
+  __shared__ double Xbuf[2 * RB * SW];
+  __shared__ double Sbuf[2][RB * SI];
+  __shared__ double red[NW];
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  const int q = lane >> 4, c = lane & 15, di = (int)d;
+  const int64_t slab = (int64_t)blockIdx.x * D * D;
+  const double* __restrict__ const W = W_ + slab;
+  const int tr = w / TPR, tc = w % TPR, col = 16 * tc + c;
+  for (int e = tid; e < DS * SI; e += NT) IWimg[e] = 0.0;
+  for (int e = tid; e < DS; e += NT) wdiag[e] = 0.0;
+  __syncthreads();
+#pragma unroll
+  for (int t = 0; t < 4; ++t) {
+    const int row = 16 * tr + q + 4 * t;
+    if (row < di && col < di) {
+      const double wv = W[(int64_t)row * D + col];
+      if (row == col) wdiag[row] = wv;
+      IWimg[row * SI + col] = one_minus(row == col, wv, false);
+    }
+  }
+  __syncthreads();
+  dbl4 z;
+  double loss;
+  const double inv_n = 1.0 / (double)lg.n;
+  logit_score_phase<DS, NW>(lg.X + (int64_t)blockIdx.x * lg.stride, lg.n, lg.n_pad, di, Xbuf, Sbuf[0], Sbuf[1],
+                            IWimg, wdiag, true, tr, tc, inv_n, z, loss);
+  loss = wave_sum(loss);
+  if (lane == 0) red[w] = loss;
+  __syncthreads();
+  if (tid == 0) {
+    double x = 0.0;
+#pragma unroll 1
+    for (int y = 0; y < NW; ++y) x += red[y];
+    loss_out[blockIdx.x] = x * inv_n;
+  }
+  if (G_) {
+#pragma unroll
+    for (int t = 0; t < 4; ++t) {
+      const int row = 16 * tr + q + 4 * t;
+      if (row < di && col < di) {
+        const int64_t idx = slab + (int64_t)row * D + col;
+        G_[idx] = z[t] - cov_[idx];  // (1 / n X^T) @ expit(X W) - cov, linear.py:92
+      }
+    }
+  }
+}
+
 }  // namespace
 
 #ifdef MIDAGMA_KSTAMPS
@@ -1029,11 +1235,22 @@ int small_block(int64_t d) {
   return d <= 16 ? 16 : (d <= 32 ? 32 : (d <= 64 && s64 ? 64 : 0));
 }
 
+int small_logit_rows(int64_t d) {
+  const int ds = small_block(d);
+  return ds == 16 ? kLogitRows<16> : (ds == 32 ? kLogitRows<32> : (ds == 64 ? kLogitRows<64> : 0));
+}
+
+namespace {
+bool logit_ok(const SmallLogit& lg, int rb) {
+  return lg.X && lg.n >= 1 && rb > 0 && lg.n_pad >= lg.n && lg.n_pad % rb == 0 && lg.stride >= 0;
+}
+}  // namespace
+
 void launch_small_minimize(const Params* pr, State* st, double* W, double* m, double* v, const double* covs,
                            const double* minc, const double* mexc, const double* bc_table, CkptRec* ckpt,
                            int64_t ckpt_cap, double* carry, double* pstore, int64_t d, int64_t n_slots,
                            hipStream_t stream, const SmallTcc* tcc, bool w32, const int32_t* index,
-                           int64_t n_problems, const SmallPst* pst) {
+                           int64_t n_problems, const SmallPst* pst, const SmallLogit* logit) {
   const int ds = small_block(d);
   if (ds == 0) throw std::invalid_argument("small_minimize: d > 64");
   if (n_problems < 1 || (!index && n_problems != 1))
@@ -1049,13 +1266,28 @@ void launch_small_minimize(const Params* pr, State* st, double* W, double* m, do
   const bool bs5 = tcc && ds == 32 && d <= 20 && knob("MIDAGMA_EXP_TCC_BS5", 1) != 0;
   const SmallTcc tc = tcc ? *tcc : SmallTcc{};
   const SmallPst ps = pst ? *pst : SmallPst{};
+  if (logit && (tcc || pst || w32 || !index || !logit_ok(*logit, small_logit_rows(d))))
+    throw std::invalid_argument(
+        "small_minimize: the logistic loss runs in a batch, float64, without a trek regularizer, on a padded X");
+  const SmallLogit lg = logit ? *logit : SmallLogit{};
 #define MIDAGMA_SMALL_(DS_, NW_, TCC_, W32_, PST_)                                                                \
   hipLaunchKernelGGL((small_minimize_kernel<DS_, NW_, TCC_, W32_, PST_>), dim3((unsigned)n_problems),             \
                      dim3(64 * NW_), 0, stream, pr, st, W, m, v, covs, minc, mexc, bc_table, ckpt, ckpt_cap, carry, \
-                     pstore, n_slots, tc, index, ps)
+                     pstore, n_slots, tc, index, ps, lg)
 #define MIDAGMA_SMALL(DS_, NW_, TCC_, W32_) MIDAGMA_SMALL_(DS_, NW_, TCC_, W32_, false)
+#define MIDAGMA_SMALL_LOGIT(DS_, NW_)                                                                              \
+  hipLaunchKernelGGL((small_minimize_kernel<DS_, NW_, 0, false, false, true>), dim3((unsigned)n_problems),         \
+                     dim3(64 * NW_), 0, stream, pr, st, W, m, v, covs, minc, mexc, bc_table, ckpt, ckpt_cap, carry, \
+                     pstore, n_slots, tc, index, ps, lg)
   // one wave per 16 x 16 tile
-  if (pst) {
+  if (logit) {
+    if (ds == 16)
+      MIDAGMA_SMALL_LOGIT(16, 1);
+    else if (ds == 32)
+      MIDAGMA_SMALL_LOGIT(32, 4);
+    else
+      MIDAGMA_SMALL_LOGIT(64, 16);
+  } else if (pst) {
     if (ds == 16)
       MIDAGMA_SMALL_(16, 1, 0, false, true);
     else
@@ -1081,6 +1313,7 @@ void launch_small_minimize(const Params* pr, State* st, double* W, double* m, do
   } else {
     MIDAGMA_SMALL(64, 16, 0, false);
   }
+#undef MIDAGMA_SMALL_LOGIT
 #undef MIDAGMA_SMALL
 #undef MIDAGMA_SMALL_
   HIP_TRY(hipGetLastError());
@@ -1098,6 +1331,21 @@ void launch_small_pst_eval(const double* W, int64_t d, int64_t D, int64_t n_prob
   else
     hipLaunchKernelGGL((small_pst_eval_kernel<32, 4>), dim3((unsigned)n_problems), dim3(256), 0, stream, W, d, D, ps,
                        value, grad);
+  HIP_TRY(hipGetLastError());
+}
+
+void launch_small_logit_eval(const double* W, const double* cov, int64_t d, int64_t D, int64_t n_problems,
+                             const SmallLogit& lg, double* loss, double* G, hipStream_t stream) {
+  const int ds = small_block(d);
+  if (ds == 0 || n_problems < 1 || !W || !loss || (G && !cov) || !logit_ok(lg, small_logit_rows(d)))
+    throw std::invalid_argument("small_logit_eval: d <= 64 and a padded X");
+  const dim3 grid((unsigned)n_problems);
+  if (ds == 16)
+    hipLaunchKernelGGL((small_logit_eval_kernel<16, 1>), grid, dim3(64), 0, stream, W, cov, d, D, lg, loss, G);
+  else if (ds == 32)
+    hipLaunchKernelGGL((small_logit_eval_kernel<32, 4>), grid, dim3(256), 0, stream, W, cov, d, D, lg, loss, G);
+  else
+    hipLaunchKernelGGL((small_logit_eval_kernel<64, 16>), grid, dim3(1024), 0, stream, W, cov, d, D, lg, loss, G);
   HIP_TRY(hipGetLastError());
 }
 

@@ -65,6 +65,15 @@ inline Params cov_l2_params(int64_t d, int64_t D, double mu, double s, double la
   p.score_scale = 0.5 / (-mu);
   return p;
 }
+// cov_l2_params' Params turned into those of a data-mode logistic call over n rows: G_score =
+// (mu / n) X^T expit(X W) - mu cov, score = loss / n (linear.py:89-92, 245-246)
+inline void logistic_data_params(Params& p, double mu, double n) {
+  p.logistic = 1;
+  p.zscale = mu / n;
+  p.cscale = -mu;
+  p.score_scale = 0.0;
+  p.logit_scale = 1.0 / n;
+}
 // the State before a call's first slot
 inline State initial_state(double lr) {
   State st{};
@@ -1002,10 +1011,7 @@ struct midagma_solver {
       p.cscale = 0.0;
       p.score_scale = 0.5 / n;
     } else {
-      p.zscale = mu_ / n;
-      p.cscale = -mu_;
-      p.score_scale = 0.0;
-      p.logit_scale = 1.0 / n;
+      logistic_data_params(p, mu_, n);
     }
     hp = p;
     HIP_TRY(hipMemcpyAsync(d_params.p, &hp, sizeof(Params), hipMemcpyHostToDevice, stream));

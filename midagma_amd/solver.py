@@ -1053,7 +1053,12 @@ class HipBatch(_Handle):
     With `set_trek` (d <= 32) the PST trek regularizer runs inside each problem's workgroup
     (csrc/pst_blk.h): one pair list, a weight per problem.  A problem's result then does not
     depend on the rest of the batch, and agrees with `HipSolver.set_trek`'s launch chain to
-    rounding, not bit for bit."""
+    rounding, not bit for bit.
+
+    With `set_data` the logistic loss runs in the same slots (`minimize_logistic`,
+    `midagma_blogit_*`): each workgroup streams its problem's X in row blocks through the score
+    phase.  Float64, no trek regularizer, one n for all problems; results are independent of the
+    rest of the batch bit for bit and agree with `HipSolver(d, "logistic", "data")` to rounding."""
 
     MAX_D, MAX_B, MAX_D_TREK = 64, 16384, 32
     _destroy, _last_error = "midagma_batch_destroy", "midagma_batch_last_error"
@@ -1062,7 +1067,7 @@ class HipBatch(_Handle):
         self.L = _lib.lib()
         self.h = None
         self.d, self.B, self.device = int(d), int(B), int(device)
-        self._has_cov = False
+        self._has_cov = self._has_data = False
         h = C.c_void_p()
         self._check(self.L.midagma_batch_create(C.byref(h), self.d, self.B, self.device), None, "batch_create")
         self.h = h
@@ -1152,8 +1157,43 @@ class HipBatch(_Handle):
         self._check(self.L.midagma_btrek_value(self.h, dptr(W), dptr(v), dptr(G)), self.h, "btrek_value")
         return v, G
 
+    def set_data(self, X, shared: bool = False):
+        """The logistic loss's data (copied, not written): one (n, d) X for all problems, stored once
+        on the device (`shared=True`), or (B, n, d).  ValueError on inf / nan, or when the padded
+        slabs exceed the device's free memory."""
+        X = _as_f64(X)
+        if X.ndim != (2 if shared else 3) or X.shape[-1] != self.d or (not shared and X.shape[0] != self.B) \
+                or X.shape[-2] < 1:
+            raise ValueError(f"X must be (n, {self.d}) shared or ({self.B}, n, {self.d}), got {X.shape} "
+                             f"(shared={bool(shared)})")
+        rc = self.L.midagma_blogit_set_data(self.h, dptr(X), int(X.shape[-2]), 1 if shared else 0)
+        self._check(rc, self.h, "blogit_set_data")
+        self._has_data = True
+
+    def score_logistic(self, W: np.ndarray, grad: bool = True):
+        """The reference's logistic `_score` (linear.py:89-92) of B matrices (B x d x d) on the
+        problems' X and cov, no Adam step: ((B,) losses, (B, d, d) gradients or None)."""
+        W = self._stack(W, "W")
+        if not self._has_data or (grad and not self._has_cov):
+            raise _lib.HipSolverError("blogit_score: set_data (and set_cov for the gradient) first")
+        loss = np.empty(self.B)
+        G = np.empty((self.B, self.d, self.d)) if grad else None
+        self._check(self.L.midagma_blogit_score(self.h, dptr(W), dptr(loss), dptr(G)), self.h, "blogit_score")
+        return loss, G
+
+    def minimize_logistic(self, W: np.ndarray, mu, s, lr, lambda1, max_iter: int, tol: float = 1e-6,
+                          beta_1: float = 0.99, beta_2: float = 0.999, checkpoint: int = 1000, active=None,
+                          want_checkpoints: bool = False):
+        """`minimize` with the logistic loss on the X of `set_data`; `set_cov` holds the uncentred
+        X^T X / n of each problem (linear.py:428)."""
+        if not self._has_data:
+            raise _lib.HipSolverError("blogit_minimize: set_data before minimize_logistic")
+        return self.minimize(W, mu, s, lr, lambda1, max_iter, tol, beta_1, beta_2, checkpoint, active,
+                             want_checkpoints, _entry="midagma_blogit_minimize")
+
     def minimize(self, W: np.ndarray, mu, s, lr, lambda1, max_iter: int, tol: float = 1e-6, beta_1: float = 0.99,
-                 beta_2: float = 0.999, checkpoint: int = 1000, active=None, want_checkpoints: bool = False):
+                 beta_2: float = 0.999, checkpoint: int = 1000, active=None, want_checkpoints: bool = False,
+                 _entry: str = "midagma_batch_minimize"):
         """linear.py:165-333 for every active problem in one launch sequence.  W (B x d x d float64)
         is updated in place; mu, s, lr, lambda1 are scalars or hold B values; active: B booleans
         (None: all).  Returns B `MinimizeResult`s; an inactive problem's W is untouched and its
@@ -1167,10 +1207,10 @@ class HipBatch(_Handle):
         if act is not None and act.shape != (self.B,):
             raise ValueError(f"active must hold {self.B} values")
         res = (_lib.MidagmaResult * self.B)()
-        rc = self.L.midagma_batch_minimize(self.h, dptr(W), dptr(mu), dptr(s), dptr(lr), dptr(lambda1), int(max_iter),
-                                           float(tol), float(beta_1), float(beta_2), int(checkpoint),
-                                           None if act is None else C.c_void_p(act.ctypes.data), res)
-        self._check(rc, self.h, "batch_minimize")
+        rc = getattr(self.L, _entry)(self.h, dptr(W), dptr(mu), dptr(s), dptr(lr), dptr(lambda1), int(max_iter),
+                                     float(tol), float(beta_1), float(beta_2), int(checkpoint),
+                                     None if act is None else C.c_void_p(act.ctypes.data), res)
+        self._check(rc, self.h, _entry[len("midagma_"):])
         return [MinimizeResult.from_c(res[b], self.checkpoints(b) if want_checkpoints else ())
                 if act is None or act[b] else None for b in range(self.B)]
 
