@@ -40,7 +40,7 @@ the one for binary data:
 
 The logistic loss cannot fold n into a covariance: every Adam step needs X^T expit(X W).  Each
 problem's workgroup streams its X through that step in row blocks on the FP64 matrix cores
-(csrc/small.hip, the logistic score phase); a shared X is stored once.  X is not centred
+(csrc/logit_blk.h, the logistic score phase); a shared X is stored once.  X is not centred
 (linear.py:410 centres for l2 only).  A problem's result does not depend on the rest of the batch,
 bit for bit, and matches `DagmaLinear("logistic").fit` (the large-tile launch chain) to rounding.
 

@@ -8,7 +8,7 @@
 // not depend on how the host splits slots over launches.  With PST (pst_blk.h's body in the
 // slots; the single solver runs trek.hip's launch chain) a problem's result does not depend on
 // the rest of the batch, and agrees with the single solver's to rounding.  The logistic loss
-// (midagma_blogit_*) runs small.hip's row-block score phase over the problem's X inside the slots,
+// (midagma_blogit_*) runs logit_blk.h's row-block score phase over the problem's X inside small.hip's slots,
 // where the single solver runs gemm.hip's launch chain: again independent of the rest of the batch
 // bit for bit, and equal to the single solver to rounding.
 //
@@ -157,10 +157,13 @@ void midagma_batch::minimize(double* Wh, const double* mu, const double* s_dom, 
   for (int64_t launched = 0; n_run > 0;) {
     const int64_t slots = small_next_batch(-1, launched, cap, midagma_solver::kSmallBatch);
     // (the logistic slots read the plain cov: G_score = (zscale X)^T expit(X W) + cscale cov)
-    launch_small_minimize(d_params.p, d_state.p, W.p, m.p, v.p, logistic ? cov.p : covs.p,
+    const SmallArrays arr{d_params.p, d_state.p, W.p, m.p, v.p, logistic ? cov.p : covs.p,
                           has_inc ? minc.p : nullptr, has_exc ? mexc.p : nullptr, bc_table.p, d_ckpt.p, ckpt_cap,
-                          carry.p, pstore.p, d, slots, stream, nullptr, false, d_index.p, n_run,
-                          trek.mode && !logistic ? &trek : nullptr, logistic ? &lg : nullptr);
+                          carry.p, pstore.p};
+    SmallRun run{d, slots, d_index.p, n_run};
+    run.pst = trek.mode && !logistic ? &trek : nullptr;
+    run.logit = logistic ? &lg : nullptr;
+    launch_small_minimize(arr, run, stream);
     launched += slots;
     HIP_TRY(hipMemcpyAsync(h_state.p, d_state.p, B * sizeof(State), hipMemcpyDeviceToHost, stream));
     HIP_TRY(hipStreamSynchronize(stream));
@@ -323,20 +326,30 @@ extern "C" int midagma_batch_set_masks(midagma_batch* h, const double* mask_inc,
   });
 }
 
+// The argument checks of the two minimize entries (`what`: the entry's name in the messages)
+static int check_minimize_args(midagma_batch* h, const std::string& what, bool logistic, const double* W,
+                               const double* mu, const double* s_dom, const double* lr, const double* lambda1,
+                               int64_t max_iter, int64_t checkpoint, const uint8_t* active, const midagma_result* res) {
+  const auto bad = [&](const char* why) { return abi_fail(h, MIDAGMA_E_ARG, what + ": " + why); };
+  if (!h) return bad("null handle");
+  if (!W || !mu || !s_dom || !lr || !lambda1 || !res) return bad("null argument");
+  if (max_iter < 1 || checkpoint < 1) return bad("max_iter and checkpoint must be >= 1");
+  if (!logistic && !h->has_cov) return bad("set_cov before minimize");
+  if (logistic && (!h->has_cov || !h->has_data)) return bad("set_cov and blogit_set_data before minimize");
+  if (logistic && h->trek.mode) return bad("the logistic loss runs without a trek regularizer");
+  const int64_t dd = h->d * h->d;
+  for (int64_t b = 0; b < h->B; ++b)
+    if ((!active || active[b]) && !finite_block(W + b * dd, dd)) return bad("array must not contain infs or NaNs");
+  return MIDAGMA_OK;
+}
+
 extern "C" int midagma_batch_minimize(midagma_batch* h, double* W, const double* mu, const double* s_dom,
                                       const double* lr, const double* lambda1, int64_t max_iter, double tol,
                                       double beta1, double beta2, int64_t checkpoint, const uint8_t* active,
                                       midagma_result* res) {
-  if (!h) return abi_fail(h, MIDAGMA_E_ARG, "batch_minimize: null handle");
-  if (!W || !mu || !s_dom || !lr || !lambda1 || !res)
-    return abi_fail(h, MIDAGMA_E_ARG, "batch_minimize: null argument");
-  if (max_iter < 1 || checkpoint < 1)
-    return abi_fail(h, MIDAGMA_E_ARG, "batch_minimize: max_iter and checkpoint must be >= 1");
-  if (!h->has_cov) return abi_fail(h, MIDAGMA_E_ARG, "batch_minimize: set_cov before minimize");
-  const int64_t dd = h->d * h->d;
-  for (int64_t b = 0; b < h->B; ++b)
-    if ((!active || active[b]) && !finite_block(W + b * dd, dd))
-      return abi_fail(h, MIDAGMA_E_ARG, "batch_minimize: array must not contain infs or NaNs");
+  if (const int rc = check_minimize_args(h, "batch_minimize", false, W, mu, s_dom, lr, lambda1, max_iter, checkpoint,
+                                         active, res))
+    return rc;
   return abi_guarded(h, [&] {
     h->minimize(W, mu, s_dom, lr, lambda1, max_iter, tol, beta1, beta2, checkpoint, active, res);
   });
@@ -401,19 +414,9 @@ extern "C" int midagma_blogit_minimize(midagma_batch* h, double* W, const double
                                        const double* lr, const double* lambda1, int64_t max_iter, double tol,
                                        double beta1, double beta2, int64_t checkpoint, const uint8_t* active,
                                        midagma_result* res) {
-  if (!h) return abi_fail(h, MIDAGMA_E_ARG, "blogit_minimize: null handle");
-  if (!W || !mu || !s_dom || !lr || !lambda1 || !res)
-    return abi_fail(h, MIDAGMA_E_ARG, "blogit_minimize: null argument");
-  if (max_iter < 1 || checkpoint < 1)
-    return abi_fail(h, MIDAGMA_E_ARG, "blogit_minimize: max_iter and checkpoint must be >= 1");
-  if (!h->has_cov || !h->has_data)
-    return abi_fail(h, MIDAGMA_E_ARG, "blogit_minimize: set_cov and blogit_set_data before minimize");
-  if (h->trek.mode)
-    return abi_fail(h, MIDAGMA_E_ARG, "blogit_minimize: the logistic loss runs without a trek regularizer");
-  const int64_t dd = h->d * h->d;
-  for (int64_t b = 0; b < h->B; ++b)
-    if ((!active || active[b]) && !finite_block(W + b * dd, dd))
-      return abi_fail(h, MIDAGMA_E_ARG, "blogit_minimize: array must not contain infs or NaNs");
+  if (const int rc = check_minimize_args(h, "blogit_minimize", true, W, mu, s_dom, lr, lambda1, max_iter, checkpoint,
+                                         active, res))
+    return rc;
   return abi_guarded(h, [&] {
     h->minimize(W, mu, s_dom, lr, lambda1, max_iter, tol, beta1, beta2, checkpoint, active, res, true);
   });

@@ -249,23 +249,15 @@ struct DfWork {
 void launch_df_inverse(double* Mt, int64_t D, const DfWork& w, const BInvWork& bw, int passes, State* st,
                        hipStream_t stream);
 
-// --- small.hip --------------------------------------------------------------
+// --- small.hip, small_eval.hip ----------------------------------------------
 // LDS/register block edge of the one-workgroup small-d inner loop (16, 32 or 64; 0: d > 64).
 int small_block(int64_t d);
-// Up to n_slots slots of the cov-mode l2 inner loop (linear.py:224-331) in one persistent
-// workgroup: W, m, v (leading dimension pr->D) are read at entry and written back at exit,
-// with the State.  Across launches: carry (NORM_FIELDS + 1 doubles) holds a pending
-// checkpoint step's norms and the warm-start count, pstore (2 x 32 x 32) the last two
-// inverses; zero carry before a call's first launch.  Slots after a terminal status are
-// not run.
-// tcc (nullable; d <= 32): the TCC trek regularizer inside every slot ('opt') or every
-// checkpoint slot ('log'), tcc_blk.h's body on the workgroup, its state words read at entry and
-// written back at exit (the graph-replayed slots' TccWork words, so the two paths interleave).
-// pst (nullable; d <= 32, float64, no tcc): the PST trek regularizer inside the slots in the same
-// way, pst_blk.h's body; its weight and mode are the problem's Params.trek_weight / trek_mode.
-// index (nullable; float64, no tcc): a batch (batch.hip).  n_problems workgroups, workgroup g on
-// problem index[g] of per-problem arrays: pr and st by 1, the matrices by pr->D * pr->D, ckpt by
-// ckpt_cap, carry by NORM_FIELDS + 1, pstore by 2 * small_block(d)^2; bc_table is shared.
+// The slots' regularizers and the logistic loss, as launch_small_minimize's SmallRun names them.
+// tcc (d <= 32): the TCC trek regularizer inside every slot ('opt') or every checkpoint slot
+// ('log'), tcc_blk.h's body on the workgroup, its state words read at entry and written back at
+// exit (the graph-replayed slots' TccWork words, so the two paths interleave).
+// pst (d <= 32, float64, no tcc): the PST trek regularizer inside the slots in the same way,
+// pst_blk.h's body; its weight and mode are the problem's Params.trek_weight / trek_mode.
 struct SmallTcc {
   const double* S;        // D x D pair indicator
   double ws, eps, m, weight;
@@ -295,12 +287,36 @@ struct SmallLogit {
 };
 // rows of one X block of the logistic score phase (and what n_pad is a multiple of)
 int small_logit_rows(int64_t d);
-void launch_small_minimize(const Params* pr, State* st, double* W, double* m, double* v, const double* covs,
-                           const double* minc, const double* mexc, const double* bc_table, CkptRec* ckpt,
-                           int64_t ckpt_cap, double* carry, double* pstore, int64_t d, int64_t n_slots,
-                           hipStream_t stream, const SmallTcc* tcc = nullptr, bool w32 = false,
-                           const int32_t* index = nullptr, int64_t n_problems = 1, const SmallPst* pst = nullptr,
-                           const SmallLogit* logit = nullptr);
+bool logit_ok(const SmallLogit& lg, int rows);  // a padded X in row blocks of `rows`
+// Up to n_slots slots of the cov-mode l2 inner loop (linear.py:224-331) in one persistent workgroup
+// per problem.  The single solver is the batch of one (no index, n_problems 1).
+struct SmallArrays {  // per problem: a batch strides each array by the problem (the stride in brackets)
+  const Params* pr;        // [1]
+  State* st;               // [1] read at entry, written back at exit; slots after a terminal status are not run
+  double* W;               // [pr->D * pr->D] W, m, v: leading dimension pr->D, read at entry, written back at exit
+  double* m;
+  double* v;
+  const double* cov;       // [pr->D * pr->D] (-mu) cov; with logit the plain cov
+  const double* minc;      // [pr->D * pr->D] the masks (nullable)
+  const double* mexc;
+  const double* bc_table;  // shared: 1 - beta^it pairs
+  CkptRec* ckpt;           // [ckpt_cap]
+  int64_t ckpt_cap;
+  double* carry;           // [NORM_FIELDS + 1] across launches: a pending checkpoint step's norms and the
+                           // warm-start count; zero before a call's first launch
+  double* pstore;          // [2 * small_block(d)^2] across launches: the last two inverses
+};
+struct SmallRun {
+  int64_t d;
+  int64_t n_slots;
+  const int32_t* index = nullptr;     // a batch (float64, no tcc): workgroup g works on problem index[g]
+  int64_t n_problems = 1;             // workgroups
+  bool w32 = false;                   // float32 W (d <= 32, no batch)
+  const SmallTcc* tcc = nullptr;      // each nullable
+  const SmallPst* pst = nullptr;
+  const SmallLogit* logit = nullptr;
+};
+void launch_small_minimize(const SmallArrays& a, const SmallRun& r, hipStream_t stream);
 // The reference's logistic _score (linear.py:89-92) of n_problems matrices (D x D slabs of W), one
 // workgroup each, on the row-block body of the slots: loss[b] = sum(logaddexp(0, X W) - X o (X W)) / n
 // and, with G (D x D slabs, nullable), (X^T / n) expit(X W) - cov on the d x d block.

@@ -1,5 +1,5 @@
 // The logistic loss's two scalar functions, shared by its device paths (gemm.hip's sigmoid
-// epilogues on the large-tile launch chain, small.hip's row-block score phase in the batch) so
+// epilogues on the large-tile launch chain, logit_blk.h's row-block score phase in the batch) so
 // that both use the same arithmetic.
 #pragma once
 

@@ -1,7 +1,7 @@
 // PST trek regularizer (trek.hip) for d <= 32 in ONE workgroup: the device
-// body the small-d persistent inner loop (small.hip) runs inside its slots, on the slot's
-// workgroup and its element ownership (wave w owns the 16 x 16 tile (w / (DS/16), w % (DS/16));
-// lane l owns column 16 tc + (l & 15), rows 16 tr + (l >> 4) + 4 t).
+// body the small-d persistent inner loop (small.hip) runs inside its slots and the evaluation
+// kernel (small_eval.hip) runs once, on the caller's workgroup, its element ownership and its
+// primitives (wgtile.h: the owner map, tile_mma, the wave reductions, the Gauss-Jordan).
 //
 //     W2 = W o W,  F = f(W2),  H = F^T F,  value = agg(H[i_p, j_p]),
 //     C = d value / d H,  G_F = F (C + C^T),  grad = 2 W o L_f(W2, G_F^T)^T
@@ -13,7 +13,7 @@
 //     L_12 = 0,  L_{k-1} = (X L_k + E Q_k) / k,  Q_{k-1} = I + X Q_k / k;   L <- Q L + L Q, Q <- Q^2
 // which costs 12 + s products in pass 1 and 3 (12 + s) in pass 2, each DS^3 on
 // v_mfma_f64_16x16x4f64 with the output in its owner's registers.
-// inv: F = ((1 + eps) I - W2)^-1 by the unpivoted Gauss-Jordan of the slot, L = F E F.
+// inv: F = ((1 + eps) I - W2)^-1 by the slot's unpivoted Gauss-Jordan (wg_gauss_jordan), L = F E F.
 //
 // The pair list enters as its multiplicity matrix N (N[i][j]: how often (i, j) occurs), so value
 // and C are sums over the lane's own elements in a fixed order, with no atomics:
@@ -29,14 +29,14 @@
 #include <cmath>
 
 #include "launch.h"
-#include "mfma64.h"
+#include "wgtile.h"
 
 namespace midagma {
 namespace pstb {
 
 // the caller's idle buffers: two [m][k] pairs (DS x SW each) and one [k][n] pair (DS x SI each)
-// of the product-form inverse, and the Gauss-Jordan pivot row / column pairs (DS each)
-// (each pair contiguous: the second half follows the first)
+// of the product-form inverse, and the Gauss-Jordan pivot row / column pairs (DS each, 32-byte
+// aligned) (each pair contiguous: the second half follows the first)
 struct PstBufs {
   double* pa;
   double* pr;
@@ -48,33 +48,13 @@ struct PstBufs {
 // the body's own LDS
 template <int DS, int NW>
 struct PstLds {
-  static constexpr int SW = DS + 2;
-  double nimg[DS * DS];    // N, zero outside d x d (loaded by the caller)
+  static constexpr int SW = WgTile<DS>::SW;
+  double nimg[DS * DS];    // N, zero outside d x d (loaded by the caller: wg_load_dense)
   double lb[2][DS * SW];   // the derivative's [k][n] images; H and the result for transposed reads
   double colsum[DS];
   double red[4][NW];
   double val;              // the value of the last run
 };
-
-template <int DS, int SA_, int SB_>
-__device__ __forceinline__ dbl4 mma(const double* __restrict__ A, const double* __restrict__ B, int row0, int col0,
-                                    int q, int c) {
-  dbl4 acc = dbl4{0.0, 0.0, 0.0, 0.0};
-#pragma unroll
-  for (int kk = 0; kk < DS / 4; ++kk)
-    acc = __builtin_amdgcn_mfma_f64_16x16x4f64(A[(row0 + c) * SA_ + 4 * kk + q], B[(4 * kk + q) * SB_ + col0 + c],
-                                               acc, 0, 0, 0);
-  return acc;
-}
-
-__device__ __forceinline__ double wsum(double x) {
-  for (int off = 32; off > 0; off >>= 1) x += __shfl_xor(x, off);
-  return x;
-}
-__device__ __forceinline__ double wmax(double x) {
-  for (int off = 32; off > 0; off >>= 1) x = fmax(x, __shfl_xor(x, off));
-  return x;
-}
 
 // d value / d H at one entry, times its multiplicity
 __device__ __forceinline__ double coef(int agg, double n, double h, double mx, double value, double base) {
@@ -94,18 +74,15 @@ __device__ __forceinline__ void pst_blk_body(const SmallPst& ps, int di, const d
                                              bool want_grad, double (&g)[4]) {
   static_assert(DS == 16 || DS == 32, "PST in one workgroup: d <= 32");
   static_assert(NW * 256 == DS * DS, "one 16 x 16 tile per wave");
-  constexpr int TPR = DS / 16, SW = DS + 2, SI = ((DS + 15) / 32) * 32 + 16;
-  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-  const int q = lane >> 4, c = lane & 15;
-  const int row0 = 16 * (w / TPR), col0 = 16 * (w % TPR);
-  const int cj = col0 + c;
-  int ri[4];
-  bool real[4];
+  constexpr int SW = WgTile<DS>::SW, SI = WgTile<DS>::SI;
+  const int tid = threadIdx.x, lane = tid & 63;
+  const WgTile<DS> T(tid, di);
+  const int w = T.w, cj = T.cj;
+  const auto& ri = T.ri;
+  const auto& real = T.real;
   double dl[4];  // the identity on d x d
 #pragma unroll
   for (int t = 0; t < 4; ++t) {
-    ri[t] = row0 + q + 4 * t;
-    real[t] = ri[t] < di && cj < di;
     dl[t] = real[t] && ri[t] == cj ? 1.0 : 0.0;
     g[t] = 0.0;
   }
@@ -113,8 +90,6 @@ __device__ __forceinline__ void pst_blk_body(const SmallPst& ps, int di, const d
   const auto pa = [&](int x) { return B.pa + x * (DS * SW); };
   const auto pr = [&](int x) { return B.pr + x * (DS * SW); };
   const auto pb = [&](int x) { return B.pb + x * (DS * SI); };
-  const auto rowb = [&](int x) { return B.rowb + x * DS; };
-  const auto colb = [&](int x) { return B.colb + x * DS; };
   const bool is_exp = ps.seq == TREK_EXP;
   int p = 0;  // the buffer pair of the next step
   int s = 0;
@@ -132,7 +107,7 @@ __device__ __forceinline__ void pst_blk_body(const SmallPst& ps, int di, const d
       L.colsum[tid] = cs;
     }
     __syncthreads();
-    const double nrm = wmax(lane < DS ? L.colsum[lane] : 0.0);
+    const double nrm = wave_max(lane < DS ? L.colsum[lane] : 0.0);
     while (s < TREK_SMAX && nrm / ldexp(1.0, s) > 0.25) ++s;  // trek_scale_kernel
     scal = ldexp(1.0, -s);
     double qk[4];
@@ -146,7 +121,7 @@ __device__ __forceinline__ void pst_blk_body(const SmallPst& ps, int di, const d
 #pragma unroll
       for (int t = 0; t < 4; ++t) pb(p)[ri[t] * SI + cj] = qk[t];
       __syncthreads();
-      const dbl4 acc = mma<DS, SW, SI>(pa(0), pb(p), row0, col0, q, c);
+      const dbl4 acc = tile_mma<DS, SW, SI>(pa(0), pb(p), T, di);
       const double rk = 1.0 / k;
 #pragma unroll
       for (int t = 0; t < 4; ++t) qk[t] = real[t] ? dl[t] + rk * acc[t] : 0.0;
@@ -159,7 +134,7 @@ __device__ __forceinline__ void pst_blk_body(const SmallPst& ps, int di, const d
         pb(p)[ri[t] * SI + cj] = qk[t];
       }
       __syncthreads();
-      const dbl4 acc = mma<DS, SW, SI>(pr(p), pb(p), row0, col0, q, c);
+      const dbl4 acc = tile_mma<DS, SW, SI>(pr(p), pb(p), T, di);
 #pragma unroll
       for (int t = 0; t < 4; ++t) qk[t] = real[t] ? acc[t] : 0.0;
       p ^= 1;
@@ -167,42 +142,13 @@ __device__ __forceinline__ void pst_blk_body(const SmallPst& ps, int di, const d
 #pragma unroll
     for (int t = 0; t < 4; ++t) f[t] = qk[t];
   } else {
-    // F = ((1 + eps) I - W2)^-1: in-place Gauss-Jordan, no pivoting (the slot's, small.hip)
+    // F = ((1 + eps) I - W2)^-1: the slot's in-place Gauss-Jordan, no pivots kept
     const double sd = 1.0 + ps.eps_inv;
     double a[4];
 #pragma unroll
-    for (int t = 0; t < 4; ++t) {
+    for (int t = 0; t < 4; ++t)
       a[t] = real[t] ? sw_entry(ri[t] == cj, sd, wv[t], false) : (ri[t] == cj ? 1.0 : 0.0);
-      if (ri[t] == 0) rowb(0)[cj] = a[t];
-      if (cj == 0) colb(0)[ri[t]] = a[t];
-    }
-    __syncthreads();
-    for (int k = 0; k < di; ++k) {
-      const int b = k & 1;
-      const double pv = rowb(b)[k];
-      const double pinv = 1.0 / pv;
-      const double rk = rowb(b)[cj] * pinv;
-#pragma unroll
-      for (int t = 0; t < 4; ++t) {
-        if (!real[t]) continue;
-        const int i = ri[t];
-        const double cki = colb(b)[i];
-        if (i == k)
-          a[t] = (cj == k) ? pinv : a[t] * pinv;
-        else if (cj == k)
-          a[t] = -(a[t] * pinv);
-        else
-          a[t] = a[t] - cki * rk;
-      }
-      if (k + 1 < di) {
-#pragma unroll
-        for (int t = 0; t < 4; ++t) {
-          if (ri[t] == k + 1) rowb(b ^ 1)[cj] = a[t];
-          if (cj == k + 1) colb(b ^ 1)[ri[t]] = a[t];
-        }
-      }
-      __syncthreads();
-    }
+    wg_gauss_jordan<DS>(a, T, di, B.rowb, B.colb);
 #pragma unroll
     for (int t = 0; t < 4; ++t) f[t] = real[t] ? a[t] : 0.0;
   }
@@ -216,7 +162,7 @@ __device__ __forceinline__ void pst_blk_body(const SmallPst& ps, int di, const d
       pb(p)[ri[t] * SI + cj] = f[t];
     }
     __syncthreads();
-    const dbl4 acc = mma<DS, SW, SI>(pr(p), pb(p), row0, col0, q, c);
+    const dbl4 acc = tile_mma<DS, SW, SI>(pr(p), pb(p), T, di);
 #pragma unroll
     for (int t = 0; t < 4; ++t) h[t] = real[t] ? acc[t] : 0.0;
     p ^= 1;
@@ -236,8 +182,8 @@ __device__ __forceinline__ void pst_blk_body(const SmallPst& ps, int di, const d
         pm = fmax(pm, h[t]);
       }
     }
-    ps_ = wsum(ps_);
-    pm = wmax(pm);
+    ps_ = wave_sum(ps_);
+    pm = wave_max(pm);
     if (lane == 0) {
       L.red[0][w] = ps_;
       L.red[1][w] = pm;
@@ -261,8 +207,8 @@ __device__ __forceinline__ void pst_blk_body(const SmallPst& ps, int di, const d
         se += nn[t] * exp(h[t] - mx);
         ties += h[t] == mx ? nn[t] : 0.0;
       }
-    se = wsum(se);
-    ties = wsum(ties);
+    se = wave_sum(se);
+    ties = wave_sum(ties);
     if (lane == 0) {
       L.red[2][w] = se;
       L.red[3][w] = ties;
@@ -300,7 +246,7 @@ __device__ __forceinline__ void pst_blk_body(const SmallPst& ps, int di, const d
       pb(p)[ri[t] * SI + cj] = sm[t];
     }
     __syncthreads();
-    const dbl4 acc = mma<DS, SW, SI>(pr(p), pb(p), row0, col0, q, c);
+    const dbl4 acc = tile_mma<DS, SW, SI>(pr(p), pb(p), T, di);
 #pragma unroll
     for (int t = 0; t < 4; ++t) gf[t] = real[t] ? acc[t] : 0.0;
     p ^= 1;
@@ -323,9 +269,9 @@ __device__ __forceinline__ void pst_blk_body(const SmallPst& ps, int di, const d
         L.lb[p][ri[t] * SW + cj] = lk[t];
       }
       __syncthreads();
-      const dbl4 t1 = mma<DS, SW, SW>(pa(0), L.lb[p], row0, col0, q, c);
-      const dbl4 t2 = mma<DS, SW, SI>(pa(1), pb(p), row0, col0, q, c);
-      const dbl4 tq = mma<DS, SW, SI>(pa(0), pb(p), row0, col0, q, c);
+      const dbl4 t1 = tile_mma<DS, SW, SW>(pa(0), L.lb[p], T, di);
+      const dbl4 t2 = tile_mma<DS, SW, SI>(pa(1), pb(p), T, di);
+      const dbl4 tq = tile_mma<DS, SW, SI>(pa(0), pb(p), T, di);
       const double rk = 1.0 / k;
 #pragma unroll
       for (int t = 0; t < 4; ++t) {
@@ -344,9 +290,9 @@ __device__ __forceinline__ void pst_blk_body(const SmallPst& ps, int di, const d
         L.lb[p][ri[t] * SW + cj] = lk[t];
       }
       __syncthreads();
-      const dbl4 t1 = mma<DS, SW, SW>(pa(p), L.lb[p], row0, col0, q, c);
-      const dbl4 t2 = mma<DS, SW, SI>(pr(p), pb(p), row0, col0, q, c);
-      const dbl4 tq = mma<DS, SW, SI>(pa(p), pb(p), row0, col0, q, c);
+      const dbl4 t1 = tile_mma<DS, SW, SW>(pa(p), L.lb[p], T, di);
+      const dbl4 t2 = tile_mma<DS, SW, SI>(pr(p), pb(p), T, di);
+      const dbl4 tq = tile_mma<DS, SW, SI>(pa(p), pb(p), T, di);
 #pragma unroll
       for (int t = 0; t < 4; ++t) {
         lk[t] = real[t] ? t1[t] + t2[t] : 0.0;
@@ -359,14 +305,14 @@ __device__ __forceinline__ void pst_blk_body(const SmallPst& ps, int di, const d
 #pragma unroll
     for (int t = 0; t < 4; ++t) pb(p)[cj * SI + ri[t]] = gf[t];
     __syncthreads();
-    const dbl4 t1 = mma<DS, SW, SI>(pr(pf), pb(p), row0, col0, q, c);
+    const dbl4 t1 = tile_mma<DS, SW, SI>(pr(pf), pb(p), T, di);
 #pragma unroll
     for (int t = 0; t < 4; ++t) {
       pr(p)[ri[t] * SW + cj] = real[t] ? t1[t] : 0.0;
       pb(p ^ 1)[ri[t] * SI + cj] = f[t];
     }
     __syncthreads();
-    const dbl4 t2 = mma<DS, SW, SI>(pr(p), pb(p ^ 1), row0, col0, q, c);
+    const dbl4 t2 = tile_mma<DS, SW, SI>(pr(p), pb(p ^ 1), T, di);
 #pragma unroll
     for (int t = 0; t < 4; ++t) lk[t] = real[t] ? t2[t] : 0.0;
   }

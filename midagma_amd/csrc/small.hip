@@ -20,31 +20,28 @@
 //   control (checkpoint objective + tolerance, line search, lr halving: the decisions of
 //   step.hip's control_kernel, by thread 0 on a State kept in LDS, broadcast through LDS) ->
 //   G_obj, Adam, W -= lr g, W *= mask (or the line-search revert / halving).
-// Element ownership follows the f64 16x16x4 MFMA accumulator map, so every product's output
-// lands in the registers of the lane that owns the element: wave w owns the 16 x 16 tile
+// Element ownership follows the f64 16x16x4 MFMA accumulator map (wgtile.h), so every product's
+// output lands in the registers of the lane that owns the element: wave w owns the 16 x 16 tile
 // (w / (DS/16), w % (DS/16)); lane l owns column 16 tc + (l & 15), rows 16 tr + (l >> 4) + 4 t
-// for t = 0..3.  DS = 16, 32, 64 -> 1, 4, 16 waves.
+// for t = 0..3.  DS = 16, 32, 64 -> 1, 4, 16 waves.  The tile product, the wave reductions and the
+// pivot column's placement are wgtile.h's, shared with the bodies a slot runs (pst_blk.h,
+// logit_blk.h) and with the evaluation kernels (small_eval.hip).  The slot kernel keeps its own
+// set-up of the map and its own Gauss-Jordan, written over tiles-per-wave loops of one iteration:
+// without them the DS = 64 kernel's register allocation reloads about 25 more spilled words in
+// every slot (d = 48, 64: -4 % steps/s), with the same registers and scratch bytes.
 // Arithmetic per element is step.hip's, in the same order (built with -ffp-contract=off).
 //
-// The logistic loss (LOGIT; a batch, float64, no regularizer) has no covariance to fold n into:
-// its score phase streams the problem's X (n_pad x DS doubles, zero padding) through the workgroup
-// in blocks of kLogitRows rows, in ascending order.  Per block, R = X_blk W on the matrix cores
-// against the W image in LDS, S = expit(R) staged through LDS (the accumulator layout is not the
-// B-operand layout), Z += (mu / n X_blk)^T S into the owner's accumulator (X^T scaled first, as
-// the reference scales it), so Z lands where rhs lands for l2.  A block is loaded once: the wave takes its X_blk^T fragments for the second product into
-// registers while the block is current, which lets two X buffers and two S buffers run at one
-// barrier a block.  The S buffers alias the product form's operand images (the inverse and the
-// score phase never overlap), the X buffers take the place of the (-mu) cov image.  On checkpoint
-// slots the lanes also sum logaddexp(0, R) - X o R over the valid n x d entries.  Every sum has a
-// fixed order (blocks ascending, lanes, waves), so a problem's result does not depend on the batch.
+// The logistic loss (LOGIT; a batch, float64, no regularizer) replaces the score product by
+// logit_blk.h's row-block phase over the problem's X; its S blocks alias the product form's operand
+// images, its X blocks take the place of the (-mu) cov image.
 #include <type_traits>
 
 #include "launch.h"
-#include "logit_math.h"
+#include "logit_blk.h"
 #include "np_sum.h"
-#include "mfma64.h"
-#include "tcc_blk.h"
 #include "pst_blk.h"
+#include "tcc_blk.h"
+#include "wgtile.h"
 
 namespace midagma {
 
@@ -84,148 +81,6 @@ __device__ unsigned long long g_small_stamps[16];  // [0..11] phase sums, [12] s
 namespace {
 
 __device__ __forceinline__ double sgn(double w) { return w > 0.0 ? 1.0 : (w < 0.0 ? -1.0 : w); }
-
-__device__ __forceinline__ double wave_sum(double x) {
-  for (int off = 32; off > 0; off >>= 1) x += __shfl_xor(x, off);
-  return x;
-}
-__device__ __forceinline__ double wave_max(double x) {
-  for (int off = 32; off > 0; off >>= 1) x = fmax(x, __shfl_xor(x, off));
-  return x;
-}
-__device__ __forceinline__ double wave_min(double x) {
-  for (int off = 32; off > 0; off >>= 1) x = fmin(x, __shfl_xor(x, off));
-  return x;
-}
-
-// colb position of row i: the 4 rows a lane owns (16 tr + q + 4 t) are 4 consecutive slots
-__device__ __forceinline__ int cpos(int i) { return (i & ~15) + 4 * (i & 3) + ((i & 15) >> 2); }
-
-// acc += A[row0 .. row0+15][0 .. kd) * B[0 .. kd)[col0 .. col0+15] on the f64 16x16x4 MFMA;
-// A from an [m][k] image (stride SA_), B from a [k][n] image (stride SB_).  Terms with
-// k >= d are exact zeros in every product of this file (zero off-diagonal padding).
-template <int DS, int SA_, int SB_>
-__device__ __forceinline__ dbl4 tile_mma(const double* __restrict__ A, const double* __restrict__ B, int row0,
-                                         int col0, int q, int c, int kd, dbl4 acc) {
-  if (DS >= 64) {  // (a full unroll keeps 32 operands in flight: the 1024-thread kernel's registers spill)
-#pragma unroll 4
-    for (int kk = 0; 4 * kk < kd; ++kk)
-      acc = __builtin_amdgcn_mfma_f64_16x16x4f64(A[(row0 + c) * SA_ + 4 * kk + q], B[(4 * kk + q) * SB_ + col0 + c],
-                                                 acc, 0, 0, 0);
-    return acc;
-  }
-  // DS <= 32: all DS / 4 k-steps, unguarded (the k >= d terms are the exact zeros above): the
-  // operand reads of a branch-free unrolled chain issue together, where a guard per k-step
-  // serialised read, wait and MFMA (d = 20: 5 guarded steps cost more than 8 pipelined ones)
-  (void)kd;
-#pragma unroll
-  for (int kk = 0; kk < DS / 4; ++kk)
-    acc = __builtin_amdgcn_mfma_f64_16x16x4f64(A[(row0 + c) * SA_ + 4 * kk + q], B[(4 * kk + q) * SB_ + col0 + c],
-                                               acc, 0, 0, 0);
-  return acc;
-}
-
-// Rows of one X block of the logistic score phase.  DS <= 32: DS rows, so the block's R has one
-// 16 x 16 tile per wave; DS = 64: 32 rows (8 of the 16 waves form R), which is what fits beside
-// the inverse's images in the CU's 160 KB of LDS.
-template <int DS>
-constexpr int kLogitRows = DS >= 64 ? 32 : DS;
-
-// The logistic score phase of one workgroup: z += (xscale X)^T expit(X W) over the nb = n_pad / RB
-// row blocks of X, for the 16 x 16 tile (tr, tc) this wave owns.  X^T is scaled before the product,
-// entry by entry, as the reference's `mu / n * X.T @ sigmoid(X @ W)` scales it (linear.py:246), and
-// an element's terms are added in ascending row order: with binary X an exactly cancelling entry of
-// G_score keeps the rounding the reference's own sum leaves there, whose sign picks the L1 branch.
-// With want_loss also this lane's share of sum(logaddexp(0, R) - X o R) over the rows < n and
-// columns < di.  W is read as the B operand from
-// the I - W image (off-diagonal entries are -W exactly) and the diagonal words.  Xbuf: 2 x RB x
-// (DS + 2) doubles, S0 / S1: RB x SI doubles each.  Stage s (one barrier each): the second product of
-// block s - 1 from the wave's registers and S[(s - 1) & 1]; the wave's X^T fragments of block s;
-// the first product of block s, its sigmoid into S[s & 1]; block s + 1 from registers into
-// Xbuf[(s + 1) & 1] and block s + 2 from global memory into registers.  Block 0 is stored ahead of
-// the first barrier, which also ends every wave's earlier reads of whatever S0 / S1 alias.
-template <int DS, int NW>
-__device__ __forceinline__ void logit_score_phase(const double* __restrict__ X, int64_t n, int64_t n_pad, int di,
-                                                  double* __restrict__ Xbuf, double* __restrict__ S0,
-                                                  double* __restrict__ S1, const double* __restrict__ IWimg,
-                                                  const double* __restrict__ wdiag, bool want_loss, int tr, int tc,
-                                                  double xscale, dbl4& z, double& loss) {
-  constexpr int RB = kLogitRows<DS>, NT = 64 * NW, TPR = DS / 16, SX = DS + 2;
-  constexpr int SI = ((DS + 15) / 32) * 32 + 16;
-  constexpr int XE = RB * DS / NT;  // elements of a block per thread
-  constexpr bool HOIST = DS <= 32;  // the W fragments stay in registers over the blocks
-  static_assert(XE * NT == RB * DS && RB % 16 == 0 && (RB / 16) * TPR <= NW, "block shape");
-  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, q = lane >> 4, c = lane & 15;
-  const int rt = w / TPR, ct = w % TPR;  // this wave's tile of the block's R
-  const bool has_r = rt < RB / 16;
-  const int64_t nb = n_pad / RB;
-  double ga[XE], gb[XE], xt[RB / 4];
-  [[maybe_unused]] double wb[HOIST ? DS / 4 : 1];
-  auto w_at = [&](int k, int nn) { return k == nn ? wdiag[k] : -IWimg[k * SI + nn]; };
-  if constexpr (HOIST) {
-#pragma unroll
-    for (int kk = 0; kk < DS / 4; ++kk) wb[kk] = w_at(4 * kk + q, 16 * ct + c);
-  }
-  // a block travels global memory -> registers -> LDS, two blocks ahead of its products: one stage
-  // is shorter than a global load's latency
-  auto load_blk = [&](double(&gr)[XE], int64_t blk) __attribute__((always_inline)) {
-    const double* __restrict__ const Xn = X + blk * (RB * DS);
-#pragma unroll
-    for (int i = 0; i < XE; ++i) gr[i] = Xn[tid + i * NT];
-  };
-  auto store_blk = [&](const double(&gr)[XE], int64_t blk) __attribute__((always_inline)) {
-    double* __restrict__ const Xw = Xbuf + (blk & 1) * (RB * SX);
-#pragma unroll
-    for (int i = 0; i < XE; ++i) {
-      const int e = tid + i * NT;
-      Xw[(e / DS) * SX + e % DS] = gr[i];
-    }
-  };
-  load_blk(ga, 0);
-  if (nb > 1) load_blk(gb, 1);
-  store_blk(ga, 0);
-  z = dbl4{0.0, 0.0, 0.0, 0.0};
-  loss = 0.0;
-  __syncthreads();
-  // stage s; gw holds block s + 1, gl (block s, stored a stage ago) takes block s + 2
-  auto stage = [&](int64_t s, const double(&gw)[XE], double(&gl)[XE]) __attribute__((always_inline)) {
-    const double* __restrict__ const Xc = Xbuf + (s & 1) * (RB * SX);
-    if (s + 2 < nb) load_blk(gl, s + 2);
-    if (s >= 1) {
-      const double* __restrict__ const Sp = ((s - 1) & 1) ? S1 : S0;
-#pragma unroll
-      for (int kk = 0; kk < RB / 4; ++kk)
-        z = __builtin_amdgcn_mfma_f64_16x16x4f64(xt[kk], Sp[(4 * kk + q) * SI + 16 * tc + c], z, 0, 0, 0);
-    }
-    if (s == nb) return;
-#pragma unroll
-    for (int kk = 0; kk < RB / 4; ++kk) xt[kk] = xscale * Xc[(4 * kk + q) * SX + 16 * tr + c];
-    if (has_r) {
-      dbl4 r = dbl4{0.0, 0.0, 0.0, 0.0};
-#pragma unroll
-      for (int kk = 0; kk < DS / 4; ++kk)
-        if (DS < 64 || 4 * kk < di) {  // (X's columns and W's rows >= d are zero)
-          const double wop = HOIST ? wb[HOIST ? kk : 0] : w_at(4 * kk + q, 16 * ct + c);
-          r = __builtin_amdgcn_mfma_f64_16x16x4f64(Xc[(16 * rt + c) * SX + 4 * kk + q], wop, r, 0, 0, 0);
-        }
-      double* __restrict__ const Sc = (s & 1) ? S1 : S0;
-      const int col = 16 * ct + c;
-#pragma unroll
-      for (int t = 0; t < 4; ++t) {
-        const int row = 16 * rt + q + 4 * t;
-        Sc[row * SI + col] = expit(r[t]);
-        // padded rows and columns have R = 0, logaddexp = log 2: they stay out of the loss
-        if (want_loss && s * RB + row < n && col < di) loss += logaddexp0(r[t]) - Xc[row * SX + col] * r[t];
-      }
-    }
-    if (s + 1 < nb) store_blk(gw, s + 1);
-    __syncthreads();
-  };
-  for (int64_t s = 0; s <= nb; s += 2) {
-    stage(s, gb, ga);
-    if (s + 1 <= nb) stage(s + 1, ga, gb);
-  }
-}
 
 struct SmallCtl {
   int32_t act, norms, run, pad_;
@@ -402,7 +257,7 @@ __global__ __launch_bounds__(64 * NW) void small_minimize_kernel(
   static_assert(TPW * NW == TPR * TPR, "whole tiles per wave");
   // PST: pst_blk.h's body on this workgroup's ownership (one tile per wave), float64, never with TCC
   static_assert(!PST || (TCC == 0 && !W32 && DS <= 32 && TPW == 1), "PST in the small loop: d <= 32, float64");
-  // LOGIT: the logistic loss (logit_score_phase above), float64 without a regularizer; `covs` is the
+  // LOGIT: the logistic loss (logit_blk.h's logit_score_phase), float64 without a regularizer; `covs` is the
   // plain cov, this lane's entries in registers
   static_assert(!LOGIT || (TCC == 0 && !W32 && !PST && TPW == 1), "logistic in the small loop: float64, no trek");
   constexpr int SW = DS + 2;                         // W, cov images: 16 rows x 4 cols per read
@@ -1113,107 +968,6 @@ __global__ __launch_bounds__(64 * NW) void small_minimize_kernel(
   }
 }
 
-// The PST penalty of B given matrices, no Adam step: workgroup b runs pst_blk.h's body on problem
-// b's D x D slab of W; value[b], and with grad (D x D slabs) d value / d W on d x d.
-template <int DS, int NW>
-__global__ __launch_bounds__(64 * NW) void small_pst_eval_kernel(const double* __restrict__ W_, int64_t d, int64_t D,
-                                                                  SmallPst ps, double* __restrict__ value,
-                                                                  double* __restrict__ grad_) {
-  constexpr int NT = 64 * NW, TPR = DS / 16, SW = DS + 2, SI = ((DS + 15) / 32) * 32 + 16;
-  __shared__ double Wimg[DS * SW];
-  __shared__ double PAbuf[2 * DS * SW], PRbuf[2 * DS * SW], PBbuf[2 * DS * SI];
-  __shared__ double rowb[2][DS], colb[2][DS];
-  __shared__ pstb::PstLds<DS, NW> PL;
-  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-  const int q = lane >> 4, c = lane & 15, di = (int)d;
-  const double* __restrict__ const W = W_ + (int64_t)blockIdx.x * D * D;
-  const int col = 16 * (w % TPR) + c;
-  double wv[4], g[4];
-#pragma unroll
-  for (int t = 0; t < 4; ++t) {
-    const int row = 16 * (w / TPR) + q + 4 * t;
-    wv[t] = (row < di && col < di) ? W[(int64_t)row * D + col] : 0.0;
-    Wimg[row * SW + col] = wv[t];
-  }
-  for (int e = tid; e < DS * DS; e += NT) {
-    const int r = e / DS, k = e % DS;
-    PL.nimg[e] = (r < di && k < di) ? ps.N[r * di + k] : 0.0;
-  }
-  __syncthreads();
-  const pstb::PstBufs pbufs{PAbuf, PRbuf, PBbuf, rowb[0], colb[0]};
-  pstb::pst_blk_body<DS, NW>(ps, di, wv, Wimg, pbufs, PL, grad_ != nullptr, g);
-  __syncthreads();
-  if (tid == 0) value[blockIdx.x] = PL.val;
-  if (grad_) {
-    double* __restrict__ const G = grad_ + (int64_t)blockIdx.x * D * D;
-#pragma unroll
-    for (int t = 0; t < 4; ++t) {
-      const int row = 16 * (w / TPR) + q + 4 * t;
-      if (row < di && col < di) G[(int64_t)row * D + col] = g[t];
-    }
-  }
-}
-
-// The reference's logistic _score (linear.py:89-92) of B given matrices, no Adam step: workgroup b
-// runs logit_score_phase on problem b's D x D slab of W and its X; loss[b], and with G (D x D slabs)
-// X^T expit(X W) / n - cov on d x d.
-template <int DS, int NW>
-__global__ __launch_bounds__(64 * NW) void small_logit_eval_kernel(const double* __restrict__ W_,
-                                                                    const double* __restrict__ cov_, int64_t d,
-                                                                    int64_t D, SmallLogit lg,
-                                                                    double* __restrict__ loss_out,
-                                                                    double* __restrict__ G_) {
-  constexpr int NT = 64 * NW, TPR = DS / 16, SW = DS + 2, SI = ((DS + 15) / 32) * 32 + 16;
-  constexpr int RB = kLogitRows<DS>;
-  __shared__ double IWimg[DS * SI];
-  __shared__ double wdiag[DS];
-  __shared__ double Xbuf[2 * RB * SW];
-  __shared__ double Sbuf[2][RB * SI];
-  __shared__ double red[NW];
-  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-  const int q = lane >> 4, c = lane & 15, di = (int)d;
-  const int64_t slab = (int64_t)blockIdx.x * D * D;
-  const double* __restrict__ const W = W_ + slab;
-  const int tr = w / TPR, tc = w % TPR, col = 16 * tc + c;
-  for (int e = tid; e < DS * SI; e += NT) IWimg[e] = 0.0;
-  for (int e = tid; e < DS; e += NT) wdiag[e] = 0.0;
-  __syncthreads();
-#pragma unroll
-  for (int t = 0; t < 4; ++t) {
-    const int row = 16 * tr + q + 4 * t;
-    if (row < di && col < di) {
-      const double wv = W[(int64_t)row * D + col];
-      if (row == col) wdiag[row] = wv;
-      IWimg[row * SI + col] = one_minus(row == col, wv, false);
-    }
-  }
-  __syncthreads();
-  dbl4 z;
-  double loss;
-  const double inv_n = 1.0 / (double)lg.n;
-  logit_score_phase<DS, NW>(lg.X + (int64_t)blockIdx.x * lg.stride, lg.n, lg.n_pad, di, Xbuf, Sbuf[0], Sbuf[1],
-                            IWimg, wdiag, true, tr, tc, inv_n, z, loss);
-  loss = wave_sum(loss);
-  if (lane == 0) red[w] = loss;
-  __syncthreads();
-  if (tid == 0) {
-    double x = 0.0;
-#pragma unroll 1
-    for (int y = 0; y < NW; ++y) x += red[y];
-    loss_out[blockIdx.x] = x * inv_n;
-  }
-  if (G_) {
-#pragma unroll
-    for (int t = 0; t < 4; ++t) {
-      const int row = 16 * tr + q + 4 * t;
-      if (row < di && col < di) {
-        const int64_t idx = slab + (int64_t)row * D + col;
-        G_[idx] = z[t] - cov_[idx];  // (1 / n X^T) @ expit(X W) - cov, linear.py:92
-      }
-    }
-  }
-}
-
 }  // namespace
 
 #ifdef MIDAGMA_KSTAMPS
@@ -1241,21 +995,26 @@ int small_logit_rows(int64_t d) {
 }
 
 namespace {
-bool logit_ok(const SmallLogit& lg, int rb) {
-  return lg.X && lg.n >= 1 && rb > 0 && lg.n_pad >= lg.n && lg.n_pad % rb == 0 && lg.stride >= 0;
+// one launch of the slot kernel: n_problems workgroups of NW waves (one wave per 16 x 16 tile)
+template <int DS, int NW, int TCC, bool W32 = false, bool PST = false, bool LOGIT = false>
+void launch_slots(const SmallArrays& a, const SmallRun& r, const SmallTcc& tc, const SmallPst& ps,
+                  const SmallLogit& lg, hipStream_t stream) {
+  hipLaunchKernelGGL((small_minimize_kernel<DS, NW, TCC, W32, PST, LOGIT>), dim3((unsigned)r.n_problems),
+                     dim3(64 * NW), 0, stream, a.pr, a.st, a.W, a.m, a.v, a.cov, a.minc, a.mexc, a.bc_table, a.ckpt,
+                     a.ckpt_cap, a.carry, a.pstore, r.n_slots, tc, r.index, ps, lg);
 }
 }  // namespace
 
-void launch_small_minimize(const Params* pr, State* st, double* W, double* m, double* v, const double* covs,
-                           const double* minc, const double* mexc, const double* bc_table, CkptRec* ckpt,
-                           int64_t ckpt_cap, double* carry, double* pstore, int64_t d, int64_t n_slots,
-                           hipStream_t stream, const SmallTcc* tcc, bool w32, const int32_t* index,
-                           int64_t n_problems, const SmallPst* pst, const SmallLogit* logit) {
-  const int ds = small_block(d);
+void launch_small_minimize(const SmallArrays& a, const SmallRun& r, hipStream_t stream) {
+  const SmallTcc* const tcc = r.tcc;
+  const SmallPst* const pst = r.pst;
+  const SmallLogit* const logit = r.logit;
+  const bool w32 = r.w32;
+  const int ds = small_block(r.d);
   if (ds == 0) throw std::invalid_argument("small_minimize: d > 64");
-  if (n_problems < 1 || (!index && n_problems != 1))
+  if (r.n_problems < 1 || (!r.index && r.n_problems != 1))
     throw std::invalid_argument("small_minimize: a batch needs its index list");
-  if (index && (tcc || w32)) throw std::invalid_argument("small_minimize: a batch is float64 without TCC");
+  if (r.index && (tcc || w32)) throw std::invalid_argument("small_minimize: a batch is float64 without TCC");
   if (tcc && ds > 32) throw std::invalid_argument("small_minimize: the TCC regularizer needs d <= 32");
   if (tcc && w32) throw std::invalid_argument("small_minimize: float32 W with TCC runs on the graph path");
   if (pst && (tcc || w32 || ds > 32 || !pst->N || !(pst->m > 0.0) || (pst->mode != 1 && pst->mode != 2) ||
@@ -1263,89 +1022,46 @@ void launch_small_minimize(const Params* pr, State* st, double* W, double* m, do
     throw std::invalid_argument("small_minimize: PST needs d <= 32, a float64 W, no TCC, seq exp or inv and pairs");
   // d <= 20 on DS = 32: the one-wave 5 x 5 body (d=20: 10.4k -> 11.7k steps/s; experiment knob
   // MIDAGMA_EXP_TCC_BS5=0: NB = 16, 4 x 4)
-  const bool bs5 = tcc && ds == 32 && d <= 20 && knob("MIDAGMA_EXP_TCC_BS5", 1) != 0;
+  const bool bs5 = tcc && ds == 32 && r.d <= 20 && knob("MIDAGMA_EXP_TCC_BS5", 1) != 0;
   const SmallTcc tc = tcc ? *tcc : SmallTcc{};
   const SmallPst ps = pst ? *pst : SmallPst{};
-  if (logit && (tcc || pst || w32 || !index || !logit_ok(*logit, small_logit_rows(d))))
+  if (logit && (tcc || pst || w32 || !r.index || !logit_ok(*logit, small_logit_rows(r.d))))
     throw std::invalid_argument(
         "small_minimize: the logistic loss runs in a batch, float64, without a trek regularizer, on a padded X");
   const SmallLogit lg = logit ? *logit : SmallLogit{};
-#define MIDAGMA_SMALL_(DS_, NW_, TCC_, W32_, PST_)                                                                \
-  hipLaunchKernelGGL((small_minimize_kernel<DS_, NW_, TCC_, W32_, PST_>), dim3((unsigned)n_problems),             \
-                     dim3(64 * NW_), 0, stream, pr, st, W, m, v, covs, minc, mexc, bc_table, ckpt, ckpt_cap, carry, \
-                     pstore, n_slots, tc, index, ps, lg)
-#define MIDAGMA_SMALL(DS_, NW_, TCC_, W32_) MIDAGMA_SMALL_(DS_, NW_, TCC_, W32_, false)
-#define MIDAGMA_SMALL_LOGIT(DS_, NW_)                                                                              \
-  hipLaunchKernelGGL((small_minimize_kernel<DS_, NW_, 0, false, false, true>), dim3((unsigned)n_problems),         \
-                     dim3(64 * NW_), 0, stream, pr, st, W, m, v, covs, minc, mexc, bc_table, ckpt, ckpt_cap, carry, \
-                     pstore, n_slots, tc, index, ps, lg)
-  // one wave per 16 x 16 tile
   if (logit) {
     if (ds == 16)
-      MIDAGMA_SMALL_LOGIT(16, 1);
+      launch_slots<16, 1, 0, false, false, true>(a, r, tc, ps, lg, stream);
     else if (ds == 32)
-      MIDAGMA_SMALL_LOGIT(32, 4);
+      launch_slots<32, 4, 0, false, false, true>(a, r, tc, ps, lg, stream);
     else
-      MIDAGMA_SMALL_LOGIT(64, 16);
+      launch_slots<64, 16, 0, false, false, true>(a, r, tc, ps, lg, stream);
   } else if (pst) {
     if (ds == 16)
-      MIDAGMA_SMALL_(16, 1, 0, false, true);
+      launch_slots<16, 1, 0, false, true>(a, r, tc, ps, lg, stream);
     else
-      MIDAGMA_SMALL_(32, 4, 0, false, true);
+      launch_slots<32, 4, 0, false, true>(a, r, tc, ps, lg, stream);
   } else if (ds == 16) {
     if (tcc)
-      MIDAGMA_SMALL(16, 1, 4, false);
+      launch_slots<16, 1, 4>(a, r, tc, ps, lg, stream);
     else if (w32)
-      MIDAGMA_SMALL(16, 1, 0, true);
+      launch_slots<16, 1, 0, true>(a, r, tc, ps, lg, stream);
     else
-      MIDAGMA_SMALL(16, 1, 0, false);
+      launch_slots<16, 1, 0>(a, r, tc, ps, lg, stream);
   } else if (ds == 32) {
     if (bs5)
-      MIDAGMA_SMALL(32, 4, 5, false);
+      launch_slots<32, 4, 5>(a, r, tc, ps, lg, stream);
     else if (tcc)
-      MIDAGMA_SMALL(32, 4, 4, false);
+      launch_slots<32, 4, 4>(a, r, tc, ps, lg, stream);
     else if (w32)
-      MIDAGMA_SMALL(32, 4, 0, true);
+      launch_slots<32, 4, 0, true>(a, r, tc, ps, lg, stream);
     else
-      MIDAGMA_SMALL(32, 4, 0, false);
+      launch_slots<32, 4, 0>(a, r, tc, ps, lg, stream);
   } else if (w32) {
     throw std::invalid_argument("small_minimize: a float32 W with 32 < d <= 64 runs on the graph path");
   } else {
-    MIDAGMA_SMALL(64, 16, 0, false);
+    launch_slots<64, 16, 0>(a, r, tc, ps, lg, stream);
   }
-#undef MIDAGMA_SMALL_LOGIT
-#undef MIDAGMA_SMALL
-#undef MIDAGMA_SMALL_
-  HIP_TRY(hipGetLastError());
-}
-
-void launch_small_pst_eval(const double* W, int64_t d, int64_t D, int64_t n_problems, const SmallPst& ps,
-                           double* value, double* grad, hipStream_t stream) {
-  const int ds = small_block(d);
-  if (ds == 0 || ds > 32 || n_problems < 1 || !ps.N || !(ps.m > 0.0) || (ps.seq != TREK_EXP && ps.seq != TREK_INV) ||
-      ps.agg < TREK_MEAN || ps.agg > TREK_LSE)
-    throw std::invalid_argument("small_pst_eval: PST needs d <= 32, seq exp or inv and pairs");
-  if (ds == 16)
-    hipLaunchKernelGGL((small_pst_eval_kernel<16, 1>), dim3((unsigned)n_problems), dim3(64), 0, stream, W, d, D, ps,
-                       value, grad);
-  else
-    hipLaunchKernelGGL((small_pst_eval_kernel<32, 4>), dim3((unsigned)n_problems), dim3(256), 0, stream, W, d, D, ps,
-                       value, grad);
-  HIP_TRY(hipGetLastError());
-}
-
-void launch_small_logit_eval(const double* W, const double* cov, int64_t d, int64_t D, int64_t n_problems,
-                             const SmallLogit& lg, double* loss, double* G, hipStream_t stream) {
-  const int ds = small_block(d);
-  if (ds == 0 || n_problems < 1 || !W || !loss || (G && !cov) || !logit_ok(lg, small_logit_rows(d)))
-    throw std::invalid_argument("small_logit_eval: d <= 64 and a padded X");
-  const dim3 grid((unsigned)n_problems);
-  if (ds == 16)
-    hipLaunchKernelGGL((small_logit_eval_kernel<16, 1>), grid, dim3(64), 0, stream, W, cov, d, D, lg, loss, G);
-  else if (ds == 32)
-    hipLaunchKernelGGL((small_logit_eval_kernel<32, 4>), grid, dim3(256), 0, stream, W, cov, d, D, lg, loss, G);
-  else
-    hipLaunchKernelGGL((small_logit_eval_kernel<64, 16>), grid, dim3(1024), 0, stream, W, cov, d, D, lg, loss, G);
   HIP_TRY(hipGetLastError());
 }
 

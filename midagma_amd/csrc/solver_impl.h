@@ -1113,9 +1113,12 @@ struct midagma_solver {
       if (trek_on && trek_tcc)
         tc = SmallTcc{cw.S, ccfg.w, ccfg.eps, (double)ccfg.m, ccfg.weight, ccfg.mode, cw.scal, cw.vprev, cw.uprev,
                       cw.fix};
-      launch_small_minimize(d_params.p, d_state.p, W.p, m.p, v.p, covs.p, has_inc ? minc.p : nullptr,
-                            has_exc ? mexc.p : nullptr, bc_table.p, d_ckpt.p, ckpt_cap, scarry.p, sprev.p, d, B,
-                            stream, trek_on && trek_tcc ? &tc : nullptr, w32);
+      const SmallArrays arr{d_params.p, d_state.p, W.p, m.p, v.p, covs.p, has_inc ? minc.p : nullptr,
+                            has_exc ? mexc.p : nullptr, bc_table.p, d_ckpt.p, ckpt_cap, scarry.p, sprev.p};
+      SmallRun run{d, B};
+      run.w32 = w32;
+      run.tcc = trek_on && trek_tcc ? &tc : nullptr;
+      launch_small_minimize(arr, run, stream);
       launched += B;
       HIP_TRY(hipMemcpyAsync(&h_state.p[1], d_state.p, sizeof(State), hipMemcpyDeviceToHost, stream));
       HIP_TRY(hipStreamSynchronize(stream));

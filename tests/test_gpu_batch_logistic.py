@@ -1,4 +1,4 @@
-"""The logistic loss in the batch of small-d problems (csrc/small.hip's row-block score phase,
+"""The logistic loss in the batch of small-d problems (csrc/logit_blk.h's row-block score phase,
 `HipBatch.set_data` / `minimize_logistic` / `score_logistic`, `DagmaLogisticBatch`): the score
 against numpy, trajectories against `LinearOracle("logistic")` and the single logistic solver,
 bit-for-bit independence of a problem from the rest of the batch and from how X is stored, the
