@@ -195,7 +195,7 @@ hipGraphExec_t group_capture(midagma_group* g, const midagma_solver* caller, int
   // forked member streams from it and joined them back crashed hipStreamEndCapture on the box,
   // ROCm 7.2; the emulated group checks arithmetic, not overlap)
   // (on member 0's capture stream, not its launch stream: midagma_solver::capture)
-  midagma_solver::StreamSwap on_cap(g->m[0], g->m[0]->capture_stream());
+  midagma_solver::StreamSwap on_cap(g->m[0], g->m[0]->graphs.capture_stream());
   midagma_group::OnStream0 on(g);
   HIP_TRY(hipStreamBeginCapture(g->s0(), hipStreamCaptureModeThreadLocal));
   try {
@@ -290,11 +290,7 @@ int midagma_group_create(midagma_group** out, int loss, int64_t d, const int* de
       for (int k = 0; k < ndev; ++k) {
         midagma_solver* s = g->m[(size_t)k];
         HIP_TRY(hipSetDevice(s->device));
-        s->comm = comms[(size_t)k];
-        s->comm_ranks = ndev;
-        s->agree.alloc(8);
-        s->h_agree.alloc(8);
-        s->graphs_valid = false;  // its slot graphs now carry the all-reduce
+        s->attach_comm(comms[(size_t)k], ndev);  // its slot graphs now carry the all-reduce
       }
     }
     return MIDAGMA_OK;
@@ -367,7 +363,7 @@ int midagma_group_minimize(midagma_group* g, double* W, double mu, int64_t max_i
       for (midagma_solver* s : g->m) s->begin(W, mu, max_iter, s_dom, lr, tol, beta1, beta2, lambda1, checkpoint);
       gmark("begun");
       // the combined graphs bake every member's buffers and settings in: captured afresh per call
-      g->m[0]->destroy_graphs();
+      g->m[0]->graphs.destroy();
       g->m[0]->run_loop(max_iter, checkpoint);
       gmark("loop done");
       for (int64_t k = 0; k < N; ++k) g->m[(size_t)k]->finish(Wk[(size_t)k].data(), &rk[(size_t)k]);

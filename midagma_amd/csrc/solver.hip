@@ -54,6 +54,174 @@ int singular_or_nonfinite(midagma_solver* s, int rc, const midagma_result* res, 
 
 }  // namespace
 
+// ---- the handle's evaluations of a given W and its diagnostics (declared in solver_impl.h) ----
+
+// W (d x d, host) zero-padded into scratch
+static void upload_scratch(midagma_solver* s, const double* Wh) {
+  const int64_t DD = s->D * s->D;
+  s->scratch.alloc(DD);
+  HIP_TRY(hipMemsetAsync(s->scratch.p, 0, DD * sizeof(double), s->stream));
+  s->upload_matrix(s->scratch, Wh, s->d);
+}
+
+void midagma_solver::eval_trek(const double* Wh, double* value, double* G) {
+  if (!trek.on) {  // trek_value_grad: (0, zeros) when disabled (notreks.py)
+    *value = 0.0;
+    if (G) std::fill(G, G + d * d, 0.0);
+    return;
+  }
+  upload_scratch(this, Wh);
+  // weight 1: the bare gradient, as trek_value_grad returns it
+  trek.enqueue(scratch.p, d, D, trek.probe.p, stream, /*weight1=*/true);
+  HIP_TRY(hipMemcpyAsync(value, trek.scal(), sizeof(double), hipMemcpyDeviceToHost, stream));
+  if (G) {
+    if (trek.cfg.mode == 2) {
+      HIP_TRY(hipMemcpy2DAsync(G, d * sizeof(double), trek.G.p, D * sizeof(double), d * sizeof(double), d,
+                               hipMemcpyDeviceToHost, stream));
+    } else {
+      std::fill(G, G + d * d, 0.0);
+    }
+  }
+  HIP_TRY(hipStreamSynchronize(stream));
+}
+
+void midagma_solver::eval_h(const double* Wh, double s_dom, double* h, double* G) {
+  const int64_t DD = D * D;
+  upload_scratch(this, Wh);
+  DevBuf<> work;
+  work.alloc(DD);
+  launch_build_at(scratch.p, D, true, work.p, D, d, s_dom, nullptr, nullptr, stream);
+  GJWork gw = gj();
+  gw.Pstore = nullptr;
+  launch_gj_inverse(work.p, D, D, gw, nullptr, stream);
+  std::vector<double> pl(D);
+  HIP_TRY(hipMemcpyAsync(pl.data(), pivlog.p, D * sizeof(double), hipMemcpyDeviceToHost, stream));
+  if (G) {
+    Gtmp.alloc((size_t)d * d);
+    launch_h_grad(scratch.p, work.p, Gtmp.p, d, D, stream);
+    HIP_TRY(hipMemcpyAsync(G, Gtmp.p, (size_t)d * d * sizeof(double), hipMemcpyDeviceToHost, stream));
+  }
+  HIP_TRY(hipStreamSynchronize(stream));
+  double ld = 0.0;
+  for (int64_t i = 0; i < d; ++i) ld += pl[i];
+  *h = -ld + (double)d * std::log(s_dom);
+}
+
+void midagma_solver::trace_l1(const double* Wd, const double* Z, double* sd, double* l1) {
+  launch_trace_l1(Wd, Z, partials.p, d, D, stream);
+  std::vector<double> part(2 * NRED);
+  HIP_TRY(hipMemcpyAsync(part.data(), partials.p, part.size() * sizeof(double), hipMemcpyDeviceToHost, stream));
+  HIP_TRY(hipStreamSynchronize(stream));
+  double a = 0.0, b = 0.0;
+  for (int i = 0; i < NRED; ++i) {
+    a += part[2 * i];
+    b += part[2 * i + 1];
+  }
+  *sd = a;
+  if (l1) *l1 = b;
+}
+
+void midagma_solver::eval_score(const double* Wh, double* loss_out, double* G) {
+  const int64_t DD = D * D;
+  upload_scratch(this, Wh);
+  DevBuf<> rhs;
+  rhs.alloc(DD);
+  // rhs = cov @ (I - W)   (linear.py:85-86)
+  enqueue_cov_gemm(cov_spec(cov.p, false, scratch.p, B_IMINUS), rhs.p, nullptr);
+  double sd = 0;
+  trace_l1(scratch.p, rhs.p, &sd, nullptr);
+  *loss_out = 0.5 * sd;
+  if (G) {
+    Gtmp.alloc((size_t)d * d);
+    launch_scale(rhs.p, -1.0, rhs.p, DD, stream);  // G_loss = -rhs
+    download_matrix(G, rhs.p);
+  }
+  HIP_TRY(hipStreamSynchronize(stream));
+}
+
+void midagma_solver::score_partial(const double* Wh) {
+  upload_scratch(this, Wh);
+  HIP_TRY(hipMemsetAsync(zbuf + D * D, 0, 64 * sizeof(double), stream));
+  // Force loss partials: pass no state (st == nullptr computes them unconditionally).
+  enqueue_data_partial(scratch.p, nullptr);
+  HIP_TRY(hipStreamSynchronize(stream));
+}
+
+void midagma_solver::score_finish(double* loss_out, double* G) {
+  const int64_t DD = D * D;
+  const double n = (double)data.n_global;
+  if (loss == MIDAGMA_LOSS_L2) {
+    // loss = 0.5 tr((I-W)^T cov (I-W)) with cov (I-W) = Z / n ; G = -Z / n
+    double sd = 0;
+    trace_l1(scratch.p, zbuf, &sd, nullptr);
+    *loss_out = 0.5 * (sd / n);
+    if (G) {
+      std::vector<double> z((size_t)d * d);
+      download_matrix(z.data(), zbuf);
+      HIP_TRY(hipStreamSynchronize(stream));
+      for (size_t i = 0; i < z.size(); ++i) G[i] = -(z[i] / n);
+    }
+  } else {
+    double tail = 0;
+    HIP_TRY(hipMemcpyAsync(&tail, zbuf + DD, sizeof(double), hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
+    *loss_out = 1.0 / n * tail;
+    if (G) {
+      std::vector<double> z((size_t)d * d), c((size_t)d * d);
+      download_matrix(z.data(), zbuf);
+      download_matrix(c.data(), cov.p);
+      HIP_TRY(hipStreamSynchronize(stream));
+      for (size_t i = 0; i < z.size(); ++i) G[i] = (1.0 / n) * z[i] - c[i];
+    }
+  }
+}
+
+// [0] build (sI - W o W)^T   [1] GJ inverse   [2] score GEMM(s)   [3] whole slot (graph)
+// data mode: [4] Y = X (I - W) GEMM   [5] Z = X^T Y GEMM (+ slice sum)
+// blocked: [6] build + fast blocked inverse, less [0]   [7] whole fast slot (graph)
+void midagma_solver::profile_parts(int reps, double* ms_out) {
+  Event a, b;
+  a.create();
+  b.create();
+  auto timed = [&](auto&& body) {
+    HIP_TRY(hipEventRecord(a, stream));
+    for (int r = 0; r < reps; ++r) body();
+    HIP_TRY(hipEventRecord(b, stream));
+    HIP_TRY(hipEventSynchronize(b));
+    float ms = 0.f;
+    HIP_TRY(hipEventElapsedTime(&ms, a, b));
+    return (double)ms / reps;
+  };
+  ms_out[0] = timed([&] { launch_build_at(W.p, D, true, Mt.p, D, d, 0.0, d_params.p, d_state.p, stream, IW.p); });
+  ms_out[1] = timed([&] { launch_gj_inverse(Mt.p, D, D, gj(), d_state.p, stream); });
+  if (mode == MIDAGMA_MODE_COV) {
+    ms_out[2] = timed([&] { enqueue_score_cov(zbuf, d_state.p, true); });
+    ms_out[4] = ms_out[5] = 0.0;
+  } else {
+    ms_out[2] = timed([&] { enqueue_data_partial(W.p, d_state.p, IW.p); });
+    ms_out[4] = timed([&] { data.enqueue_xw(W.p, d_state.p, IW.p, stream); });
+    ms_out[5] = timed([&] { data.enqueue_xty(zbuf, d_state.p, stream); });
+  }
+  ms_out[3] = timed([&] { HIP_TRY(hipGraphLaunch(graphs[SlotGraphs::FULL], stream)); });
+  ms_out[6] = ms_out[7] = 0.0;
+  if (blocked()) {
+    // Both need a warm start and no pending checkpoint: one slow slot first.
+    HIP_TRY(hipGraphLaunch(graphs[SlotGraphs::FULL], stream));
+    ms_out[6] = timed([&] { enqueue_build_inverse(/*fast=*/true, 2); }) - ms_out[0];
+    ms_out[7] = timed([&] { HIP_TRY(hipGraphLaunch(graphs[SlotGraphs::FAST], stream)); });
+    State st{};
+    HIP_TRY(hipMemcpy(&st, d_state.p, sizeof(State), hipMemcpyDeviceToHost));
+    if (st.status == ST_NEED_GJ) {  // the fast path did not run: report it, leave a clean state
+      ms_out[6] = ms_out[7] = -1.0;
+      static const int32_t running = ST_RUNNING;
+      HIP_TRY(hipMemcpy(&d_state.p->status, &running, sizeof(int32_t), hipMemcpyHostToDevice));
+      binv.fast_ready = false;
+    }
+  }
+}
+
+// ---- the C ABI: argument checks, one abi_guarded, a call on the handle (abi.h) ----------------
+
 extern "C" {
 
 int midagma_abi_version(void) { return MIDAGMA_ABI_VERSION; }
@@ -72,22 +240,11 @@ int midagma_create(midagma_solver** out, int loss, int mode, int64_t d, int devi
       (loss == MIDAGMA_LOSS_LOGISTIC && mode == MIDAGMA_MODE_COV))
     return abi_fail(nullptr, MIDAGMA_E_ARG, "midagma_create: bad arguments (logistic needs data mode)");
   midagma_solver* s = new midagma_solver();
+  s->knobs = SolverKnobs::read();
   s->loss = loss;
   s->mode = mode;
   s->d = d;
-  // 128-multiples feed the 128x128 GEMM tiles.  Cov mode pads 129 <= d <= 192 to 256 as well: the
-  // blocked inverse then has one 256-wide outer block, and its warm-started product form beats
-  // the flat Gauss-Jordan's 6 block steps on 192 (data mode keeps 192: X's columns are GEMM work)
-  const bool pad256 = mode == MIDAGMA_MODE_COV && knob("MIDAGMA_EXP_COV_PAD256", 1) != 0;
-  s->D = d > 192 || (pad256 && d > 128) ? (d + 127) / 128 * 128 : round_up64(d);
-  // Cov mode, 256 < d <= 640: D to a multiple of 256, so the blocked inverse runs B2 = 256 outer
-  // blocks (2 instead of 3 at D = 384 -> 512, 3 instead of 5 at 640 -> 768: d=300 11.1k -> 11.3k,
-  // d=600 6.4k -> 7.0k steps/s).  Larger D keep B2 = 128 (d=1150 even, d=1400 -3.5%, d=1700
-  // even: the padded GEMM work outweighs the saved outer steps).  Knob MIDAGMA_EXP_COV_PAD_B2:
-  // 0 off, 1 at every d > 256.
-  const int pad_b2 = (int)knob("MIDAGMA_EXP_COV_PAD_B2", -1);
-  if (mode == MIDAGMA_MODE_COV && d > 256 && (pad_b2 == 1 || (pad_b2 < 0 && d <= 640)))
-    s->D = (d + 255) / 256 * 256;
+  s->D = padded_dim(d, mode, s->knobs);
   s->device = device;
   int rc = abi_guarded(s, [&] {
     setup_attributes();
@@ -134,26 +291,7 @@ int midagma_set_cov(midagma_solver* s, const double* cov, int64_t ld) {
 int midagma_set_masks(midagma_solver* s, const double* mask_inc, const double* mask_exc) {
   if (!s) return abi_fail(s, MIDAGMA_E_ARG, "set_masks: null solver");
   return abi_guarded(s, [&] {
-    const size_t DD = (size_t)s->D * s->D;
-    const bool inc = mask_inc != nullptr, exc = mask_exc != nullptr;
-    if (inc) {
-      s->minc.alloc(DD);
-      HIP_TRY(hipMemsetAsync(s->minc.p, 0, DD * sizeof(double), s->stream));
-      s->upload_matrix(s->minc, mask_inc, s->d);
-    }
-    if (exc) {
-      s->mexc.alloc(DD);
-      HIP_TRY(hipMemsetAsync(s->mexc.p, 0, DD * sizeof(double), s->stream));
-      s->upload_matrix(s->mexc, mask_exc, s->d);
-    }
-    HIP_TRY(hipStreamSynchronize(s->stream));
-    const double* pi = inc ? s->minc.p : nullptr;
-    const double* pe = exc ? s->mexc.p : nullptr;
-    if (pi != s->cap_minc || pe != s->cap_mexc) s->graphs_valid = false;  // captured pointers changed
-    s->cap_minc = pi;
-    s->cap_mexc = pe;
-    s->has_inc = inc;
-    s->has_exc = exc;
+    s->set_masks(mask_inc, mask_exc);
     return MIDAGMA_OK;
   });
 }
@@ -164,117 +302,7 @@ int midagma_set_data(midagma_solver* s, const double* X, int64_t n_local, int64_
   if (!on_device && !all_finite(X, n_local, s->d, s->d))
     return abi_fail(s, MIDAGMA_E_ARG, std::string("set_data: ") + kNonFinite);
   return abi_guarded(s, [&] {
-    const int64_t D = s->D;
-    s->n_local = n_local;
-    s->n_global = n_global;
-    s->n_pad = (n_local + 127) / 128 * 128;
-    const size_t nx = (size_t)s->n_pad * D;
-    // experiments build: MIDAGMA_EXP_PREPAD_MB of device memory allocated (and kept) before X, to
-    // move X, X^T and Y elsewhere (the X^T Y GEMM's fetched bytes against placement)
-    if (const long pad = knob("MIDAGMA_EXP_PREPAD_MB", 0); pad > 0 && !s->prepad.p)
-      s->prepad.alloc((size_t)pad << 17);
-    s->X.alloc(nx);
-    // logistic with few 128-tiles: the sigmoid GEMM in two serial K halves when its last round of
-    // tiles would be at most half full (n = 1e4, d = 1000: 632 tiles for 512 resident slots)
-    const int64_t sig_tiles = (s->n_pad / 128) * (D / 128);
-    const int sig_rule = (int)knob("MIDAGMA_EXP_SIG_SPLIT", 1);
-    const bool sig_ok = s->loss == MIDAGMA_LOSS_LOGISTIC && D % 128 == 0 && sig_tiles % 8 == 0;
-    s->sig_split = sig_ok && sig_rule > 0 && sig_tiles < 2048 && sig_tiles % 512 != 0 && sig_tiles % 512 <= 256 ? 2 : 1;
-    if (s->sig_split_force == 1) s->sig_split = 1;  // midagma_debug_sig_split (tests)
-    if (s->sig_split_force == 2 && sig_ok) s->sig_split = 2;
-    if (s->sig_split == 2) {  // the output, the first halves' partial, then one flag word per tile
-      s->Y.alloc(2 * nx + (size_t)(sig_tiles + 1) / 2);
-      HIP_TRY(hipMemsetAsync(s->Y.p + 2 * nx, 0, (size_t)(sig_tiles + 1) / 2 * sizeof(double), s->stream));
-    } else {
-      // experiments build: Y placed MIDAGMA_EXP_Y_OFFSET bytes into its allocation (L2 set
-      // aliasing between X and Y in the X^T Y GEMM)
-      s->Y.alloc_shifted(nx, (size_t)knob("MIDAGMA_EXP_Y_OFFSET", 0) / sizeof(double));
-    }
-    HIP_TRY(hipMemsetAsync(s->X.p, 0, nx * sizeof(double), s->stream));
-    HIP_TRY(hipMemcpy2DAsync(s->X.p, D * sizeof(double), X, s->d * sizeof(double), s->d * sizeof(double), n_local,
-                             on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, s->stream));
-    if (on_device) {  // the host path checked before the copy
-      int* flag = reinterpret_cast<int*>(s->partials.p);
-      launch_any_nonfinite(s->X.p, (int64_t)nx, flag, s->stream);
-      int bad = 0;
-      HIP_TRY(hipMemcpyAsync(&bad, flag, sizeof(int), hipMemcpyDeviceToHost, s->stream));
-      HIP_TRY(hipStreamSynchronize(s->stream));
-      if (bad) throw std::invalid_argument(std::string("set_data: ") + kNonFinite);
-    }
-    size_t mem_free = 0, mem_total = 0;
-    HIP_TRY(hipMemGetInfo(&mem_free, &mem_total));
-    // (the 128-tile GEMM only: D % 128 == 0; smaller problems are not worth the copy)
-    s->use_xt = getenv("MIDAGMA_NO_XT") == nullptr && D % 128 == 0 &&
-                mem_free > nx * sizeof(double) + (size_t(2) << 30);
-    if (s->use_xt) {
-      s->XT.alloc(nx);
-      launch_transpose(s->X.p, D, s->n_pad, D, s->XT.p, s->n_pad, s->stream);
-    } else {
-      s->XT.release();
-    }
-    if (s->loss == MIDAGMA_LOSS_L2 && (D % 128 == 0 || s->w32))  // (float32 W: I - W from build_at)
-      s->IW.alloc((size_t)D * D);
-    else
-      s->IW.release();
-    // split-K over the rows so the X^T Y GEMM fills the chip: (D/64)^2 tiles x split >= ~1024 workgroups
-    const int64_t tiles = (D % 128 == 0) ? (D / 128) * (D / 128) : (D / 64) * (D / 64);
-    const int64_t ktiles = s->n_pad / 64;
-    int split = (int)std::max<int64_t>(1, std::min<int64_t>(ktiles / 8, (1024 + tiles - 1) / tiles));
-    s->split = std::min(split, 32);
-    if (knob_set("MIDAGMA_EXP_DATA_SPLIT")) s->split = (int)knob("MIDAGMA_EXP_DATA_SPLIT", s->split);
-    if (s->split > 1) s->Zparts.alloc((size_t)s->split * D * D);
-    // X^T Y by one level of Strassen (gemm.hip): when the shape allows it (D % 256 == 0), every
-    // product's K slice is long enough to amortise its tile's prologue and epilogue
-    // (kXtyStrassenMinSlice), and the device has room for the five operand sums of X (1.25 x the
-    // size of X; the same free-memory rule as X^T).  Everything else keeps the classical GEMM.
-    s->xty_form = 1;
-    bool strassen = s->xty_form_force != 1 && xty_strassen_shape(D, s->n_pad) && !knob_set("MIDAGMA_EXP_DATA_SPLIT");
-    XtyStrassenPlan plan{};
-    if (strassen) {
-      plan = xty_strassen_plan(D, s->n_pad, s->xty_split_force);
-      if (s->xty_form_force != 2 && plan.kslice < kXtyStrassenMinSlice) strassen = false;
-    }
-    if (strassen) {
-      const size_t nsum = (size_t)xty_strassen_sum_count(D, s->n_pad);
-      HIP_TRY(hipMemGetInfo(&mem_free, &mem_total));
-      strassen = mem_free > nsum * sizeof(double) + (size_t(2) << 30);
-      if (strassen) {
-        try {
-          s->Xsums.alloc(nsum);
-          s->Sparts.alloc((size_t)xty_strassen_part_count(D, plan.nsplit));
-        } catch (const HipError& e) {
-          if (e.code != hipErrorOutOfMemory) throw;
-          (void)hipGetLastError();
-          strassen = false;
-        }
-      }
-    }
-    if (strassen) {
-      launch_xty_strassen_sums(s->X.p, D, s->n_pad, s->Xsums.p, s->stream);
-      s->xty_form = 2;
-      s->xty_split = s->xty_split_force;
-    } else {
-      s->Xsums.release();
-      s->Sparts.release();
-    }
-    s->loss_part_count = (s->n_pad / 64) * (D / 64);
-    // small shards run the cov-mode slot structure: the warm-started fast blocked inverse in
-    // sequence with the GEMMs (hand-backs and checkpoint slots on the pivoted path).  Forked beside
-    // GEMMs that fill the chip, the pivoted inverse's 20-odd dependent launches wait for CU slots
-    // and end after the GEMMs (logistic d=1000, n=1e4: 1.01 ms per slot for 0.70 ms of GEMMs);
-    // large shards keep the fork, which hides it (MIDAGMA_EXP_DATA_FAST_ROWS: the row bound)
-    static const int64_t fast_rows = knob("MIDAGMA_EXP_DATA_FAST_ROWS", 16384);
-    const int b2 = binv_block(D);
-    const int B2_new = (b2 > 0 && s->n_pad <= fast_rows && s->Malt.p) ? b2 : 0;
-    if (B2_new != s->B2) s->graphs_valid = false;
-    s->B2 = B2_new;
-    if (s->loss == MIDAGMA_LOSS_LOGISTIC) {
-      s->loss_part.alloc(s->loss_part_count);
-      HIP_TRY(hipMemsetAsync(s->loss_part.p, 0, s->loss_part_count * sizeof(double), s->stream));
-    }
-    HIP_TRY(hipStreamSynchronize(s->stream));
-    s->has_data = true;
-    s->graphs_valid = false;
+    s->set_data(X, n_local, n_global, on_device != 0);
     return MIDAGMA_OK;
   });
 }
@@ -282,9 +310,7 @@ int midagma_set_data(midagma_solver* s, const double* X, int64_t n_local, int64_
 int midagma_data_gram(midagma_solver* s) {
   if (!s || !s->has_data) return abi_fail(s, MIDAGMA_E_STATE, "data_gram: set_data first");
   return abi_guarded(s, [&] {
-    GemmSpec gs = s->xty_spec();  // X^T X: the X^T Y GEMM with Y = X
-    gs.B = s->X.p;
-    launch_gemm_summed(gs, s->Zparts.p, s->zbuf, nullptr, s->stream);
+    s->data.enqueue_gram(s->zbuf, s->stream);
     HIP_TRY(hipStreamSynchronize(s->stream));
     return MIDAGMA_OK;
   });
@@ -339,14 +365,7 @@ int midagma_comm_init(midagma_solver* s, const void* id, int64_t id_len, int nra
   if (!s || !id || id_len != 128 || nranks < 1 || rank < 0 || rank >= nranks || s->mode != MIDAGMA_MODE_DATA)
     return abi_fail(s, MIDAGMA_E_ARG, "comm_init: bad arguments (data mode, a 128-byte unique id, 0 <= rank < nranks)");
   return abi_guarded(s, [&] {
-    HIP_TRY(hipStreamSynchronize(s->stream));
-    comm_destroy(s->comm);
-    s->comm = nullptr;
-    s->comm = comm_create(id, nranks, rank);
-    s->comm_ranks = nranks;
-    s->agree.alloc(8);
-    s->h_agree.alloc(8);
-    s->graphs_valid = false;  // the slot graphs now carry the all-reduce
+    s->init_comm(id, nranks, rank);
     return MIDAGMA_OK;
   });
 }
@@ -367,7 +386,7 @@ int midagma_bind_zbuf(midagma_solver* s, void* dev_ptr, int64_t len) {
   if (!s || len < s->D * s->D + 64) return abi_fail(s, MIDAGMA_E_ARG, "bind_zbuf: buffer too small");
   return abi_guarded(s, [&] {
     s->zbuf = dev_ptr ? static_cast<double*>(dev_ptr) : s->zown.p;
-    s->graphs_valid = false;
+    s->graphs.valid = false;
     return MIDAGMA_OK;
   });
 }
@@ -399,15 +418,7 @@ int midagma_begin(midagma_solver* s, const double* W, double mu, int64_t max_ite
 int midagma_run_slots(midagma_solver* s, int64_t n) {
   if (!s || !s->begun || n < 0) return abi_fail(s, MIDAGMA_E_STATE, "run_slots: call begin first");
   return abi_guarded(s, [&] {
-    if (s->blocked()) {
-      s->drive_blocked(n);
-      return MIDAGMA_OK;
-    }
-    if (s->small_on()) {
-      s->drive_small(n);
-      return MIDAGMA_OK;
-    }
-    for (int64_t i = 0; i < n; ++i) HIP_TRY(hipGraphLaunch(s->g_full, s->stream));
+    s->run_slots(n);
     return MIDAGMA_OK;
   });
 }
@@ -423,49 +434,7 @@ int midagma_sync(midagma_solver* s) {
 int midagma_profile_parts(midagma_solver* s, int reps, double* ms_out) {
   if (!s || !s->begun || reps < 1 || !ms_out) return abi_fail(s, MIDAGMA_E_STATE, "profile_parts: call begin first");
   return abi_guarded(s, [&] {
-    Event a, b;
-    a.create();
-    b.create();
-    auto timed = [&](auto&& body) {
-      HIP_TRY(hipEventRecord(a, s->stream));
-      for (int r = 0; r < reps; ++r) body();
-      HIP_TRY(hipEventRecord(b, s->stream));
-      HIP_TRY(hipEventSynchronize(b));
-      float ms = 0.f;
-      HIP_TRY(hipEventElapsedTime(&ms, a, b));
-      return (double)ms / reps;
-    };
-    const int64_t D = s->D;
-    // [0] build (sI - W o W)^T   [1] GJ inverse   [2] score GEMM(s)   [3] whole slot (graph)
-    // data mode: [4] Y = X (I - W) GEMM   [5] Z = X^T Y GEMM (+ slice sum)
-    ms_out[0] = timed([&] { launch_build_at(s->W.p, D, true, s->Mt.p, D, s->d, 0.0, s->d_params.p, s->d_state.p,
-                                            s->stream, s->IW.p); });
-    ms_out[1] = timed([&] { launch_gj_inverse(s->Mt.p, D, D, s->gj(), s->d_state.p, s->stream); });
-    if (s->mode == MIDAGMA_MODE_COV) {
-      ms_out[2] = timed([&] { s->enqueue_score_cov(s->zbuf, s->d_state.p, true); });
-      ms_out[4] = ms_out[5] = 0.0;
-    } else {
-      ms_out[2] = timed([&] { s->enqueue_data_partial(s->W.p, s->d_state.p, s->IW.p); });
-      ms_out[4] = timed([&] { s->enqueue_xw(s->W.p, s->d_state.p, s->IW.p); });
-      ms_out[5] = timed([&] { s->enqueue_xty(s->d_state.p); });
-    }
-    ms_out[3] = timed([&] { HIP_TRY(hipGraphLaunch(s->g_full, s->stream)); });
-    ms_out[6] = ms_out[7] = 0.0;
-    if (s->blocked()) {
-      // [6] build + fast blocked inverse, less [0]   [7] whole fast slot (graph).  Both need a
-      // warm start and no pending checkpoint: one slow slot first.
-      HIP_TRY(hipGraphLaunch(s->g_full, s->stream));
-      ms_out[6] = timed([&] { s->enqueue_build_inverse(/*fast=*/true, 2); }) - ms_out[0];
-      ms_out[7] = timed([&] { HIP_TRY(hipGraphLaunch(s->g_fast, s->stream)); });
-      State st{};
-      HIP_TRY(hipMemcpy(&st, s->d_state.p, sizeof(State), hipMemcpyDeviceToHost));
-      if (st.status == ST_NEED_GJ) {  // the fast path did not run: report it, leave a clean state
-        ms_out[6] = ms_out[7] = -1.0;
-        static const int32_t running = ST_RUNNING;
-        HIP_TRY(hipMemcpy(&s->d_state.p->status, &running, sizeof(int32_t), hipMemcpyHostToDevice));
-        s->fast_ready = false;
-      }
-    }
+    s->profile_parts(reps, ms_out);
     return MIDAGMA_OK;
   });
 }
@@ -473,7 +442,7 @@ int midagma_profile_parts(midagma_solver* s, int reps, double* ms_out) {
 int midagma_step_partial(midagma_solver* s) {
   if (!s || !s->begun) return abi_fail(s, MIDAGMA_E_STATE, "step_partial: call begin first");
   return abi_guarded(s, [&] {
-    HIP_TRY(hipGraphLaunch(s->g_part1, s->stream));
+    HIP_TRY(hipGraphLaunch(s->graphs[SlotGraphs::PART1], s->stream));
     return MIDAGMA_OK;
   });
 }
@@ -481,7 +450,7 @@ int midagma_step_partial(midagma_solver* s) {
 int midagma_step_finish(midagma_solver* s) {
   if (!s || !s->begun) return abi_fail(s, MIDAGMA_E_STATE, "step_finish: call begin first");
   return abi_guarded(s, [&] {
-    HIP_TRY(hipGraphLaunch(s->g_part2, s->stream));
+    HIP_TRY(hipGraphLaunch(s->graphs[SlotGraphs::PART2], s->stream));
     return MIDAGMA_OK;
   });
 }
@@ -509,16 +478,7 @@ int midagma_end(midagma_solver* s, double* W, midagma_result* res) {
 int midagma_set_w_float32(midagma_solver* s, int float32) {
   if (!s) return abi_fail(s, MIDAGMA_E_ARG, "null solver");
   return abi_guarded(s, [&] {
-    const bool on = float32 != 0;
-    if (on != s->w32) s->graphs_valid = false;  // the float32 slots carry numpy's L1 sum
-    if (on && !s->l1w.p) s->l1w.alloc((size_t)(1 + (np_l1_chunks(s->d) + 1) / 2));
-    if (on && (s->mode == MIDAGMA_MODE_COV || s->loss == MIDAGMA_LOSS_L2) && !s->IW.p) {
-      // the score GEMM's I - W (float32 diagonal) comes from build_at, not the GEMM's staging
-      s->IW.alloc((size_t)s->D * s->D);
-      HIP_TRY(hipMemsetAsync(s->IW.p, 0, (size_t)s->D * s->D * sizeof(double), s->stream));
-      s->graphs_valid = false;
-    }
-    s->w32 = on;
+    s->set_w_float32(float32 != 0);
     return MIDAGMA_OK;
   });
 }
@@ -532,13 +492,13 @@ extern "C" int64_t midagma_debug_live_bytes(void) { return g_live_bytes.load(); 
 // allows it; -1: no change).  Returns the form the current data uses (1 or 2).
 extern "C" int midagma_debug_sig_split(midagma_solver* s, int mode) {
   if (!s || mode < -1 || mode > 2) return -1;
-  if (mode >= 0) s->sig_split_force = mode;
-  return s->sig_split;
+  if (mode >= 0) s->data.sig_split_force = mode;
+  return s->data.sig_split;
 }
 
 // The form of the data-mode X^T Y GEMM the current data uses: 1 classical, 2 one level of
 // Strassen (0: no data).
-int midagma_xty_form(const midagma_solver* s) { return s && s->has_data ? s->xty_form : 0; }
+int midagma_xty_form(const midagma_solver* s) { return s && s->has_data ? s->data.xty_form : 0; }
 
 // Test hook (not in the public header): choose that form for the next set_data (mode 0: the size
 // rule, 1: always classical, 2: Strassen wherever the shape allows it; -1: no change) and the
@@ -546,9 +506,9 @@ int midagma_xty_form(const midagma_solver* s) { return s && s->has_data ? s->xty
 // change).  Returns the form the current data uses (1 or 2).
 extern "C" int midagma_debug_xty_form(midagma_solver* s, int mode, int split) {
   if (!s || mode < -1 || mode > 2 || split < -1) return -1;
-  if (mode >= 0) s->xty_form_force = mode;
-  if (split >= 0) s->xty_split_force = split;
-  return s->xty_form;
+  if (mode >= 0) s->data.xty_form_force = mode;
+  if (split >= 0) s->data.xty_split_force = split;
+  return s->data.xty_form;
 }
 
 // Test hooks (not in the public header) for the hand-back path of the blocked inverse:
@@ -559,7 +519,7 @@ extern "C" int midagma_debug_xty_form(midagma_solver* s, int mode, int split) {
 extern "C" int midagma_debug_spoil_warm(midagma_solver* s) {
   if (!s || !s->blocked()) return -1;
   return abi_guarded(s, [&] {
-    for (DevBuf<>* b : {&s->Pst2, &s->Pst2b})
+    for (DevBuf<>* b : {&s->binv.Pst2, &s->binv.Pst2b})
       if (b->p) HIP_TRY(hipMemsetAsync(b->p, 0, b->n * sizeof(double), s->stream));
     HIP_TRY(hipStreamSynchronize(s->stream));
     return MIDAGMA_OK;
@@ -570,10 +530,10 @@ extern "C" int64_t midagma_debug_handbacks(const midagma_solver* s) { return s ?
 // it hands back (0: the whole gated chain on every slot; < 0: no change).  Returns the old value.
 extern "C" int midagma_debug_tcc_fast_steps(midagma_solver* s, int steps) {
   if (!s) return -1;
-  const int old = s->tcc_fast_steps;
+  const int old = s->knobs.tcc_fast_steps;
   if (steps >= 0 && steps != old) {
-    s->tcc_fast_steps = steps;
-    s->graphs_valid = false;
+    s->knobs.tcc_fast_steps = steps;
+    s->graphs.valid = false;
   }
   return old;
 }
@@ -582,11 +542,11 @@ extern "C" int midagma_debug_tcc_fast_steps(midagma_solver* s, int steps) {
 // it.  Returns the old setting.
 extern "C" int midagma_debug_tcc_fix(midagma_solver* s, int on) {
   if (!s) return -1;
-  const int old = s->tcc_fix != 0 ? 1 : 0;
+  const int old = s->knobs.tcc_fix != 0 ? 1 : 0;
   if (on >= 0 && (on != 0 ? 1 : 0) != old) {
-    s->tcc_fix = on != 0 ? 1 : 0;
-    s->cw.fix = s->tcc_fix;
-    s->graphs_valid = false;
+    s->knobs.tcc_fix = on != 0 ? 1 : 0;
+    s->trek.tcc.w.fix = s->knobs.tcc_fix;
+    s->graphs.valid = false;
   }
   return old;
 }
@@ -595,23 +555,23 @@ extern "C" int midagma_debug_tcc_fix(midagma_solver* s, int on) {
 // or off (0) for the next set_trek_tcc; < 0 leaves it.  Returns the old setting.
 extern "C" int midagma_debug_tcc_fastblk(midagma_solver* s, int on) {
   if (!s) return -1;
-  const int old = s->tcc_fastblk ? 1 : 0;
-  if (on >= 0) s->tcc_fastblk = on != 0;
+  const int old = s->knobs.tcc_fastblk ? 1 : 0;
+  if (on >= 0) s->knobs.tcc_fastblk = on != 0;
   return old;
 }
 
 // Test hook (not in the public header): build_at folded into the previous slot's update
-// (at_fold, MIDAGMA_EXP_AT_FOLD) on (1) or off (0); < 0 leaves it.  Returns the old setting, or -1
+// (knobs.at_fold) on (1) or off (0); < 0 leaves it.  Returns the old setting, or -1
 // (no handle / the fold cannot apply: not a blocked cov solver).
 extern "C" int midagma_debug_at_fold(midagma_solver* s, int on) {
   if (!s || s->begun) return -1;
-  const int old = s->at_fold ? 1 : 0;
-  if (on < 0 || (on != 0) == s->at_fold) return old;
+  const int old = s->knobs.at_fold > 0 ? 1 : 0;
+  if (on < 0 || (on != 0) == (old != 0)) return old;
   if (on && !(s->mode == MIDAGMA_MODE_COV && s->blocked())) return -1;
   return abi_guarded(s, [&] {
-    if (on && !s->A0.p) s->A0.alloc(s->D * s->D);
-    s->at_fold = on != 0;
-    s->graphs_valid = false;
+    if (on && !s->binv.A0.p) s->binv.A0.alloc(s->D * s->D);
+    s->knobs.at_fold = on != 0;
+    s->graphs.valid = false;
     return old;
   });
 }
@@ -650,13 +610,14 @@ extern "C" int midagma_debug_slot_matrices(midagma_solver* s, double* W_out, dou
 // passes that did not run in the last slot).
 extern "C" int midagma_debug_blocked(midagma_solver* s, double* out, int64_t cap) {
   if (!s || !s->blocked()) return 0;
-  const int64_t K2 = s->D / s->B2, per = NM_PASSES + 2;
+  const int B2 = s->binv.B2, NT = B2 / 16;
+  const int64_t K2 = s->D / B2, per = NM_PASSES + 2;
   if (cap < K2 * per) return -1;
   std::vector<double> part((size_t)K2 * (NM_PASSES + 1) * PART_STRIDE);
   std::vector<int> done(K2);
-  if (hipMemcpy(part.data(), s->nmPart.p, part.size() * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess) return -1;
-  if (hipMemcpy(done.data(), s->nmDone.p, K2 * sizeof(int), hipMemcpyDeviceToHost) != hipSuccess) return -1;
-  const int B2 = s->B2, NT = B2 / 16;
+  if (hipMemcpy(part.data(), s->binv.nmPart.p, part.size() * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess)
+    return -1;
+  if (hipMemcpy(done.data(), s->binv.nmDone.p, K2 * sizeof(int), hipMemcpyDeviceToHost) != hipSuccess) return -1;
   for (int64_t g = 0; g < K2; ++g) {
     out[g * per] = done[g];
     for (int p = 0; p <= NM_PASSES; ++p) {
@@ -711,37 +672,7 @@ int midagma_trek(midagma_solver* s, const double* W, double* value, double* G) {
   if (!s || !W || !value) return abi_fail(s, MIDAGMA_E_ARG, "trek: null argument");
   if (!all_finite(W, s->d, s->d, s->d)) return abi_fail(s, MIDAGMA_E_ARG, std::string("trek: ") + kNonFinite);
   return abi_guarded(s, [&] {
-    const int64_t D = s->D, d = s->d, DD = D * D;
-    if (!s->trek_on) {  // trek_value_grad: (0, zeros) when disabled (notreks.py)
-      *value = 0.0;
-      if (G) std::fill(G, G + d * d, 0.0);
-      return MIDAGMA_OK;
-    }
-    s->scratch.alloc(DD);
-    HIP_TRY(hipMemsetAsync(s->scratch.p, 0, DD * sizeof(double), s->stream));
-    s->upload_matrix(s->scratch, W, d);
-    const double* scal;
-    if (s->trek_tcc) {
-      TccCfg c = s->ccfg;
-      c.weight = 1.0;  // the bare gradient, as trek_value_grad returns it
-      launch_trek_tcc(s->scratch.p, d, D, c, s->cw, s->d_state_probe.p, s->Gtrek.p, s->stream);
-      scal = s->cw.scal;
-    } else {
-      TrekCfg c = s->tcfg;
-      c.weight = 1.0;
-      launch_trek_pst(s->scratch.p, d, D, c, s->tw, s->d_state_probe.p, s->Gtrek.p, s->stream);
-      scal = s->tw.scal;
-    }
-    HIP_TRY(hipMemcpyAsync(value, scal, sizeof(double), hipMemcpyDeviceToHost, s->stream));
-    if (G) {
-      if (s->tcfg.mode == 2) {
-        HIP_TRY(hipMemcpy2DAsync(G, d * sizeof(double), s->Gtrek.p, D * sizeof(double), d * sizeof(double), d,
-                                 hipMemcpyDeviceToHost, s->stream));
-      } else {
-        std::fill(G, G + d * d, 0.0);
-      }
-    }
-    HIP_TRY(hipStreamSynchronize(s->stream));
+    s->eval_trek(W, value, G);
     return MIDAGMA_OK;
   });
 }
@@ -750,67 +681,16 @@ int midagma_h(midagma_solver* s, const double* W, double s_dom, double* h, doubl
   if (!s || !W || !h) return abi_fail(s, MIDAGMA_E_ARG, "h: null argument");
   if (!all_finite(W, s->d, s->d, s->d)) return abi_fail(s, MIDAGMA_E_ARG, std::string("h: ") + kNonFinite);
   return abi_guarded(s, [&] {
-    const int64_t D = s->D, d = s->d, DD = D * D;
-    s->scratch.alloc(DD);
-    HIP_TRY(hipMemsetAsync(s->scratch.p, 0, DD * sizeof(double), s->stream));
-    s->upload_matrix(s->scratch, W, d);
-    DevBuf<> work;
-    work.alloc(DD);
-    launch_build_at(s->scratch.p, D, true, work.p, D, d, s_dom, nullptr, nullptr, s->stream);
-    GJWork gw = s->gj();
-    gw.Pstore = nullptr;
-    launch_gj_inverse(work.p, D, D, gw, nullptr, s->stream);
-    std::vector<double> pl(D);
-    HIP_TRY(hipMemcpyAsync(pl.data(), s->pivlog.p, D * sizeof(double), hipMemcpyDeviceToHost, s->stream));
-    if (G) {
-      s->Gtmp.alloc((size_t)d * d);
-      launch_h_grad(s->scratch.p, work.p, s->Gtmp.p, d, D, s->stream);
-      HIP_TRY(hipMemcpyAsync(G, s->Gtmp.p, (size_t)d * d * sizeof(double), hipMemcpyDeviceToHost, s->stream));
-    }
-    HIP_TRY(hipStreamSynchronize(s->stream));
-    double ld = 0.0;
-    for (int64_t i = 0; i < d; ++i) ld += pl[i];
-    *h = -ld + (double)d * std::log(s_dom);
+    s->eval_h(W, s_dom, h, G);
     return MIDAGMA_OK;
   });
-}
-
-static void host_trace_l1(midagma_solver* s, const double* Wd, const double* Z, double* sd, double* l1) {
-  launch_trace_l1(Wd, Z, s->partials.p, s->d, s->D, s->stream);
-  std::vector<double> part(2 * NRED);
-  HIP_TRY(hipMemcpyAsync(part.data(), s->partials.p, part.size() * sizeof(double), hipMemcpyDeviceToHost,
-                         s->stream));
-  HIP_TRY(hipStreamSynchronize(s->stream));
-  double a = 0.0, b = 0.0;
-  for (int i = 0; i < NRED; ++i) {
-    a += part[2 * i];
-    b += part[2 * i + 1];
-  }
-  *sd = a;
-  if (l1) *l1 = b;
 }
 
 int midagma_score(midagma_solver* s, const double* W, double* loss, double* G) {
   if (!s || !W || !loss) return abi_fail(s, MIDAGMA_E_ARG, "score: null argument");
   if (s->mode != MIDAGMA_MODE_COV || !s->has_cov) return abi_fail(s, MIDAGMA_E_STATE, "score: cov mode with set_cov");
   return abi_guarded(s, [&] {
-    const int64_t D = s->D, d = s->d, DD = D * D;
-    s->scratch.alloc(DD);
-    HIP_TRY(hipMemsetAsync(s->scratch.p, 0, DD * sizeof(double), s->stream));
-    s->upload_matrix(s->scratch, W, d);
-    DevBuf<> rhs;
-    rhs.alloc(DD);
-    // rhs = cov @ (I - W)   (linear.py:85-86)
-    s->enqueue_cov_gemm(s->cov_spec(s->cov.p, false, s->scratch.p, B_IMINUS), rhs.p, nullptr);
-    double sd = 0;
-    host_trace_l1(s, s->scratch.p, rhs.p, &sd, nullptr);
-    *loss = 0.5 * sd;
-    if (G) {
-      s->Gtmp.alloc((size_t)d * d);
-      launch_scale(rhs.p, -1.0, rhs.p, DD, s->stream);  // G_loss = -rhs
-      s->download_matrix(G, rhs.p);
-    }
-    HIP_TRY(hipStreamSynchronize(s->stream));
+    s->eval_score(W, loss, G);
     return MIDAGMA_OK;
   });
 }
@@ -819,14 +699,7 @@ int midagma_score_partial(midagma_solver* s, const double* W) {
   if (!s || !W || s->mode != MIDAGMA_MODE_DATA || !s->has_data)
     return abi_fail(s, MIDAGMA_E_STATE, "score_partial: data mode with set_data");
   return abi_guarded(s, [&] {
-    const int64_t DD = s->D * s->D;
-    s->scratch.alloc(DD);
-    HIP_TRY(hipMemsetAsync(s->scratch.p, 0, DD * sizeof(double), s->stream));
-    s->upload_matrix(s->scratch, W, s->d);
-    HIP_TRY(hipMemsetAsync(s->zbuf + DD, 0, 64 * sizeof(double), s->stream));
-    // Force loss partials: pass no state (st == nullptr computes them unconditionally).
-    s->enqueue_data_partial(s->scratch.p, nullptr);
-    HIP_TRY(hipStreamSynchronize(s->stream));
+    s->score_partial(W);
     return MIDAGMA_OK;
   });
 }
@@ -834,32 +707,7 @@ int midagma_score_partial(midagma_solver* s, const double* W) {
 int midagma_score_finish(midagma_solver* s, double* loss, double* G) {
   if (!s || !loss || s->mode != MIDAGMA_MODE_DATA) return abi_fail(s, MIDAGMA_E_STATE, "score_finish: data mode");
   return abi_guarded(s, [&] {
-    const int64_t D = s->D, d = s->d, DD = D * D;
-    const double n = (double)s->n_global;
-    if (s->loss == MIDAGMA_LOSS_L2) {
-      // loss = 0.5 tr((I-W)^T cov (I-W)) with cov (I-W) = Z / n ; G = -Z / n
-      double sd = 0;
-      host_trace_l1(s, s->scratch.p, s->zbuf, &sd, nullptr);
-      *loss = 0.5 * (sd / n);
-      if (G) {
-        std::vector<double> z((size_t)d * d);
-        s->download_matrix(z.data(), s->zbuf);
-        HIP_TRY(hipStreamSynchronize(s->stream));
-        for (size_t i = 0; i < z.size(); ++i) G[i] = -(z[i] / n);
-      }
-    } else {
-      double tail = 0;
-      HIP_TRY(hipMemcpyAsync(&tail, s->zbuf + DD, sizeof(double), hipMemcpyDeviceToHost, s->stream));
-      HIP_TRY(hipStreamSynchronize(s->stream));
-      *loss = 1.0 / n * tail;
-      if (G) {
-        std::vector<double> z((size_t)d * d), c((size_t)d * d);
-        s->download_matrix(z.data(), s->zbuf);
-        s->download_matrix(c.data(), s->cov.p);
-        HIP_TRY(hipStreamSynchronize(s->stream));
-        for (size_t i = 0; i < z.size(); ++i) G[i] = (1.0 / n) * z[i] - c[i];
-      }
-    }
+    s->score_finish(loss, G);
     return MIDAGMA_OK;
   });
 }
@@ -891,10 +739,10 @@ extern "C" int midagma_debug_df_plan(int64_t D, int passes, int nwg, double* est
 // plan order: wait start, go, done; 100 MHz ticks), with MIDAGMA_DF_STAMPS set at create.
 // Returns the number of values copied, or -1.
 extern "C" int64_t midagma_debug_df_stamps(midagma_solver* s, unsigned long long* out, int64_t cap) {
-  if (!s || !s->dfw.stamps) return -1;
-  const int64_t n = std::min<int64_t>(cap, (int64_t)s->dfStamps.n);
+  if (!s || !s->df.w.stamps) return -1;
+  const int64_t n = std::min<int64_t>(cap, (int64_t)s->df.Stamps.n);
   if (hipStreamSynchronize(s->stream) != hipSuccess) return -1;
-  if (hipMemcpy(out, s->dfStamps.p, n * sizeof(unsigned long long), hipMemcpyDeviceToHost) != hipSuccess) return -1;
+  if (hipMemcpy(out, s->df.Stamps.p, n * sizeof(unsigned long long), hipMemcpyDeviceToHost) != hipSuccess) return -1;
   return n;
 }
 #endif  // MIDAGMA_EXPERIMENTS

@@ -114,3 +114,25 @@ def test_dagma_linear_pst_fit_runs(hip):
     assert abs(tv - v_ref) <= 1e-11 * v_ref
     with pytest.raises(ValueError):
         DagmaLinear("l2", trek_reg=reg("nope"))
+
+
+def test_rejected_set_trek_keeps_the_previous_regularizer(hip):
+    """A set_trek the library rejects after its allocations (a pair index out of range) leaves the
+    handle on the regularizer it had: the same value and gradient as before, bit for bit, from the
+    launch view of the accepted call (an 'inv' view under the kept 'exp' configuration would lack
+    the Taylor buffers)."""
+    d = 20
+    _, pairs = _trek_case(d, 7)
+    W = np.random.default_rng(1).uniform(-0.3, 0.3, (d, d))
+    np.fill_diagonal(W, 0)
+    s = _solver(d, np.eye(d))
+    s.set_trek(pairs, "exp", agg="mean", mode="opt", weight=0.5)
+    v0, g0 = s.trek_value(W)
+    bad = np.vstack([pairs[:3], [[1, d]]])
+    with pytest.raises(ValueError):
+        s.set_trek(bad, "inv", agg="mean", mode="opt", weight=0.5)
+    v1, g1 = s.trek_value(W)
+    v_ref, g_ref = pst_value_grad(W, pairs, "exp")
+    assert v1 == v0 and np.array_equal(g1, g0)
+    assert abs(v1 - v_ref) <= 1e-11 * max(1.0, abs(v_ref))
+    s.close()
